@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the Step-2 FDTD hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config C3] [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--config C3] [--scaling weak|strong] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline and nothing else: it sets up the workload, runs W untimed steps (more if W steps are
+shorter than 0.35 s of load), times exactly K steps, writes the outputs of the timed path with --dump-outputs and prints the
+line. `--full` adds everything else this file measures or checks, after the headline: the per-kernel pass with its roofline,
+the CPU baseline, the shear medium, the production schedule, the placement bound, the 1024^3 and group figures, the Rayleigh /
+BHTE rates, and the multi-rank exchange checks; the `--no-*` options leave single blocks of --full out.
 
 A "step" is one full time step (stress half-step + velocity half-step + RMS accumulation + sensor capture when due)
 over the whole domain. Workload at N=1: BASELINE.json configs[2] ("512^3 CT-derived heterogeneous skull, CTX500
@@ -19,14 +25,15 @@ Without a launcher (`WORLD_SIZE` unset) `--gpus N` with N > 1 runs the ONE-PROCE
 (bfd_group_*, what PropagationModel(devices=[...]) uses; the reference's caller is one process making one call,
 BabelIntegrationBASE.py:2338): headline = strong scaling of ONE C5 volume (1024^3) over devices 0..N-1, the weak-scaling C3
 figure as a secondary block. If fewer than N devices are visible the ordinals repeat and the line says "emulated": true.
-Under torchrun the ranks take the RCCL path (slab.py) and rank 0 adds `group_strong_c3` (one 512^3 C3 volume split over the N
+Under torchrun the ranks take the RCCL path (slab.py) and with --full rank 0 adds `group_strong_c3` (one 512^3 C3 volume split over the N
 devices through bfd_group) after the ranks have released their slabs; `--gpus 1` adds `group_one_slab`.
 
-Prints ONE JSON line on rank 0. `value` = voxel-steps of all ranks / max-over-ranks wall time of K timed steps (median of
-`--windows` windows of exactly K steps, each between barrier + synchronize; min / max beside it; inputs resident in HBM), in
-Mvoxel-steps/s. `roofline` describes the kernel with the longest average launch:
+Prints ONE JSON line on rank 0. `value` = voxel-steps of all ranks / max-over-ranks wall time of K timed steps (one window of
+exactly K steps between barrier + synchronize; with `--windows 3` the median of three such windows, min / max beside it; inputs
+resident in HBM), in Mvoxel-steps/s, and `ms_per_step` the milliseconds one timed step took. `roofline` describes the whole time
+step in a plain run (algorithmic bytes of a step / time per step) and with --full the kernel with the longest average launch:
 achieved = ALGORITHMIC bytes of one launch (per-cell byte tables of the tile classes the engine built, DESIGN.md
-section 6; bfd_algorithmic_bytes) / average launch duration from HIP events on the engine's stream. At N=1 the line also
+section 6; bfd_algorithmic_bytes) / average launch duration from HIP events on the engine's stream. With --full, at N=1 the line also
 carries `shear_workload` (the C2 medium -- cortical bone with shear -- on the same 512^3 grid: the viscoelastic kernels)
 and `cpu_baseline` (the oracle on this host's cores).
 """
@@ -51,6 +58,8 @@ METRIC = 'Mvoxel-steps/sec, 512^3 skull FDTD per device (achieved HBM GB/s in ro
 RAYLEIGH_SIMD_CYCLES_PER_PAIR = 864.0 / 8 / 64
 RAYLEIGH_PEAK_GPAIRS = 1024 * 2.4 / RAYLEIGH_SIMD_CYCLES_PER_PAIR        # 1024 SIMDs x 2.4 GHz
 PROFILE_STALE_TOL = 0.03       # a committed PMC profile describes the running binary while its kernel's live launch average stays within 3 % of the profiled one
+DUMP_BYTES = 48 << 20          # --dump-outputs: all arrays of one run together (float32)
+DUMP_SEED = 20240607           # --dump-outputs: the sample of an array larger than its share depends on its size alone
 
 
 def parse():
@@ -58,7 +67,13 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--warmup', type=int, default=50)
-    ap.add_argument('--windows', type=int, default=3, help='timed windows of K steps each; value = the median window (SURVEY 8d: median of >= 3 runs)')
+    ap.add_argument('--windows', type=int, default=1, help='timed windows of K steps each; value = the median window (default 1: --steps is the number of timed steps; 3 for a median of three)')
+    ap.add_argument('--full', action='store_true', help='after the headline, run every secondary block and check (CPU baseline, shear medium, per-kernel pass and roofline, '
+                                                        'production schedule, placement bound, 1024^3 and group figures, Rayleigh / BHTE rates, multi-rank checks); '
+                                                        'without it the run sets up, warms up, times K steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the timed path computed (Pressure RMS map, last Pressure map, '
+                                                                         'sensor series) as DIR/<name>.npy, float32; arrays larger than their share of %d MiB as a fixed '
+                                                                         'seeded sample' % (DUMP_BYTES >> 20))
     ap.add_argument('--config', default='C3')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak')
     ap.add_argument('--size', type=int, nargs=3, default=None, help='override the grid N1 N2 N3 (per GPU if weak, total if strong)')
@@ -80,7 +95,7 @@ def parse():
     ap.add_argument('--strong-c5-steps', type=int, default=30, help='timed steps of the strong_c5 block (14 ms each on one device)')
     ap.add_argument('--no-group', action='store_true', help='skip the one-process bfd_group figures (group_one_slab at N=1, group_strong_c3 under torchrun)')
     ap.add_argument('--production-call', action='store_true', help='N=1: also time ONE production-shaped drop-in call of the config (nt from the caller\'s time plan, RMS over the last 2 periods, full sensor block) with the tile runs ahead of the wave front returning at entry (library default) and with every run working (BFD_SKIP_ZERO=0); adds about a minute at C3')
-    ap.add_argument('--watchdog-seconds', type=float, default=1200.0, help='rank 0 / the launcher-free process: after this long the line is printed with whatever blocks have finished (a headline that was measured must not be lost to a secondary block that hangs on hardware nobody has run it on); 0 = off')
+    ap.add_argument('--watchdog-seconds', type=float, default=540.0, help='rank 0 / the launcher-free process: after this long the line is printed with whatever blocks have finished (a headline that was measured must not be lost to a secondary block that hangs on hardware nobody has run it on); 0 = off')
     ap.add_argument('--no-next-rows', action='store_true', help='skip the Rayleigh / BHTE kernel rates (N=1, default workload only)')
     ap.add_argument('--no-extra-strong', action='store_true', help='N > 1: skip the extra block that splits ONE C5 volume (1024^3, 1 MHz) over the ranks')
     ap.add_argument('--extra-strong-steps', type=int, default=40, help='timed steps of the extra strong-scaling block')
@@ -247,6 +262,34 @@ def profile_traffic(config, n1, n2, n3, variant):
         return t.get('%s_%dx%dx%d_variant%d' % (config, n1, n2, n3, variant), {})
     except Exception:
         return {}
+
+
+def dump_outputs(src, outdir, tag='', share=1):
+    """--dump-outputs: what a caller of the timed path receives after its last step, from an Engine or a Group `src`: the RMS / peak
+    maps (`selRMSorPeak`), the last maps and the sensor series, as outdir/<name><tag>.npy in float32. An array with more elements than
+    its share of DUMP_BYTES / `share` is written as the elements at a fixed seeded set of flat indices (sorted, depending on the array's
+    size only), so that two builds given the same arguments write comparable files. Returns {name: [elements written, elements]}."""
+    from babelbrain_amd._engine import KIND_LAST, KIND_PEAK, KIND_RMS
+    mode = int(src.cfg.selRMSorPeak)
+    getters = [('rms_%s' % n, lambda n=n: src.get_map(KIND_RMS, n)) for n in src.selR if mode & 1]
+    getters += [('peak_%s' % n, lambda n=n: src.get_map(KIND_PEAK, n)) for n in src.selR if mode & 2]
+    getters += [('last_%s' % n, lambda n=n: src.get_map(KIND_LAST, n)) for n in src.selR]
+    sensors = []
+    if src.selS:
+        getters += [('sensor_%s' % n, lambda q=q: sensors[0][q]) for q, n in enumerate(src.selS)]
+    cap = DUMP_BYTES // 4 // (len(getters) * max(share, 1))
+    os.makedirs(outdir, exist_ok=True)
+    done = {}
+    for name, get in getters:
+        if name.startswith('sensor_') and not sensors:
+            sensors.append(src.sensors())
+        a = np.ascontiguousarray(get(), np.float32)
+        total = int(a.size)
+        if total > cap:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, cap))]
+        np.save(os.path.join(outdir, name + tag + '.npy'), a)
+        done[name] = [int(a.size), total]
+    return done
 
 
 class Workload:
@@ -456,7 +499,7 @@ def single_domain_check(args, rank, world, local_rank, dist, dt_fn):
     return out[0]
 
 
-def group_run(args, config, N, ndev, dt_fn, steps, warmup, windows, variant, label):
+def group_run(args, config, N, ndev, dt_fn, steps, warmup, windows, variant, label, dump=None):
     """ONE volume split into `ndev` Z-slabs inside the library (bfd_group_*): the path PropagationModel(devices=[...]) takes.
     Devices 0 .. ndev-1 when that many are visible, otherwise the visible ordinals repeat ("emulated")."""
     from babelbrain_amd import _engine, harness as H, RayleighAndBHTE
@@ -491,6 +534,7 @@ def group_run(args, config, N, ndev, dt_fn, steps, warmup, windows, variant, lab
             g.timing_begin()
             g.run(steps)
             rows.append(g.timing_end())
+        dumped = dump_outputs(g, dump) if dump else None
         order = sorted(range(len(rows)), key=lambda i: rows[i]['total_ms'])
         tm = rows[order[len(order) // 2]]
         slabs = [g.slab(r) for r in range(g.size)]
@@ -511,6 +555,8 @@ def group_run(args, config, N, ndev, dt_fn, steps, warmup, windows, variant, lab
                'slabs': [[k0, nk, dev] for k0, nk, dev, _ in slabs], 'device_bytes': int(g.device_bytes), 'host_build_s': host_build, 'setup_s': setup,
                'dt': info['dt'], 'ppp': info['ppp'], 'n_sources': info['n_sources'], 'medium': info['medium'], 'tx': info['tx'], 'n_mat': info['n_mat'],
                'array_placement_slab0': slabs[0][3].placement_note()}
+        if dump:
+            out['dumped'] = dumped
         if alg == alg and alg > 0:
             ach = alg / (tm['total_ms'] / steps * 1e-3) / 1e9
             out['roofline_step'] = {'achieved': ach, 'peak': HBM_PEAK_GBS * (1 if emulated else ndev), 'frac': ach / (HBM_PEAK_GBS * (1 if emulated else ndev)),
@@ -721,7 +767,7 @@ def main_group(args):
                        'parallelism': 'z-slab x%d, one process' % ndev, 'kernel_variant': args.variant, 'launcher': 'none (bfd_group_*)'}}
     watch_line(line)
     try:
-        head = group_run(args, cfgname, dims, ndev, dt_fn, args.steps, args.warmup, args.windows, args.variant, what)
+        head = group_run(args, cfgname, dims, ndev, dt_fn, args.steps, args.warmup, args.windows, args.variant, what, dump=args.dump_outputs)
     except Exception as e:          # a first-ever failure on real hardware (peer access, memory) must still leave a line
         head = None
         line['error'] = repr(e)
@@ -742,12 +788,15 @@ def main_group(args):
             line['roofline'] = dict(bound='hbm', kernel='whole time step, all slabs', achieved=r['achieved'], peak=r['peak'], unit='GB/s', frac=r['frac'], traffic=None,
                                     note='algorithmic bytes of the slabs per step / wall time per step; peak = 8 TB/s x distinct devices; the per-kernel figures are in the N=1 line')
             line['roofline_step'] = r
+    if head is not None and args.dump_outputs:
+        line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': head['dumped'], 'note': '[elements written, elements of the array]'}
     line['cpu_baseline'] = {'value': None, 'note': 'timed at N=1 only'}
-    try:
-        line['group_check'] = group_equals_single(args, ndev, dt_fn, args.variant)
-    except Exception as e:
-        line['group_check'] = {'equals_single_domain': None, 'error': repr(e)}
-    if not args.no_strong_c5 and not args.no_extra_strong:
+    if args.full:
+        try:
+            line['group_check'] = group_equals_single(args, ndev, dt_fn, args.variant)
+        except Exception as e:
+            line['group_check'] = {'equals_single_domain': None, 'error': repr(e)}
+    if args.full and not args.no_strong_c5 and not args.no_extra_strong:
         line['strong_c5'] = strong_c5(args, ndev, dt_fn, args.variant)
     if stop_watchdog():
         roofline_summary(line)
@@ -816,12 +865,16 @@ def roofline_summary(line):
                     r['next_%s_%s' % (k, a)] = nr[k][a]
 
 
-def measure(w, args, traffic):
-    """Runs the passes of one workload; returns the fields of its JSON block (rank 0 uses them)."""
-    check = w.check_exchange()
+def measure(w, args, traffic, dump=None):
+    """Runs the passes of one workload; returns the fields of its JSON block (rank 0 uses them). `dump`: directory for
+    dump_outputs, written right after the timed window (before the per-kernel pass of --full steps the engine further)."""
+    check = w.check_exchange() if args.full else None
     wall, tm = w.timed()
+    dumped = None
+    if dump:
+        dumped = dump_outputs(w.eng, dump, tag='' if w.world == 1 else '_rank%d' % w.rank, share=w.world)
     value = w.total_vox * w.steps / wall / 1e6
-    out = {'value': value, 'ms_per_step': wall / w.steps * 1e3, 'exchange_check': check,
+    out = {'value': value, 'ms_per_step': wall / w.steps * 1e3, 'exchange_check': check, 'dumped': dumped,
            'windows': {'n': len(w.window_walls), 'steps_each': w.steps, 'ms_per_step': [x / w.steps * 1e3 for x in w.window_walls],
                        'value_min': w.total_vox * w.steps / max(w.window_walls) / 1e6, 'value_max': w.total_vox * w.steps / min(w.window_walls) / 1e6,
                        'note': 'value = the median window'},
@@ -836,7 +889,7 @@ def measure(w, args, traffic):
                                 'dense_accounting': {'bytes_per_voxel_step': BYTES_STEP_DENSE,
                                                      'achieved': BYTES_STEP_DENSE * w.nvox_rank / (tm['total_ms'] / w.steps * 1e-3) / 1e9,
                                                      'note': 'SURVEY 8d figure (all 15 arrays of every voxel); the tiled kernels move fewer bytes, so this is not a roofline fraction'}}
-        if not args.no_kernel_pass:
+        if args.full and not args.no_kernel_pass:
             nk = min(w.steps, 60)
             tk, kt = w.kernel_pass(nk)
             out['half_steps'] = {'stress_ms': tk['stress_ms'] / nk, 'velocity_ms': tk['velocity_ms'] / nk, 'other_ms': tk['other_ms'] / nk,
@@ -883,13 +936,13 @@ def main():
         return _engine.stable_dt(ml, f, True, h, acfl)
 
     sd_check = None
-    if world > 1 and not args.no_single_domain_check and args.variant != 1:
+    if world > 1 and args.full and not args.no_single_domain_check and args.variant != 1:
         sd_check = single_domain_check(args, rank, world, local_rank, dist, dt_fn)      # catches locally and agrees across the ranks
     cfg = H.CONFIGS[args.config]
     dims = tuple(args.size) if args.size else cfg['N']
     w = Workload(args, args.config, dims, args.scaling, rank, world, local_rank, dist, dt_fn, args.steps, args.warmup, args.variant)
     traffic = profile_traffic(args.config, dims[0], dims[1], w.sinfo['nk'], args.variant)
-    res = measure(w, args, traffic)
+    res = measure(w, args, traffic, dump=args.dump_outputs)
     info, eng = w.info, w.eng
     line = None
     if rank == 0:
@@ -926,14 +979,17 @@ def main():
         elif 'roofline_step' in res:
             s = res['roofline_step']
             line['roofline'] = dict(bound='hbm', kernel='whole time step', achieved=s['achieved'], peak=HBM_PEAK_GBS, unit='GB/s', frac=s['frac'],
-                                    traffic=None, note=note)
+                                    traffic=None, note='achieved = algorithmic bytes of one whole time step (bfd_algorithmic_bytes / DESIGN.md 6) '
+                                                       '/ time per step of the timed window; the per-kernel figures come from the pass of --full')
         if 'roofline_step' in res:
             line['roofline_step'] = res['roofline_step']
+        if args.dump_outputs:
+            line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': res['dumped'], 'note': '[elements written, elements of the array]'}
     if rank == 0:
         watch_line(line)
     w.close()
 
-    if world > 1 and not args.no_extra_strong and not (args.config == 'C5' and args.scaling == 'strong'):
+    if world > 1 and args.full and not args.no_extra_strong and not (args.config == 'C5' and args.scaling == 'strong'):
         # the curve BASELINE.json's north_star names: ONE 1024^3 volume (C5, 1 MHz) split over the N ranks -- beside the weak-
         # scaling headline above, in the same line, because the driver's invocation carries no --config / --scaling.
         # The build is local to every rank; the ranks agree that all of them succeeded BEFORE the first collective of the block
@@ -959,7 +1015,7 @@ def main():
             line['strong_c5'] = {'value': None, 'error': err or 'another rank failed to build its slab'}
         if wx is not None:
             wx.close()
-    if world > 1 and not args.no_group:
+    if world > 1 and args.full and not args.no_group:
         # the path the reference's caller gets (one process, one call): ONE 512^3 C3 volume split over the N devices through
         # bfd_group_*, run by rank 0 after every rank has released its slabs; the other ranks wait at the barrier below
         # the other ranks wait on a CPU-side (gloo) barrier: a rank waiting in an RCCL barrier keeps a kernel spinning on its GPU,
@@ -994,7 +1050,7 @@ def main():
             line['group_strong_c3'] = {'value': None, 'error': 'no CPU-side (gloo) group on every rank: the child would be measured beside ranks spinning in an RCCL barrier'}
         if have_cpu_group:
             dist.barrier(group=cpu_group)
-    if world == 1 and not args.no_wide_placement and args.placement_search_gib < 0 and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_wide_placement and args.placement_search_gib < 0 and args.config == 'C3' and not args.size:
         # the same workload, same engine, under the 64 GiB bound the library had as its default in round 4: what that bound cost on THIS box
         # (on most boxes nothing: exchanging the buffers, or a short walk, suffices)
         try:
@@ -1007,17 +1063,17 @@ def main():
             ww.close()
         except Exception as e:
             line['bounded_placement_search'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.no_strong_c5 and not args.no_group and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_strong_c5 and not args.no_group and args.config == 'C3' and not args.size:
         try:       # the first point of the 1024^3 strong-scaling curve, in the line the driver records at N = 1
             line['strong_c5'] = strong_c5(args, 1, dt_fn, args.variant)
         except Exception as e:
             line['strong_c5'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.no_group and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_group and args.config == 'C3' and not args.size:
         try:       # the same workload through the one-process group path with one slab: SCALE N=1 on both paths
             line['group_one_slab'] = group_run(args, 'C3', dims, 1, dt_fn, args.steps, args.warmup, 1, args.variant, 'one slab through bfd_group_*')
         except Exception as e:
             line['group_one_slab'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.no_shear_workload and args.variant in (0, 3) and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_shear_workload and args.variant in (0, 3) and args.config == 'C3' and not args.size:
         # the viscoelastic kernels: C2's medium (water / cortical bone with shear / brain) on the same 512^3 grid, same K/W
         try:
             ws = Workload(args, 'C2', dims, 'weak', 0, 1, local_rank, None, dt_fn, args.steps, args.warmup, args.variant, full_sensors=True)
@@ -1029,7 +1085,7 @@ def main():
             ws.close()
         except Exception as e:
             line['shear_workload'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.no_production_schedule and args.variant in (0, 3) and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_production_schedule and args.variant in (0, 3) and args.config == 'C3' and not args.size:
         # what ONE production call of the reference's caller spends its steps on: nt steps of the config's time plan
         # (BASE:2082-2109), the Pressure RMS accumulated over the last 2 periods only. `value` above prices every step as an
         # accumulating one; here the steps before the window are timed too and the two rates are weighted by the plan.
@@ -1065,7 +1121,7 @@ def main():
             wd.close()
         except Exception as e:
             line['dense_reference'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.no_next_rows and args.config == 'C3' and not args.size:
+    if world == 1 and args.full and not args.no_next_rows and args.config == 'C3' and not args.size:
         try:
             line['next_rows'] = next_rows(local_rank)
         except Exception as e:
@@ -1075,7 +1131,9 @@ def main():
             line['production_call'] = production_call(args, dt_fn, local_rank)
         except Exception as e:
             line['production_call'] = {'error': repr(e)}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and not args.full:
+        line['cpu_baseline'] = {'value': None, 'note': 'measured with --full'}
+    elif world == 1 and not args.no_cpu_baseline:
         try:
             line['cpu_baseline'] = cpu_baseline(args, dt_fn)
         except Exception as e:   # the baseline is a reported extra; never lose the GPU line over it

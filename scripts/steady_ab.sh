@@ -1,7 +1,7 @@
 # A/B at steady clocks (default K/W = 600/300), same box
 run() { # label, env..., -- bench args
   label=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --no-dense-reference $BARGS 2>/dev/null | python -c "
+  env "$@" python bench.py --no-cpu-baseline --full $BARGS 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$label', d['config']['workload'][:3], round(d['value']), round(d['ms_per_step'],4), 'stress/vel ms', [round(d['roofline']['avg_launch_ms'],4), round(d['roofline_other']['avg_launch_ms'],4)])"
 }
 for r in 1 2; do

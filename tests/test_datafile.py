@@ -75,11 +75,11 @@ def test_errors(tmp_path):
         DF.SaveToH5py([1, 2], str(tmp_path / 'x.h5'))
 
 
-@pytest.mark.skipif(not os.path.isfile('/root/reference/TranscranialModeling/MapPichardo.h5'), reason='reference tree not present')
 def test_reads_the_reference_file_itself(golden):
-    """Blosc-compressed, written by the real H5pySimple: only where the reference tree is mounted."""
+    """Blosc-compressed, written by the real H5pySimple: an excerpt of the reference's file that keeps its compressed chunks
+    byte for byte (tests/golden/pichardo_excerpt.h5, cut by tests/golden/make_pichardo_fixture.py)."""
     g, meta = golden
-    mp = DF.ReadFromH5py('/root/reference/TranscranialModeling/MapPichardo.h5', use_h5py=False)
+    mp = DF.ReadFromH5py(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'pichardo_excerpt.h5'), use_h5py=False)
     assert sorted(mp) == sorted(meta['h5pysimple_layout'])
     assert np.array_equal(mp['rho'][:6], g['h5_pichardo_rho_head'])
     assert np.array_equal(mp['MapSoS'][:3, :3], g['h5_pichardo_sos_corner'])

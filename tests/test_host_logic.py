@@ -282,3 +282,39 @@ def test_bench_watchdog_prints_the_line_it_has():
     r = subprocess.run([sys.executable, '-c', head + "bench.watch_line({'value': 1.0}); ok = bench.stop_watchdog(); time.sleep(0.6); print('finished', ok)"],
                        cwd=root, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.strip().splitlines() == ['finished True']
+
+
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output of the timed path as <name>.npy in float32, all of them within DUMP_BYTES; an array larger
+    than its share is the same seeded sample of its flat indices on every call, small arrays go whole with their shape."""
+    import argparse
+    import sys
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 3 * 4 * 1000)       # 1000 float32 per array
+
+    class Src:
+        cfg = argparse.Namespace(selRMSorPeak=1)
+        selR, selS = ('Pressure',), ('Pressure',)
+
+        def get_map(self, kind, name):
+            return np.arange(40 * 30 * 20, dtype=np.float32).reshape(40, 30, 20) * (kind + 1)
+
+        def sensors(self):
+            return np.linspace(0, 1, 1 * 25 * 8, dtype=np.float32).reshape(1, 25, 8)
+    a = bench.dump_outputs(Src(), str(tmp_path / 'a'))
+    b = bench.dump_outputs(Src(), str(tmp_path / 'b'))
+    assert a == b and sorted(a) == ['last_Pressure', 'rms_Pressure', 'sensor_Pressure']
+    assert a['rms_Pressure'][1] == 24000 and 900 < a['rms_Pressure'][0] <= 1000 and a['sensor_Pressure'] == [200, 200]
+    total = 0
+    for name in a:
+        x, y = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= bench.DUMP_BYTES
+    rms = np.load(str(tmp_path / 'a' / 'rms_Pressure.npy'))
+    assert np.all(np.diff(rms) > 0) and float(rms.max()) < 24000          # distinct elements of the map, in index order
+    assert np.load(str(tmp_path / 'a' / 'sensor_Pressure.npy')).shape == (25, 8)           # Sensor['Pressure'] of the call
+    # a plain run: one window of exactly --steps, nothing of --full, no dump
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '3'])
+    args = bench.parse()
+    assert args.steps == 7 and args.windows == 1 and not args.full and args.dump_outputs is None
