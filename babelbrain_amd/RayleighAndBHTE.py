@@ -8,7 +8,8 @@
 
 ForwardSimple runs on the MI355X through the C ABI (bfd_rayleigh_forward); there is no CPU fallback.
 BHTE / BHTEMultiplePressureFields (CalculateTemperatureEffects.py:365-456, 960-990) run on the device too
-(bfd_bhte_run_fields: four time steps per pass, csrc/bfd_bhte.hip).
+(bfd_bhte_run_fields: four time steps per pass, csrc/bfd_bhte.hip). RunBHTECycles replaces the caller's own loop over them
+(CalculateTemperatureEffects.py:259-460) with one device call for the whole protocol (bfd_bhte_run_protocol).
 """
 import ctypes as C
 import os
@@ -189,10 +190,8 @@ def bhte_pass_plan(sched, nFactorMonitoring=1, monitored_plane=True, steps_heati
     return out
 
 
-def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, nFactorMonitoring, dt, blood_rho, blood_ct,
-              stableTemp, DutyCycle, MonitoringPointsMap, initT0, initDose):
-    global last_kernel_ms
-    lib = _engine.load_library()
+def _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, blood_rho, blood_ct, DutyCycle, MonitoringPointsMap, initT0, initDose):
+    """Host-side checks and the arrays every bfd_bhte_run_* call takes (no device call)."""
     P = np.asarray(fields)
     nF, N1, N2, N3 = P.shape
     mm = np.asarray(MaterialMap)
@@ -207,7 +206,6 @@ def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, 
     # first like the oracle does): no transposes; the heat source q = (p p) qf[material] is computed on the device and comes back.
     mat = np.ascontiguousarray(mm, np.uint8)
     P32 = np.ascontiguousarray(P, np.float32)
-    q = np.empty((nF, N1, N2, N3), np.float32)
     flags = 0
     if initT0 is not None:
         T = np.array(initT0, np.float32, order='C'); flags |= 1
@@ -222,14 +220,7 @@ def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, 
     else:
         dose = np.empty((N1, N2, N3), np.float32)
     initT = np.ascontiguousarray(MaterialList['InitTemperature'], np.float32)
-    nSteps = len(sched)
-    fm = max(int(nFactorMonitoring), 1)
-    slice_ok = LocationMonitoring is not None and int(LocationMonitoring) >= 0
-    if slice_ok and int(LocationMonitoring) >= N2:
-        raise ValueError('LocationMonitoring is outside the volume')
-    nS = (nSteps + fm - 1) // fm if slice_ok else 0
-    mon = np.zeros((N1, N3, nS), np.float32) if slice_ok else None
-    idx = pts = None
+    idx = None
     if MonitoringPointsMap is not None:
         mp = np.asarray(MonitoringPointsMap)
         if mp.shape != (N1, N2, N3):
@@ -238,17 +229,38 @@ def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, 
         lin = np.flatnonzero(mp)
         order = np.argsort(mp[lin], kind='stable')               # point ids 1..n label the rows
         idx = np.ascontiguousarray(lin[order], np.uint32)
-        pts = np.zeros((len(idx), nSteps), np.float32)
+    return dict(shape=(nF, N1, N2, N3), nMat=nMat, mat=mat, cd=cd, cp=cp, qf=qf, initT=initT, P32=P32, T=T, dose=dose, flags=flags, idx=idx)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, nFactorMonitoring, dt, blood_rho, blood_ct,
+              stableTemp, DutyCycle, MonitoringPointsMap, initT0, initDose):
+    global last_kernel_ms
+    lib = _engine.load_library()
+    v = _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, blood_rho, blood_ct, DutyCycle, MonitoringPointsMap, initT0, initDose)
+    nF, N1, N2, N3 = v['shape']
+    T, dose, idx = v['T'], v['dose'], v['idx']
+    q = np.empty((nF, N1, N2, N3), np.float32)
+    nSteps = len(sched)
+    fm = max(int(nFactorMonitoring), 1)
+    slice_ok = LocationMonitoring is not None and int(LocationMonitoring) >= 0
+    if slice_ok and int(LocationMonitoring) >= N2:
+        raise ValueError('LocationMonitoring is outside the volume')
+    nS = (nSteps + fm - 1) // fm if slice_ok else 0
+    mon = np.zeros((N1, N3, nS), np.float32) if slice_ok else None
+    pts = None if idx is None else np.zeros((len(idx), nSteps), np.float32)
     ms = C.c_double()
     sched = np.ascontiguousarray(sched, np.int32)
     if sched.size == 0:
         sched = np.full(1, -1, np.int32)
 
-    def ptr(a):
-        return None if a is None else a.ctypes.data_as(C.c_void_p)
-    rc = lib.bfd_bhte_run_volumes(_device, N1, N2, N3, nMat, ptr(mat), ptr(cd), ptr(cp), ptr(qf), ptr(initT), nF, ptr(P32), ptr(q), ptr(T), ptr(dose),
-                                  flags, float(stableTemp), float(dt), nSteps, ptr(sched), int(LocationMonitoring) if slice_ok else -1, fm, ptr(mon),
-                                  0 if idx is None else len(idx), ptr(idx), ptr(pts), C.byref(ms))
+    ptr = _ptr
+    rc = lib.bfd_bhte_run_volumes(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
+                                  ptr(v['P32']), ptr(q), ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
+                                  int(LocationMonitoring) if slice_ok else -1, fm, ptr(mon), 0 if idx is None else len(idx), ptr(idx), ptr(pts), C.byref(ms))
     if rc != 0:
         raise _engine.EngineError('bfd_bhte_run_volumes failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
     last_kernel_ms = ms.value
@@ -291,3 +303,127 @@ def BHTEMultiplePressureFields(PressureFields, MaterialMap, MaterialList, dx, To
     sched = field_schedule(oo, int(TotalDurationSteps))
     return _bhte_run(P, sched, MaterialMap, MaterialList, dx, LocationMonitoring, nFactorMonitoring, dt, blood_rho, blood_ct,
                      stableTemp, 1.0, MonitoringPointsMap, initT0, initDose)
+
+
+# ------------------------------------------------------------------------------------------------
+# Repeated sonications (CalculateTemperatureEffects.py:259-460): the whole protocol as one device call (bfd_bhte_run_protocol)
+# ------------------------------------------------------------------------------------------------
+_MAX_STEPS = 2 ** 31 - 1
+
+
+def protocol_schedule(nCurrent, Repetitions, TotalIterations, TotalDurationBetweenGroups, TotalDurationStepsOff,
+                      LimitBHTEIterationsPerProcess, TotalDurationSteps, nStepsOn, multi_field=False, bRunInSubProcess=False):
+    """The steps of the BHTE calls the reference's RunBHTECycles makes from iteration nCurrent on, back to back. Per iteration n:
+    an ON call of TotalDurationSteps steps (one field: the first nStepsOn heat; several: field_schedule(nStepsOn,
+    TotalDurationSteps), restarted at every ON call), then TotalDurationStepsOff cooling steps if that is > 0, then
+    TotalDurationBetweenGroups cooling steps if (n + 1) % Repetitions == 0 and that is > 0. With bRunInSubProcess the run stops
+    after the iteration where (n + 1) % LimitBHTEIterationsPerProcess == 0.
+    Returns (fieldOfStep int32 [-1 = no heating], captureStep int32 [the step boundary at the end of each ON call], calls, nNext):
+    calls lists (kind, n, first step, steps) per call, kind 'on' / 'off' / 'pause'; nNext is the iteration to resume from."""
+    nCurrent, Repetitions, TotalIterations = int(nCurrent), int(Repetitions), int(TotalIterations)
+    nOn, nOff, nPause = int(TotalDurationSteps), int(TotalDurationStepsOff), int(TotalDurationBetweenGroups)
+    if Repetitions < 1:
+        raise ValueError('Repetitions must be >= 1')
+    if not 0 <= nCurrent < TotalIterations:
+        raise ValueError('nCurrent must lie in [0, TotalIterations): there is no iteration to run')
+    if nOn < 0 or nOff < 0 or nPause < 0:
+        raise ValueError('step counts must be non-negative')
+    nEnd = TotalIterations
+    if bRunInSubProcess:
+        limit = int(LimitBHTEIterationsPerProcess)
+        if limit < 1:
+            raise ValueError('LimitBHTEIterationsPerProcess must be >= 1')
+        nEnd = min(TotalIterations, (nCurrent // limit + 1) * limit)
+    calls, pos = [], 0
+    for n in range(nCurrent, nEnd):
+        calls.append(('on', n, pos, nOn)); pos += nOn
+        if TotalDurationStepsOff > 0:
+            calls.append(('off', n, pos, nOff)); pos += nOff
+        if (n + 1) % Repetitions == 0 and TotalDurationBetweenGroups > 0:
+            calls.append(('pause', n, pos, nPause)); pos += nPause
+        if pos > _MAX_STEPS:
+            raise ValueError('the protocol has more than 2^31 - 1 steps')
+    if multi_field:
+        on = field_schedule(nStepsOn, nOn)
+    else:
+        on = np.full(nOn, -1, np.int32)
+        on[:max(min(int(nStepsOn), nOn), 0)] = 0
+    fieldOfStep = np.full(pos, -1, np.int32)
+    caps = []
+    for kind, n, first, steps in calls:
+        if kind == 'on':
+            fieldOfStep[first:first + steps] = on
+            caps.append(first + steps)
+    return fieldOfStep, np.array(caps, np.int32), calls, nEnd
+
+
+def RunBHTECycles(nCurrent, Repetitions, TotalIterations, TotalDurationBetweenGroups, TotalDurationStepsOff, LimitBHTEIterationsPerProcess,
+                  InputPData, PMaps, MaterialMap, MaterialList, dx, TotalDurationSteps, nStepsOn, cy, nFactorMonitoring, dt, DutyCycle,
+                  Backend, MonitoringPointsMap, stableTemp, TemperaturePoints, FinalTemp, FinalDose, PreviousData, bRunInSubProcess=False):
+    """Drop-in for the caller's own loop (CalculateTemperatureEffects.py:259-460, driven at :1026-1100), same positional signature
+    and return value (ResTempMax, ResDose, FinalTemp, FinalDose, TemperaturePoints, nCurrent_next). The loop's ON calls (BHTE
+    when InputPData is a str: PMaps (N1,N2,N3), DutyCycle in the heat source; else BHTEMultiplePressureFields: PMaps
+    (nF,N1,N2,N3), nStepsOn = nStepsOnOffList, duty cycle 1), OFF calls and group pauses run as ONE device call
+    (bfd_bhte_run_protocol, schedule from `protocol_schedule`): T and the dose stay on the device, the temperature maximum over the
+    ends of the ON calls and the dose at the last of them are taken there. Every output equals what the chain of BHTE calls gives.
+    Start state: at nCurrent == 0 PreviousData['FinalTemp' / 'FinalDose'] if given, else InitTemperature[material] and zero dose;
+    at nCurrent > 0 the FinalTemp / FinalDose passed in. TemperaturePoints is replaced at nCurrent == 0 and appended to otherwise.
+    Resuming (nCurrent > 0, the bRunInSubProcess chunks of :1040-1105): ResTempMax is the maximum over the ON calls of THIS call
+    -- the caller combines chunks with np.maximum (:1094-1098); the reference's own loop cannot resume (its ResTempMax is unbound
+    there). cy (the monitored plane, which the caller discards: it passes -1) is ignored, and so is Backend (always the HIP device).
+    MonitoringPointsMap is required, as the reference's unpacking of five returns needs it."""
+    global last_kernel_ms
+    single = isinstance(InputPData, str)
+    P = np.asarray(PMaps)
+    if single:
+        if P.ndim != 3:
+            raise ValueError('PMaps must be a 3-D amplitude map when InputPData is a file name')
+        fields = P[None]
+    else:
+        if P.ndim != 4:
+            raise ValueError('PMaps must be (nFields, N1, N2, N3) for steered fields')
+        oo = np.asarray(nStepsOn)
+        if oo.ndim != 2 or oo.shape != (P.shape[0], 2):
+            raise ValueError('nStepsOnOffList needs one (on, off) row per pressure field')
+        fields = P
+    shape = fields.shape[1:]
+    if np.shape(MaterialMap) != shape:
+        raise ValueError('MaterialMap must have the shape of the pressure field(s)')
+    if MonitoringPointsMap is None:
+        raise ValueError('RunBHTECycles needs a MonitoringPointsMap')
+    if np.shape(MonitoringPointsMap) != shape:
+        raise ValueError('MonitoringPointsMap must have the shape of the pressure field')
+    sched, caps, _, nNext = protocol_schedule(nCurrent, Repetitions, TotalIterations, TotalDurationBetweenGroups, TotalDurationStepsOff,
+                                              LimitBHTEIterationsPerProcess, TotalDurationSteps, nStepsOn, not single, bRunInSubProcess)
+    if int(nCurrent) > 0:
+        initT0, initDose = FinalTemp, FinalDose
+    elif PreviousData is not None:
+        initT0, initDose = PreviousData['FinalTemp'], PreviousData['FinalDose']
+    else:
+        initT0 = initDose = None
+    v = _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, 1050, 3617, DutyCycle if single else 1.0, MonitoringPointsMap, initT0, initDose)
+    idx = v['idx']
+    if int(nCurrent) > 0:
+        if TemperaturePoints is None or np.ndim(TemperaturePoints) != 2 or np.shape(TemperaturePoints)[0] != len(idx):
+            raise ValueError('TemperaturePoints must hold one row per monitoring point when resuming (nCurrent > 0)')
+    nF, N1, N2, N3 = v['shape']
+    nSteps = len(sched)
+    pts = np.zeros((len(idx), nSteps), np.float32)
+    Tmax = np.empty((N1, N2, N3), np.float32)
+    doseCap = np.empty((N1, N2, N3), np.float32)
+    T, dose = v['T'], v['dose']
+    if nSteps == 0:
+        sched = np.full(1, -1, np.int32)
+    lib = _engine.load_library()
+    ms = C.c_double()
+    ptr = _ptr
+    rc = lib.bfd_bhte_run_protocol(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
+                                   ptr(v['P32']), None, ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
+                                   -1, max(int(nFactorMonitoring), 1), None, len(idx), ptr(idx), ptr(pts), C.byref(ms),
+                                   len(caps), ptr(caps), ptr(Tmax), ptr(doseCap))
+    if rc != 0:
+        raise _engine.EngineError('bfd_bhte_run_protocol failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    last_kernel_ms = ms.value
+    if int(nCurrent) > 0:
+        pts = np.hstack((TemperaturePoints, pts))
+    return Tmax, doseCap, T, dose, pts, nNext

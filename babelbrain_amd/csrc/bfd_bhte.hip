@@ -640,23 +640,50 @@ __global__ void heat_source(const float *p, const unsigned char *__restrict__ ma
     }
 }
 
+// np.maximum of one element: a NaN on either side wins
+__device__ __forceinline__ float nan_max(float m, float t) { return (t > m || t != t) ? t : m; }
+// A capture of a protocol (bfd_bhte_run_protocol) at a step boundary: Tmax = max(Tmax, T) (first: Tmax = T), doseCap = dose.
+// 16 B per lane and array; nVec = ceil(n / 4): the last vector may reach into the pads behind the volumes (bhte_run_core), whose
+// values are never read back.
+__global__ __launch_bounds__(256) void bhte_capture(const float4 *__restrict__ T, const float4 *__restrict__ dose, float4 *__restrict__ Tmax,
+                                                    float4 *__restrict__ doseCap, size_t nVec, int first)
+{
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nVec; v += (size_t)gridDim.x * blockDim.x) {
+        const float4 t = T[v];
+        float4 m = t;
+        if (!first) {
+            m = Tmax[v];
+            m.x = nan_max(m.x, t.x); m.y = nan_max(m.y, t.y); m.z = nan_max(m.z, t.z); m.w = nan_max(m.w, t.w);
+        }
+        Tmax[v] = m;
+        doseCap[v] = dose[v];
+    }
+}
+
 }  // namespace
 
 // The run behind all entry points. F, M, S: extents of the fastest, middle and slowest axis of the volumes as they lie in memory.
 // q (host, nFields volumes) or, if null, pressure + qf: the heat increments are then computed on the device (and copied to qOut).
 // initT (per material) replaces the upload of T when flags bit 0 is clear; the dose starts from zero when bit 1 is clear.
+// Captures (bfd_bhte_run_protocol; the other entry points pass none): at step boundary captureStep[c] (after step captureStep[c] - 1)
+// Tmax = max(Tmax, T) (the first copies T) and doseCap = dose; no pass crosses a capture boundary.
 template <bool REV>
 static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_t nMat, const unsigned char *mat, const float *cd, const float *cp,
                          const float *qf, const float *initT, int32_t nFields, const float *q, const float *pressure, float *qOut, float *T, float *dose,
                          int32_t flags, float Tcore, double dt, int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
-                         float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs)
+                         float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                         int32_t nCaptures = 0, const int32_t *captureStep = nullptr, float *Tmax = nullptr, float *doseCap = nullptr)
 {
     if (F < 3 || M < 3 || S < 3 || nMat < 1 || nMat > 256 || nFields < 1 || !mat || !cd || !cp || (!q && !(pressure && qf)) || !T || !dose || nSteps < 0 ||
-        (nSteps > 0 && !fieldOfStep) || (!(flags & 1) && !initT)) {
+        (nSteps > 0 && !fieldOfStep) || (!(flags & 1) && !initT) || nCaptures < 0 || (nCaptures > 0 && !(captureStep && Tmax && doseCap))) {
         bfd_set_error("bfd_bhte_run: bad argument"); return -1;
     }
     for (int s = 0; s < nSteps; s++)
         if (fieldOfStep[s] < -1 || fieldOfStep[s] >= nFields) { bfd_set_error("bfd_bhte_run: fieldOfStep entry out of range"); return -1; }
+    for (int c = 0; c < nCaptures; c++)
+        if (captureStep[c] < 0 || captureStep[c] > nSteps || (c > 0 && captureStep[c] < captureStep[c - 1])) {
+            bfd_set_error("bfd_bhte_run: captureStep must ascend within [0, nSteps]"); return -1;
+        }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { bfd_set_error("bfd_bhte_run: no HIP device available (no CPU fallback)"); return -3; }
     if (device < 0 || device >= ndev) { bfd_set_error("bfd_bhte_run: device ordinal out of range"); return -3; }
@@ -669,6 +696,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     const int fm = nFactorMonitoring > 0 ? nFactorMonitoring : 1;
     const long nSamples = (monitorSlice && sliceJ >= 0) ? (nSteps + fm - 1) / fm : 0;
     float *dT[2] = {nullptr, nullptr}, *dDose = nullptr, *dq = nullptr, *dcd = nullptr, *dcp = nullptr, *dqf = nullptr, *dSlice = nullptr, *dPts = nullptr;
+    float *dTmax = nullptr, *dDoseCap = nullptr;
     unsigned char *dmat = nullptr; unsigned *dIdx = nullptr;
     std::vector<void *> allocs;
     auto A = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) allocs.push_back(*p); return e; };
@@ -684,6 +712,8 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     if (e == hipSuccess) e = AP((void **)&dDose, n, 4);
     if (e == hipSuccess) e = AP((void **)&dq, n * (size_t)nFields, 4);
     if (e == hipSuccess) e = AP((void **)&dmat, n, 1);
+    if (e == hipSuccess && nCaptures) e = AP((void **)&dTmax, n, 4);
+    if (e == hipSuccess && nCaptures) e = AP((void **)&dDoseCap, n, 4);
     if (e == hipSuccess) e = A((void **)&dcd, nMat * 4);
     if (e == hipSuccess) e = A((void **)&dcp, nMat * 4);
     if (e == hipSuccess) e = A((void **)&dqf, nMat * 4);
@@ -750,6 +780,14 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
             if (dPts) hipLaunchKernelGGL(gather_points, dim3((unsigned)((nPoints + 255) / 256)), dim3(256), 0, 0, dT[cur], dIdx, dPts, (long)nPoints, (long)nSteps, (long)s);
             if (dSlice && s % fm == 0) hipLaunchKernelGGL(gather_slice<REV>, dim3(256), dim3(256), 0, 0, dT[cur], dSlice, N1, N2, N3, sliceJ, (long)(s / fm), nSamples);
         };
+        // captures due at boundary s; a pass of L steps from s may not end past the next one
+        int nextCap = 0;
+        auto captures = [&](int s) {
+            for (; nextCap < nCaptures && captureStep[nextCap] == s; nextCap++)
+                hipLaunchKernelGGL(bhte_capture, dim3(2048), dim3(256), 0, 0, (const float4 *)dT[cur], (const float4 *)dDose, (float4 *)dTmax, (float4 *)dDoseCap,
+                                   (n + 3) / 4, nextCap == 0 ? 1 : 0);
+        };
+        auto capFree = [&](int s, int L) { return nextCap >= nCaptures || (long)s + L <= captureStep[nextCap]; };
         // S steps per pass (round 6; BFD_BHTE_STEPS=2 keeps two): where the next S steps carry the same heat field (or none). Monitors of the steps
         // inside a pass are recomputed from the pass's input: the points by cone_points, a sample of the monitored plane by step_slice (first step) or
         // cone_slice (steps in between); the last step's are read off the result.
@@ -777,9 +815,10 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
             G.nBlocks = (long)tilesX * G.tilesY * ((N3 + G.zrun - 1) / G.zrun);
         }
         for (int s = 0; s < nSteps;) {
+            captures(s);
             const int stepsN = fieldOfStep[s] >= 0 ? stepsHeat : stepsCool;
             const PassGeom &G = geom[stepsN >= 3 ? stepsN : 3];
-            bool passN = stepsN >= 3 && s + stepsN <= nSteps && G.nBlocks < 0x7fffffffL;
+            bool passN = stepsN >= 3 && s + stepsN <= nSteps && G.nBlocks < 0x7fffffffL && capFree(s, stepsN);
             for (int j = 1; j < stepsN && passN; j++) passN = fieldOfStep[s + j] == fieldOfStep[s];
             if (passN) {
                 const float *qa = Q(fieldOfStep[s]);
@@ -801,7 +840,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
                 monitors(s - 1);
                 continue;
             }
-            if (fuse && s + 1 < nSteps && nBlocks2 < 0x7fffffffL) {
+            if (fuse && s + 1 < nSteps && nBlocks2 < 0x7fffffffL && capFree(s, 2)) {
                 const float *qa = Q(fieldOfStep[s]), *qb = Q(fieldOfStep[s + 1]);
                 if (dPts) hipLaunchKernelGGL(step_points<REV>, dim3((unsigned)((nPoints + 255) / 256)), dim3(256), 0, 0, dT[cur], qa, dmat, dcd, dcp, N1, N2, N3, Tcore, dIdx, dPts, (long)nPoints, (long)nSteps, (long)s);
                 if (dSlice && s % fm == 0) hipLaunchKernelGGL(step_slice<REV>, dim3(256), dim3(256), 0, 0, dT[cur], qa, dmat, dcd, dcp, N1, N2, N3, Tcore, dSlice, sliceJ, (long)(s / fm), nSamples);
@@ -818,6 +857,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
                 monitors(s - 1);
             }
         }
+        captures(nSteps);
         hipEventRecord(e1, 0);
         e = hipEventSynchronize(e1);
         if (e == hipSuccess) e = hipGetLastError();
@@ -827,6 +867,8 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     if (e == hipSuccess) e = hipMemcpy(dose, dDose, n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dSlice) e = hipMemcpy(monitorSlice, dSlice, (size_t)N1 * N3 * nSamples * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dPts) e = hipMemcpy(points, dPts, (size_t)nPoints * nSteps * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && dTmax) e = hipMemcpy(Tmax, dTmax, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && dDoseCap) e = hipMemcpy(doseCap, dDoseCap, n * 4, hipMemcpyDeviceToHost);
     if (e0) hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
     for (void *p : allocs) hipFree(p);
@@ -867,6 +909,22 @@ extern "C" int bfd_bhte_run_volumes(int32_t device, int32_t N1, int32_t N2, int3
     if (!pressure || !qf) { bfd_set_error("bfd_bhte_run_volumes: bad argument"); return -1; }
     return bhte_run_core<true>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
                                sliceJ, nFactorMonitoring, monitorSlice, nPoints, pointIndex, points, kernelMs);
+}
+
+// A whole repeated-sonication protocol (the caller's RunBHTECycles loop, CalculateTemperatureEffects.py:259-460) as one run of
+// bfd_bhte_run_volumes: fieldOfStep spans every ON call, OFF call and group pause back to back, the volumes are uploaded once and
+// downloaded once, and at each captureStep boundary (the end of an ON call) Tmax = max(Tmax, T) and doseAtCapture = dose on the
+// device. The reference discards the monitored plane of these calls: sliceJ must be -1.
+extern "C" int bfd_bhte_run_protocol(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const unsigned char *mat,
+                                     const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                                     const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                                     int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                                     float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                                     int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture)
+{
+    if (!pressure || !qf || sliceJ != -1 || nCaptures < 1) { bfd_set_error("bfd_bhte_run_protocol: bad argument"); return -1; }
+    return bhte_run_core<true>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
+                               -1, nFactorMonitoring, nullptr, nPoints, pointIndex, points, kernelMs, nCaptures, captureStep, Tmax, doseAtCapture);
 }
 
 // One pressure field heating during the first nStepsOn steps (the reference's BHTE call).

@@ -348,6 +348,21 @@ int bfd_bhte_run_volumes(int32_t device, int32_t N1, int32_t N2, int32_t N3, int
                          int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
                          float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs);
 
+/* A whole repeated-sonication protocol in one call: replaces the caller's RunBHTECycles loop
+ * (ThermalModeling/CalculateTemperatureEffects.py:259-460), which makes one BHTE call per ON period, one per OFF period and one
+ * per group pause and moves T and the dose through the host between them. Arguments as bfd_bhte_run_volumes, with fieldOfStep
+ * covering the whole protocol back to back and points [nPoints][nSteps] over all of it; sliceJ must be -1 (no monitored plane)
+ * and monitorSlice is ignored. captureStep: nCaptures >= 1 ascending step boundaries in [0, nSteps] (boundary c = after step
+ * c - 1, the end of an ON call): there Tmax = max(Tmax, T) (the first capture copies T) and doseAtCapture = dose. Tmax and
+ * doseAtCapture are [N1][N2][N3] outputs. No multi-step pass crosses a capture, so every output equals what the chain of
+ * bfd_bhte_run_volumes calls gives. */
+int bfd_bhte_run_protocol(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const unsigned char *mat,
+                          const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                          const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                          int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                          float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                          int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture);
+
 #ifdef __cplusplus
 }
 #endif
