@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from .sources import SeparableSource
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BABELFDTD_HIP_LIB: another build of the same library (A/B kernel experiments, scripts/ab_build.sh)
 LIB_PATH = os.environ.get('BABELFDTD_HIP_LIB') or os.path.join(_HERE, 'libbabelfdtd_hip.so')
@@ -24,13 +26,13 @@ FIELD_NAMES = ['Vx', 'Vy', 'Vz', 'Sxx', 'Syy', 'Szz', 'Sxy', 'Sxz', 'Syz', 'Rxx'
 ABI_SYMBOLS = [
     'bfd_abi_version', 'bfd_last_error', 'bfd_device_count', 'bfd_device_name', 'bfd_stable_dt',
     'bfd_material_tables', 'bfd_create', 'bfd_destroy', 'bfd_set_stream', 'bfd_use_private_stream', 'bfd_set_materials',
-    'bfd_set_material_map', 'bfd_set_reflector', 'bfd_set_sources', 'bfd_set_sensor_map', 'bfd_run',
+    'bfd_set_material_map', 'bfd_set_reflector', 'bfd_set_sources', 'bfd_set_sources_separable', 'bfd_set_sensor_map', 'bfd_run',
     'bfd_half_step_stress', 'bfd_half_step_velocity', 'bfd_half_step_stress_part', 'bfd_half_step_velocity_part', 'bfd_half_step_stress_part_on', 'bfd_half_step_velocity_part_on', 'bfd_sync', 'bfd_current_step', 'bfd_prepare', 'bfd_halo_region',
     'bfd_timing_begin', 'bfd_timing_end', 'bfd_timing_kernels', 'bfd_algorithmic_bytes', 'bfd_reset', 'bfd_num_sensors', 'bfd_num_sensor_steps', 'bfd_get_sensor_index',
     'bfd_get_sensors', 'bfd_get_map', 'bfd_get_field', 'bfd_tile_counts', 'bfd_tile_count_lean', 'bfd_tile_count_fused', 'bfd_activity_counts', 'bfd_device_bytes', 'bfd_rayleigh_forward', 'bfd_get_sensor_dft', 'bfd_dft_series', 'bfd_bhte_run', 'bfd_bhte_run_fields', 'bfd_bhte_run_volumes', 'bfd_bhte_run_protocol',
     'bfd_halo_fields', 'bfd_placement_note', 'bfd_set_placement', 'bfd_group_set_placement',
     'bfd_group_create', 'bfd_group_destroy', 'bfd_group_size', 'bfd_group_slab', 'bfd_group_set_materials', 'bfd_group_set_material_map',
-    'bfd_group_set_reflector', 'bfd_group_set_sources', 'bfd_group_set_sensor_map', 'bfd_group_prepare', 'bfd_group_run', 'bfd_group_sync',
+    'bfd_group_set_reflector', 'bfd_group_set_sources', 'bfd_group_set_sources_separable', 'bfd_group_set_sensor_map', 'bfd_group_prepare', 'bfd_group_run', 'bfd_group_sync',
     'bfd_group_reset', 'bfd_group_timing_begin', 'bfd_group_timing_end', 'bfd_group_num_sensors', 'bfd_group_num_sensor_steps',
     'bfd_group_get_sensor_index', 'bfd_group_get_sensors', 'bfd_group_get_sensor_dft', 'bfd_group_get_map', 'bfd_group_device_bytes',
     'bfd_group_peer_status', 'bfd_placement_cache_release',
@@ -102,6 +104,8 @@ def load_library():
     lib.bfd_set_reflector.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
     lib.bfd_set_sources.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int32, C.c_int32]
+    lib.bfd_set_sources_separable.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.bfd_set_sensor_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     lib.bfd_run.argtypes = [C.c_void_p, C.c_int32]
     lib.bfd_half_step_stress.argtypes = [C.c_void_p]
@@ -163,6 +167,8 @@ def load_library():
     lib.bfd_group_set_reflector.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
     lib.bfd_group_set_sources.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int32, C.c_int32]
+    lib.bfd_group_set_sources_separable.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.bfd_group_set_sensor_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     for fn in ('bfd_group_prepare', 'bfd_group_sync', 'bfd_group_reset', 'bfd_group_timing_begin'):
         getattr(lib, fn).argtypes = [C.c_void_p]
@@ -332,14 +338,22 @@ class Engine:
         return a
 
     def set_sources(self, localIndex, row, wx, wy, wz, PulseSource):
-        pulse = np.ascontiguousarray(np.atleast_2d(PulseSource), np.float64)
-        self._pulse = pulse     # a large table is streamed from here in time tiles during the run: keep it alive with the engine
+        """PulseSource: the dense float64 [nSources][nT] table, or a SeparableSource (weights and signals stay resident)."""
         li = np.asarray(localIndex)
         if li.size and (int(li.max()) >= 2 ** 32 or int(li.min()) < 0):
             raise ValueError('source index beyond 2^32 voxels: split the domain over devices (devices=[...])')
         li = np.ascontiguousarray(li, np.uint32)
         rw = np.ascontiguousarray(row, np.uint32)
         ws = [None if w is None else np.ascontiguousarray(w, np.float32) for w in (wx, wy, wz)]
+        if isinstance(PulseSource, SeparableSource):
+            src = PulseSource
+            _check(self.lib.bfd_set_sources_separable(self.h, li.size, _ptr(li), _ptr(rw), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]),
+                                                      src.shape[0], src.K, _ptr(src.weights), src.shape[1], _ptr(src.signals)),
+                   'bfd_set_sources_separable')
+            self._pulse = None      # only now: a streamed dense table set before is released by the call above
+            return
+        pulse = np.ascontiguousarray(np.atleast_2d(PulseSource), np.float64)
+        self._pulse = pulse     # a large table is streamed from here in time tiles during the run: keep it alive with the engine
         _check(self.lib.bfd_set_sources(self.h, li.size, _ptr(li), _ptr(rw), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]),
                                         _ptr(pulse), pulse.shape[0], pulse.shape[1]), 'bfd_set_sources')
 
@@ -594,11 +608,19 @@ class Group:
         _check(self.lib.bfd_group_set_reflector(self.h, _ptr(a), *_estrides(a)), 'bfd_group_set_reflector')
 
     def set_sources(self, globalIndex, row, wx, wy, wz, PulseSource):
-        pulse = np.ascontiguousarray(np.atleast_2d(PulseSource), np.float64)
-        self._pulse = pulse     # a large table is streamed from here during the run: keep it alive with the group
+        """PulseSource: the dense float64 [nSources][nT] table, or a SeparableSource."""
         gi = np.ascontiguousarray(globalIndex, np.int64)
         rw = np.ascontiguousarray(row, np.uint32)
         ws = [None if w is None else np.ascontiguousarray(w, np.float32) for w in (wx, wy, wz)]
+        if isinstance(PulseSource, SeparableSource):
+            src = PulseSource
+            _check(self.lib.bfd_group_set_sources_separable(self.h, gi.size, _ptr(gi), _ptr(rw), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]),
+                                                            src.shape[0], src.K, _ptr(src.weights), src.shape[1], _ptr(src.signals)),
+                   'bfd_group_set_sources_separable')
+            self._pulse = None      # only now: a streamed dense table set before is released by the call above
+            return
+        pulse = np.ascontiguousarray(np.atleast_2d(PulseSource), np.float64)
+        self._pulse = pulse     # a large table is streamed from here during the run: keep it alive with the group
         _check(self.lib.bfd_group_set_sources(self.h, gi.size, _ptr(gi), _ptr(rw), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]),
                                               _ptr(pulse), pulse.shape[0], pulse.shape[1]), 'bfd_group_set_sources')
 

@@ -441,14 +441,33 @@ __global__ void dft_series(const float *__restrict__ in, long sS, long sN, long 
     }
 }
 
-// sources. typeSource 0/1: velocity (after the velocity half-step), 2/3: normal stresses (after the stress half-step)
-__global__ void inject_sources(bfd_dev d, int typeSource, const uint32_t *__restrict__ lin, const uint32_t *__restrict__ row,
-                               const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
-                               const float *__restrict__ pulseAtStep, long nVox)
+// sources. typeSource 0/1: velocity (after the velocity half-step), 2/3: normal stresses (after the stress half-step).
+// One body for both source forms; the value policy gives the float32 source value of a row at the current step.
+struct DenseValue {            // the dense table: row `step` of the [step][source] float32 table
+    const float *__restrict__ pulseAtStep;
+    __device__ float operator()(uint32_t r) const { return pulseAtStep[r]; }
+};
+template <int K>
+struct SeparableValue {        // sum_k w[r*K + k] * sig_k(step), in that order (no contraction: -ffp-contract=off)
+    const float *__restrict__ w; float sig[K];
+    __device__ float operator()(uint32_t r) const
+    {
+        const float *wr = w + (size_t)r * K;
+        float acc = wr[0] * sig[0];
+#pragma unroll
+        for (int k = 1; k < K; k++) acc = acc + wr[k] * sig[k];
+        return acc;
+    }
+};
+
+template <class Value>
+__device__ void inject_body(const bfd_dev &d, int typeSource, const uint32_t *__restrict__ lin, const uint32_t *__restrict__ row,
+                            const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
+                            const Value &value, long nVox)
 {
     for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nVox; s += (long)gridDim.x * blockDim.x) {
         const long c = lin[s];
-        const float val = pulseAtStep[row[s]];
+        const float val = value(row[s]);
         const float x = wx ? wx[s] : 1.0f;
         if (typeSource >= 2) {
             const float v = val * x;
@@ -465,6 +484,13 @@ __global__ void inject_sources(bfd_dev d, int typeSource, const uint32_t *__rest
             else { d.Vx[c] = val * x; d.Vy[c] = val * y; d.Vz[c] = val * z; }
         }
     }
+}
+
+__global__ void inject_sources(bfd_dev d, int typeSource, const uint32_t *__restrict__ lin, const uint32_t *__restrict__ row,
+                               const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
+                               const float *__restrict__ pulseAtStep, long nVox)
+{
+    inject_body(d, typeSource, lin, row, wx, wy, wz, DenseValue{pulseAtStep}, nVox);
 }
 
 // graph replay: the step counter lives on the device
@@ -474,31 +500,64 @@ __global__ void inject_sources_at(bfd_dev d, int typeSource, const uint32_t *__r
 {
     const int step = *stepDev;
     if (step >= lengthSource) return;
-    const float *pulseAtStep = pulseT + (size_t)step * nSources;
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nVox; s += (long)gridDim.x * blockDim.x) {
-        const long c = lin[s];
-        const float val = pulseAtStep[row[s]];
-        const float x = wx ? wx[s] : 1.0f;
-        if (typeSource >= 2) {
-            const float v = val * x;
-            float *pxx = d.Sxx + c, *pyy = d.Syy + c;
-            if (d.cssRow) {         // compact solid state: a listed cell's Sxx, Syy live in the list; elsewhere nobody reads them (fluid cells keep Szz only) and
-                const long e = css_index(d, c);      // the full-volume arrays are not to be written: they may host the compact ones
-                pxx = e >= 0 ? d.cSxx + e : nullptr; pyy = e >= 0 ? d.cSyy + e : nullptr;
-            }
-            if (typeSource == 2) { if (pxx) { *pxx = *pxx + v; *pyy = *pyy + v; } d.Szz[c] = d.Szz[c] + v; }
-            else { if (pxx) { *pxx = v; *pyy = v; } d.Szz[c] = v; }
-        } else {
-            const float y = wy ? wy[s] : 1.0f, z = wz ? wz[s] : 1.0f;
-            if (typeSource == 0) { d.Vx[c] = d.Vx[c] + val * x; d.Vy[c] = d.Vy[c] + val * y; d.Vz[c] = d.Vz[c] + val * z; }
-            else { d.Vx[c] = val * x; d.Vy[c] = val * y; d.Vz[c] = val * z; }
-        }
-    }
+    inject_body(d, typeSource, lin, row, wx, wy, wz, DenseValue{pulseT + (size_t)step * nSources}, nVox);
 }
+
+// separable source: sigAtStep = the K signal values of this step ([step][K] table); the same address for every lane
+template <int K>
+__global__ void inject_sources_sep(bfd_dev d, int typeSource, const uint32_t *__restrict__ lin, const uint32_t *__restrict__ row,
+                                   const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
+                                   const float *__restrict__ weights, const float *__restrict__ sigAtStep, long nVox)
+{
+    SeparableValue<K> v; v.w = weights;
+#pragma unroll
+    for (int k = 0; k < K; k++) v.sig[k] = sigAtStep[k];
+    inject_body(d, typeSource, lin, row, wx, wy, wz, v, nVox);
+}
+
+template <int K>
+__global__ void inject_sources_sep_at(bfd_dev d, int typeSource, const uint32_t *__restrict__ lin, const uint32_t *__restrict__ row,
+                                      const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
+                                      const float *__restrict__ weights, const float *__restrict__ signals, const int *__restrict__ stepDev,
+                                      int lengthSource, long nVox)
+{
+    const int step = *stepDev;
+    if (step >= lengthSource) return;
+    SeparableValue<K> v; v.w = weights;
+#pragma unroll
+    for (int k = 0; k < K; k++) v.sig[k] = signals[(size_t)step * K + k];
+    inject_body(d, typeSource, lin, row, wx, wy, wz, v, nVox);
+}
+
 __global__ void set_step(int *stepDev, int v) { *stepDev = v; }
 __global__ void advance_step(int *stepDev) { *stepDev = *stepDev + 1; }
 
 inline int grid_for(long n, int block = 256) { return (int)std::min<long>((n + block - 1) / block, 256L * 32); }
+
+// separable injection with K terms: at host step `step`, or (stepDev != null, graph replay) at the device's step counter
+template <int K>
+void launch_inject_sep_k(hipStream_t st, const bfd_dev &view, int typeSource, const uint32_t *lin, const uint32_t *row, const float *wx,
+                         const float *wy, const float *wz, const float *weights, const float *signals, int step, const int *stepDev,
+                         int lengthSource, long n)
+{
+    if (stepDev)
+        hipLaunchKernelGGL(inject_sources_sep_at<K>, dim3(grid_for(n)), dim3(256), 0, st, view, typeSource, lin, row, wx, wy, wz,
+                           weights, signals, stepDev, lengthSource, n);
+    else
+        hipLaunchKernelGGL(inject_sources_sep<K>, dim3(grid_for(n)), dim3(256), 0, st, view, typeSource, lin, row, wx, wy, wz,
+                           weights, signals + (size_t)step * K, n);
+}
+void launch_inject_separable(int K, hipStream_t st, const bfd_dev &view, int typeSource, const uint32_t *lin, const uint32_t *row,
+                             const float *wx, const float *wy, const float *wz, const float *weights, const float *signals, int step,
+                             const int *stepDev, int lengthSource, long n)
+{
+    switch (K) {
+    case 1: launch_inject_sep_k<1>(st, view, typeSource, lin, row, wx, wy, wz, weights, signals, step, stepDev, lengthSource, n); break;
+    case 2: launch_inject_sep_k<2>(st, view, typeSource, lin, row, wx, wy, wz, weights, signals, step, stepDev, lengthSource, n); break;
+    case 3: launch_inject_sep_k<3>(st, view, typeSource, lin, row, wx, wy, wz, weights, signals, step, stepDev, lengthSource, n); break;
+    default: launch_inject_sep_k<4>(st, view, typeSource, lin, row, wx, wy, wz, weights, signals, step, stepDev, lengthSource, n); break;
+    }
+}
 
 // inputs changed: a recorded step graph holds stale pointers
 static void drop_step_graph(bfd_sim *s)
@@ -760,6 +819,7 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     s->nSrcVox = 0; s->srcLin = s->srcRow = nullptr; s->srcW[0] = s->srcW[1] = s->srcW[2] = nullptr; s->pulseT = nullptr;
     s->nSources = s->lengthSource = 0;
     s->pulseHost = nullptr; s->tileSteps = s->nTiles = 0;
+    s->srcK = 0; s->srcWeights = s->srcSignals = nullptr;
     for (int b = 0; b < 2; b++) { s->tileDev[b] = s->tilePinned[b] = nullptr; s->tileLoaded[b] = s->tilePacked[b] = -1; s->evTile[b] = nullptr; s->evTileUsed[b] = false; for (int q = 0; q < 2; q++) { s->evRead[b][q] = nullptr; s->evReadUsed[b][q] = false; } }
     s->sensEnt = nullptr; s->sensEntValid = false; s->sensIsBox = false; memset(s->sensBox, 0, sizeof s->sensBox);
     s->actBase = nullptr; s->actBytes = 0; s->actReady = false;
@@ -973,21 +1033,21 @@ int bfd_set_reflector(bfd_sim *s, const uint32_t *mask, int64_t s1, int64_t s2, 
     return 0;
 }
 
-int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
-                    const float *wx, const float *wy, const float *wz,
-                    const double *pulse, int32_t nSources, int32_t lengthSource)
+// What both source forms share: checks the voxels, releases the previous sources of either form (device tables, streaming
+// buffers, separable weights and signals) and uploads the voxel list sorted by voxel index with its Ox/Oy/Oz weights.
+// who = the entry point, for the messages.
+static int set_source_voxels(bfd_sim *s, const char *who, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
+                             const float *wx, const float *wy, const float *wz, int32_t nSources, int32_t lengthSource)
 {
-    if (!s) BFD_FAIL(-1, "null sim");
-    if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !pulse))) BFD_FAIL(-1, "bfd_set_sources: null argument");
-    if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources: bad PulseSource shape");
     BFD_HIP(hipSetDevice(s->cfg.device));
     for (int64_t v = 0; v < nVox; v++) {
-        if (localIndex[v] >= s->nloc) BFD_FAIL(-2, "bfd_set_sources: voxel index outside the slab");
-        if ((int)row[v] >= nSources) BFD_FAIL(-2, "bfd_set_sources: SourceMap id exceeds PulseSource rows");
+        if (localIndex[v] >= s->nloc) BFD_FAIL(-2, std::string(who) + ": voxel index outside the slab");
+        if ((int)row[v] >= nSources) BFD_FAIL(-2, std::string(who) + ": SourceMap id exceeds PulseSource rows");
     }
     BFD_HIP(hipStreamSynchronize(s->stream));
     dev_release(s, &s->srcLin); dev_release(s, &s->srcRow); dev_release(s, &s->pulseT);
     release_streaming(s);
+    dev_release(s, &s->srcWeights); dev_release(s, &s->srcSignals); s->srcK = 0;
     for (int a = 0; a < 3; a++) dev_release(s, &s->srcW[a]);
     s->nSrcVox = nVox; s->nSources = nSources; s->lengthSource = lengthSource;
     s->srcLowEnd = 0; s->srcHighBeg = nVox; s->tilesReady = false; s->actReady = false; drop_step_graph(s);
@@ -1014,6 +1074,18 @@ int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const 
             BFD_HIP(hipMemcpy(s->srcW[a], hw.data(), nVox * sizeof(float), hipMemcpyHostToDevice));
         }
     }
+    return 0;
+}
+
+int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
+                    const float *wx, const float *wy, const float *wz,
+                    const double *pulse, int32_t nSources, int32_t lengthSource)
+{
+    if (!s) BFD_FAIL(-1, "null sim");
+    if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !pulse))) BFD_FAIL(-1, "bfd_set_sources: null argument");
+    if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources: bad PulseSource shape");
+    int rc = set_source_voxels(s, "bfd_set_sources", nVox, localIndex, row, wx, wy, wz, nSources, lengthSource);
+    if (rc || nVox == 0) return rc;
     const size_t np = (size_t)nSources * lengthSource;
     // Large tables are streamed: the float64 table stays where the caller built it (it must stay valid until the run is
     // over, as it does inside the solver call of the drop-in) and the device holds two time tiles. BFD_SOURCE_TILE=<steps>
@@ -1048,6 +1120,37 @@ int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const 
     hipLaunchKernelGGL(transpose_pulse, dim3(grid_for((long)np)), dim3(256), 0, s->stream, tmp, s->pulseT, nSources, lengthSource);
     BFD_HIP(hipStreamSynchronize(s->stream));
     hipFree(tmp);
+    return 0;
+}
+
+int bfd_set_sources_separable(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
+                              const float *wx, const float *wy, const float *wz,
+                              int32_t nSources, int32_t K, const float *weights, int32_t lengthSource, const float *signals)
+{
+    if (!s) BFD_FAIL(-1, "null sim");
+    if (K < 1 || K > 4) BFD_FAIL(-2, "bfd_set_sources_separable: K must be 1..4");
+    if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !weights || !signals))) BFD_FAIL(-1, "bfd_set_sources_separable: null argument");
+    if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources_separable: bad weights / signals shape");
+    int rc = set_source_voxels(s, "bfd_set_sources_separable", nVox, localIndex, row, wx, wy, wz, nSources, lengthSource);
+    if (rc || nVox == 0) return rc;
+    // weights [nSources][K] as given; signals [K][lengthSource] -> [lengthSource][K]: the K values of a step side by side
+    const size_t nw = (size_t)nSources * K, ns = (size_t)lengthSource * K;
+    std::vector<float> sig(ns);
+    for (int n = 0; n < lengthSource; n++)
+        for (int k = 0; k < K; k++) sig[(size_t)n * K + k] = signals[(size_t)k * lengthSource + n];
+    hipError_t e = hipSuccess;
+    rc = dev_alloc(s, &s->srcWeights, nw, false);
+    if (!rc) rc = dev_alloc(s, &s->srcSignals, ns, false);
+    if (!rc && nw) e = hipMemcpy(s->srcWeights, weights, nw * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess && ns) e = hipMemcpy(s->srcSignals, sig.data(), ns * sizeof(float), hipMemcpyHostToDevice);
+    if (rc || e != hipSuccess) {        // nothing half-built stays behind: the sim is back to "no sources"
+        const std::string why = rc ? std::string(bfd_last_error()) : std::string("bfd_set_sources_separable: ") + hipGetErrorString(e);
+        dev_release(s, &s->srcWeights); dev_release(s, &s->srcSignals);
+        s->nSrcVox = 0; s->srcHighBeg = 0;
+        bfd_set_error(why);
+        return rc ? rc : -10;
+    }
+    s->srcK = K;
     return 0;
 }
 
@@ -2093,6 +2196,17 @@ static int inject_part(bfd_sim *s, int part, const bfd_dev &view, hipStream_t st
     if (part == 0 || s->cfg.kernelVariant == 1) { if (part == 1) return 0; end[0] = n; }
     else if (part == 1) { end[0] = s->srcLowEnd; beg[1] = s->srcHighBeg; end[1] = n; }
     else { beg[0] = s->srcLowEnd; end[0] = s->srcHighBeg; }
+    if (s->srcK) {          // separable: weights and signals are resident, nothing to stream
+        for (int r = 0; r < 2; r++) {
+            const int64_t c = end[r] - beg[r];
+            if (c <= 0) continue;
+            launch_inject_separable(s->srcK, st, view, s->cfg.typeSource, s->srcLin + beg[r], s->srcRow + beg[r],
+                                    s->srcW[0] ? s->srcW[0] + beg[r] : nullptr, s->srcW[1] ? s->srcW[1] + beg[r] : nullptr,
+                                    s->srcW[2] ? s->srcW[2] + beg[r] : nullptr, s->srcWeights, s->srcSignals, s->step, nullptr,
+                                    s->lengthSource, (long)c);
+        }
+        return 0;
+    }
     const float *pulse = nullptr;
     { const int rc = pulse_row(s, s->step, st, &pulse); if (rc) return rc; }
     for (int r = 0; r < 2; r++) {
@@ -2221,6 +2335,11 @@ static void record_plain_step(bfd_sim *s, hipStream_t cs)
     const bfd_dev &d = s->d;
     auto inject = [&]() {
         if (!s->nSrcVox) return;
+        if (s->srcK) {
+            launch_inject_separable(s->srcK, cs, d, s->cfg.typeSource, s->srcLin, s->srcRow, s->srcW[0], s->srcW[1], s->srcW[2],
+                                    s->srcWeights, s->srcSignals, 0, s->stepDev, s->lengthSource, (long)s->nSrcVox);
+            return;
+        }
         hipLaunchKernelGGL(inject_sources_at, dim3(grid_for(s->nSrcVox)), dim3(256), 0, cs, d, s->cfg.typeSource, s->srcLin, s->srcRow,
                            s->srcW[0], s->srcW[1], s->srcW[2], s->pulseT, s->stepDev, s->nSources, s->lengthSource, (long)s->nSrcVox);
     };

@@ -373,6 +373,19 @@ int bfd_group_set_reflector(bfd_group *g, const uint32_t *mask, int64_t s1, int6
     });
 }
 
+// the source voxels of slab r: local indices, rows, Ox/Oy/Oz weights (empty when the caller passed none)
+static void slab_sources(const bfd_group *g, int r, int64_t nVox, const int64_t *globalIndex, const uint32_t *row, const float *const wsrc[3],
+                         std::vector<uint32_t> &li, std::vector<uint32_t> &rw, std::vector<float> w[3])
+{
+    const int64_t plane = (int64_t)g->cfg.N1 * g->cfg.N2;
+    const int64_t lo = plane * g->k0[r], hi = lo + plane * g->nk[r];
+    for (int64_t v = 0; v < nVox; v++) {
+        if (globalIndex[v] < lo || globalIndex[v] >= hi) continue;
+        li.push_back((uint32_t)(globalIndex[v] - lo)); rw.push_back(row[v]);
+        for (int a = 0; a < 3; a++) if (wsrc[a]) w[a].push_back(wsrc[a][v]);
+    }
+}
+
 int bfd_group_set_sources(bfd_group *g, int64_t nVox, const int64_t *globalIndex, const uint32_t *row,
                           const float *wx, const float *wy, const float *wz, const double *pulse, int32_t nSources, int32_t lengthSource)
 {
@@ -380,17 +393,38 @@ int bfd_group_set_sources(bfd_group *g, int64_t nVox, const int64_t *globalIndex
     if (nVox < 0 || (nVox > 0 && (!globalIndex || !row || !pulse))) GRP_FAIL(-1, "bfd_group_set_sources: null argument");
     const int64_t plane = (int64_t)g->cfg.N1 * g->cfg.N2, total = plane * g->cfg.N3;
     for (int64_t v = 0; v < nVox; v++) if (globalIndex[v] < 0 || globalIndex[v] >= total) GRP_FAIL(-2, "bfd_group_set_sources: voxel index outside the domain");
+    const float *wsrc[3] = {wx, wy, wz};
     for (int r = 0; r < g->n; r++) {
-        const int64_t lo = plane * g->k0[r], hi = lo + plane * g->nk[r];
         std::vector<uint32_t> li, rw; std::vector<float> w[3];
-        const float *wsrc[3] = {wx, wy, wz};
-        for (int64_t v = 0; v < nVox; v++) {
-            if (globalIndex[v] < lo || globalIndex[v] >= hi) continue;
-            li.push_back((uint32_t)(globalIndex[v] - lo)); rw.push_back(row[v]);
-            for (int a = 0; a < 3; a++) if (wsrc[a]) w[a].push_back(wsrc[a][v]);
-        }
+        slab_sources(g, r, nVox, globalIndex, row, wsrc, li, rw, w);
         const int rc = bfd_set_sources(g->sim[r], (int64_t)li.size(), li.data(), rw.data(), wx ? w[0].data() : nullptr, wy ? w[1].data() : nullptr,
                                        wz ? w[2].data() : nullptr, pulse, nSources, lengthSource);
+        if (rc) return rc;
+    }
+    g->prepared = false;
+    return 0;
+}
+
+int bfd_group_set_sources_separable(bfd_group *g, int64_t nVox, const int64_t *globalIndex, const uint32_t *row,
+                                    const float *wx, const float *wy, const float *wz,
+                                    int32_t nSources, int32_t K, const float *weights, int32_t lengthSource, const float *signals)
+{
+    if (!g) GRP_FAIL(-1, "null group");
+    if (K < 1 || K > 4) GRP_FAIL(-2, "bfd_group_set_sources_separable: K must be 1..4");
+    if (nVox < 0 || (nVox > 0 && (!globalIndex || !row || !weights || !signals))) GRP_FAIL(-1, "bfd_group_set_sources_separable: null argument");
+    if (nSources < 0 || lengthSource < 0) GRP_FAIL(-2, "bfd_group_set_sources_separable: bad weights / signals shape");
+    const int64_t plane = (int64_t)g->cfg.N1 * g->cfg.N2, total = plane * g->cfg.N3;
+    for (int64_t v = 0; v < nVox; v++) {
+        if (globalIndex[v] < 0 || globalIndex[v] >= total) GRP_FAIL(-2, "bfd_group_set_sources_separable: voxel index outside the domain");
+        if ((int64_t)row[v] >= nSources) GRP_FAIL(-2, "bfd_group_set_sources_separable: SourceMap id exceeds the weight rows");
+    }
+    const float *wsrc[3] = {wx, wy, wz};
+    for (int r = 0; r < g->n; r++) {
+        std::vector<uint32_t> li, rw; std::vector<float> w[3];
+        slab_sources(g, r, nVox, globalIndex, row, wsrc, li, rw, w);
+        const int rc = bfd_set_sources_separable(g->sim[r], (int64_t)li.size(), li.data(), rw.data(), wx ? w[0].data() : nullptr,
+                                                 wy ? w[1].data() : nullptr, wz ? w[2].data() : nullptr, nSources, K, weights,
+                                                 lengthSource, signals);
         if (rc) return rc;
     }
     g->prepared = false;

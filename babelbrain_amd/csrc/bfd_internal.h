@@ -177,6 +177,9 @@ struct bfd_sim {
     hipEvent_t evTile[2]; bool evTileUsed[2];
     hipEvent_t evRead[2][2]; bool evReadUsed[2][2];      // [buffer][0 = engine stream, 1 = a side stream]: behind the last kernels that read the tile the buffer holds
     std::future<void> packJob[2];
+    // separable source (bfd_set_sources_separable; srcK = 0: the dense table above): row r at step n is
+    // sum_k srcWeights[r*K + k] * srcSignals[n*K + k], in that order, in float32
+    int srcK; float *srcWeights, *srcSignals;
     // sensors
     unsigned char *actBase; size_t actBytes; bool actReady;   // storage of bfd_dev::act; actReady = the map matches the state (cleared by setters and bfd_reset)
     bool sensIsBox; int sensBox[5];    // the sensor set is a dense box of voxels: extents in x, y and its first voxel (i0, j0, local k0); captures then need no index list

@@ -15,6 +15,7 @@ phases and forward-propagates the re-phased array to the source plane
 import numpy as np
 
 from . import harness as H
+from .sources import SeparableSource
 
 
 def _clear_layer(plane, width):
@@ -90,6 +91,19 @@ def refocus_sources(SourceMapRayleigh, SourceMapRayleighRefocus, freq, dt, T, ra
     rows[:, :nr] *= ramp[None, :nr]
     pulse[:len(ii)] = rows[:n_rows]
     return pulse
+
+
+def refocus_sources_separable(SourceMapRayleigh, SourceMapRayleighRefocus, freq, dt, T, ramp_length=4):
+    """refocus_sources as a SeparableSource: the same rows (voxels of the ORIGINAL mask, as many rows as the refocused plane
+    has non-zero voxels, missing ones zero) in the K = 2 CW form."""
+    ii, jj = np.where(np.abs(SourceMapRayleigh) > 0)
+    u = np.asarray(SourceMapRayleighRefocus)[ii, jj]
+    n_rows = int(np.sum(np.abs(SourceMapRayleighRefocus) > 0))
+    cw = SeparableSource.cw(u, freq, dt, T, ramp_length)
+    weights = np.zeros((n_rows, 2), np.float32)
+    m = min(n_rows, len(ii))
+    weights[:m] = cw.weights[:m]
+    return SeparableSource(weights, cw.signals)
 
 
 def plane_spectrum(model, args, kwargs, SensorMapBack, PunctualSource, SourceMapPunctual):

@@ -126,6 +126,16 @@ int bfd_set_reflector(bfd_sim *sim, const uint32_t *mask, int64_t s1, int64_t s2
 int bfd_set_sources(bfd_sim *sim, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
                     const float *wx, const float *wy, const float *wz,
                     const double *pulse, int32_t nSources, int32_t lengthSource);
+/* The same sources with a separable (low-rank) table instead of the dense one (ABI 7, additive): row r at step n is
+ *   acc = weights[r*K + 0] * signals[0*lengthSource + n]; acc = acc + weights[r*K + 1] * signals[1*lengthSource + n]; ...
+ * in float32, in this order, without FMA contraction and with float32 denormals flushed -- bit for bit what the dense path
+ * computes from the float64 table of those float32 values. weights = [nSources][K], signals = [K][lengthSource], 1 <= K <= 4.
+ * A CW transducer row |u| sin(2 pi f t + arg u) ramp(t) has K = 2 (weights |u| cos arg u, |u| sin arg u; signals
+ * sin(2 pi f t) ramp(t), cos(2 pi f t) ramp(t)). Both arrays are copied to the device (nSources*K + lengthSource*K floats):
+ * nothing is streamed and the caller's arrays may go at once. Setting either form of source releases the other. */
+int bfd_set_sources_separable(bfd_sim *sim, int64_t nVox, const uint32_t *localIndex, const uint32_t *row,
+                              const float *wx, const float *wy, const float *wz,
+                              int32_t nSources, int32_t K, const float *weights, int32_t lengthSource, const float *signals);
 /* SensorMap slab (BASE:2346); returns the number of sensors of this slab in *nSensors */
 int bfd_set_sensor_map(bfd_sim *sim, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3,
                        int64_t *nSensors);
@@ -274,6 +284,10 @@ int bfd_group_set_reflector(bfd_group *g, const uint32_t *mask, int64_t s1, int6
 int bfd_group_set_sources(bfd_group *g, int64_t nVox, const int64_t *globalIndex, const uint32_t *row,
                           const float *wx, const float *wy, const float *wz,
                           const double *pulse, int32_t nSources, int32_t lengthSource);
+/* as bfd_set_sources_separable with GLOBAL voxel indices; every slab holds the whole weights and signals */
+int bfd_group_set_sources_separable(bfd_group *g, int64_t nVox, const int64_t *globalIndex, const uint32_t *row,
+                                    const float *wx, const float *wy, const float *wz,
+                                    int32_t nSources, int32_t K, const float *weights, int32_t lengthSource, const float *signals);
 int bfd_group_set_sensor_map(bfd_group *g, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3, int64_t *nSensors);
 int bfd_group_set_placement(bfd_group *g, int32_t mode, int64_t searchLimitBytes);   /* bfd_set_placement of every slab */
 int bfd_group_prepare(bfd_group *g);                     /* bfd_prepare of every slab + the halo plan; bfd_group_run does it by itself */
