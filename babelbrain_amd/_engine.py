@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     'bfd_material_tables', 'bfd_create', 'bfd_destroy', 'bfd_set_stream', 'bfd_use_private_stream', 'bfd_set_materials',
     'bfd_set_material_map', 'bfd_set_reflector', 'bfd_set_sources', 'bfd_set_sources_separable', 'bfd_set_sensor_map', 'bfd_run',
     'bfd_half_step_stress', 'bfd_half_step_velocity', 'bfd_half_step_stress_part', 'bfd_half_step_velocity_part', 'bfd_half_step_stress_part_on', 'bfd_half_step_velocity_part_on', 'bfd_sync', 'bfd_current_step', 'bfd_prepare', 'bfd_halo_region',
-    'bfd_timing_begin', 'bfd_timing_end', 'bfd_timing_kernels', 'bfd_algorithmic_bytes', 'bfd_reset', 'bfd_num_sensors', 'bfd_num_sensor_steps', 'bfd_get_sensor_index',
+    'bfd_timing_begin', 'bfd_timing_end', 'bfd_timing_kernels', 'bfd_algorithmic_bytes', 'bfd_paired_launches', 'bfd_reset', 'bfd_num_sensors', 'bfd_num_sensor_steps', 'bfd_get_sensor_index',
     'bfd_get_sensors', 'bfd_get_map', 'bfd_get_field', 'bfd_tile_counts', 'bfd_tile_count_lean', 'bfd_tile_count_fused', 'bfd_activity_counts', 'bfd_device_bytes', 'bfd_rayleigh_forward', 'bfd_get_sensor_dft', 'bfd_dft_series', 'bfd_bhte_run', 'bfd_bhte_run_fields', 'bfd_bhte_run_volumes', 'bfd_bhte_run_protocol',
     'bfd_halo_fields', 'bfd_placement_note', 'bfd_set_placement', 'bfd_group_set_placement',
     'bfd_group_create', 'bfd_group_destroy', 'bfd_group_size', 'bfd_group_slab', 'bfd_group_set_materials', 'bfd_group_set_material_map',
@@ -124,6 +124,9 @@ def load_library():
     lib.bfd_timing_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bfd_algorithmic_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.bfd_reset.argtypes = [C.c_void_p]
+    if hasattr(lib, 'bfd_paired_launches'):      # absent in older builds selected with BABELFDTD_HIP_LIB
+        lib.bfd_paired_launches.argtypes = [C.c_void_p]
+        lib.bfd_paired_launches.restype = C.c_int64
     lib.bfd_num_sensors.argtypes = [C.c_void_p]
     lib.bfd_num_sensors.restype = C.c_int64
     lib.bfd_num_sensor_steps.argtypes = [C.c_void_p]
@@ -433,6 +436,10 @@ class Engine:
 
     def reset(self):
         _check(self.lib.bfd_reset(self.h), 'bfd_reset')
+
+    def paired_launches(self):
+        """Launches of the pairing stress flavour so far (paired Pressure accumulation; 0 = every step accumulated in the velocity kernels)."""
+        return int(self.lib.bfd_paired_launches(self.h)) if hasattr(self.lib, 'bfd_paired_launches') else 0
 
     def set_placement(self, mode=1, search_limit_bytes=-1):
         """Placement policy of the per-voxel arrays (bfd_set_placement), before the first step: mode 0 = off; search_limit_bytes =

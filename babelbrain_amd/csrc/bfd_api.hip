@@ -825,6 +825,8 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     s->actBase = nullptr; s->actBytes = 0; s->actReady = false;
     s->nSensors = 0; s->sensLin = nullptr; s->sensOut = nullptr; s->dftAcc = nullptr; s->dftPk = nullptr; s->dftBin = 0;
     s->acc = s->pk = nullptr; s->timing = s->perKernel = false;
+    s->pairEnv = true; s->pendingAcc = s->pairDone = false; s->pairedLaunches = 0;
+    if (const char *ev = getenv("BFD_PAIR_ACC")) s->pairEnv = atoi(ev) != 0;      // 0: every step accumulates in the velocity kernels (A/B, tests)
     s->tables = nullptr; s->profiles = nullptr; s->cmax = 0;
     memset(s->algBytes, 0, sizeof s->algBytes); s->tiles.ktimer = nullptr;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; BFD_FAIL(-10, "hipStreamCreate failed"); }
@@ -941,10 +943,14 @@ int bfd_use_private_stream(bfd_sim *s)
     return 0;
 }
 
+static int flush_pending(bfd_sim *s, hipStream_t st);
+static int flush_pending(bfd_sim *s) { return flush_pending(s, s->stream); }
+
 int bfd_set_materials(bfd_sim *s, const double *matlist, const double *qcorr)
 {
     if (!s || !matlist) BFD_FAIL(-1, "bfd_set_materials: null argument");
     BFD_HIP(hipSetDevice(s->cfg.device));
+    { const int rc = flush_pending(s); if (rc) return rc; }      // inputs set again in the middle of a run: the maps take the outstanding Pressure first
     const bfd_config &c = s->cfg;
     for (int m = 0; m < c.nMat; m++) {
         const double *r = matlist + 5 * m;
@@ -985,6 +991,7 @@ int bfd_set_material_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2
     if (!s || !map) BFD_FAIL(-1, "bfd_set_material_map: null argument");
     if (ghostLow < 0 || ghostLow > 2 || ghostHigh < 0 || ghostHigh > 2) BFD_FAIL(-2, "ghost plane counts must be 0..2");
     BFD_HIP(hipSetDevice(s->cfg.device));
+    { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
     // upload the readable span [k=-ghostLow .. nk-1+ghostHigh]
     const uint32_t *base = map - (int64_t)ghostLow * s3;
@@ -1018,6 +1025,7 @@ int bfd_set_reflector(bfd_sim *s, const uint32_t *mask, int64_t s1, int64_t s2, 
     if (!s) BFD_FAIL(-1, "null sim");
     if (!s->haveMap) BFD_FAIL(-6, "bfd_set_reflector: set the material map first");
     BFD_HIP(hipSetDevice(s->cfg.device));
+    { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
     uint32_t *tmp = nullptr;
     if (mask) {
@@ -1084,6 +1092,7 @@ int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const 
     if (!s) BFD_FAIL(-1, "null sim");
     if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !pulse))) BFD_FAIL(-1, "bfd_set_sources: null argument");
     if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources: bad PulseSource shape");
+    { const int rc = flush_pending(s); if (rc) return rc; }
     int rc = set_source_voxels(s, "bfd_set_sources", nVox, localIndex, row, wx, wy, wz, nSources, lengthSource);
     if (rc || nVox == 0) return rc;
     const size_t np = (size_t)nSources * lengthSource;
@@ -1129,6 +1138,7 @@ int bfd_set_sources_separable(bfd_sim *s, int64_t nVox, const uint32_t *localInd
 {
     if (!s) BFD_FAIL(-1, "null sim");
     if (K < 1 || K > 4) BFD_FAIL(-2, "bfd_set_sources_separable: K must be 1..4");
+    { const int rc = flush_pending(s); if (rc) return rc; }
     if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !weights || !signals))) BFD_FAIL(-1, "bfd_set_sources_separable: null argument");
     if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources_separable: bad weights / signals shape");
     int rc = set_source_voxels(s, "bfd_set_sources_separable", nVox, localIndex, row, wx, wy, wz, nSources, lengthSource);
@@ -1158,6 +1168,7 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
 {
     if (!s || !map) BFD_FAIL(-1, "bfd_set_sensor_map: null argument");
     BFD_HIP(hipSetDevice(s->cfg.device));
+    { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
     const size_t span = span_elems(d.N1, d.N2, d.nk, s1, s2, s3);
     uint32_t *tmp = nullptr; uint8_t *flags = nullptr; uint32_t *sel = nullptr; int *dcount = nullptr; void *work = nullptr;
@@ -1245,6 +1256,9 @@ static void bind_compact_views(bfd_sim *s)
     for (int a = 0; a < 10; a++)
         *cp[a] = s->tiles.cssHosted ? s->stateBase[host[a]] + 4 * (size_t)d.plane : s->tiles.css + (size_t)a * s->tiles.cssCap;
 }
+static bool quiet_runs_wanted(const bfd_sim *s);
+static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid);
+
 static int build_tile_lists(bfd_sim *s)
 {
     int tx, ty, nsub; bfd_tile_grid(s->d, &tx, &ty, &nsub);
@@ -1670,6 +1684,7 @@ static int build_tile_lists(bfd_sim *s)
             if (e != hipSuccess) BFD_FAIL(-10, std::string("solid cell counts: ") + hipGetErrorString(e));
         }
         auto overlap = [](int a, int b, int lo, int hi) { return (double)std::max(0, std::min(b, hi) - std::max(a, lo)); };
+        const bool pairAcc = pair_engine(s, quiet_runs_wanted(s), T.nFluid);      // the predicate the launches follow (pairing_step)
         for (size_t r = 0; r < all.size(); r++) {
             const int4 &run = all[r];
             const int bx = run.x % tx, by = run.x / tx, kb = run.y & 0xFFFF, ke = run.y >> 16, f = run.z;
@@ -1686,7 +1701,10 @@ static int build_tile_lists(bfd_sim *s)
                 double bs = 12.0 + 8.0 + (lossy ? 8.0 : 0.0) + (uni ? 0.0 : 2.0);
                 if (!single) bs += 8.0 + (lossy ? 8.0 : 0.0);
                 const double bv = 4.0 + 24.0 + (uni ? 0.0 : 2.0);
-                for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_FLUID] += bs * cells; B[a][BFD_K_VELOCITY_FLUID] += bv * cells + (a ? 8.0 * inner : 0.0); }
+                for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_FLUID] += bs * cells; B[a][BFD_K_VELOCITY_FLUID] += bv * cells; }
+                // Pressure sum read and written: by velocity_fluid in every accumulating step, or (paired accumulation) by stress_fluid in
+                // every second one: 4 B per launch averaged over a step pair
+                if (pairAcc) B[1][BFD_K_STRESS_FLUID] += 4.0 * inner; else B[1][BFD_K_VELOCITY_FLUID] += 8.0 * inner;
             } else if (s->cfg.kernelVariant == 2) {     // dense: V + 6 S + 6 R read, 6 S + 6 R written, id; 6 S + V read, V written, id
                 for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_SOLID] += 110.0 * cells; B[a][BFD_K_VELOCITY_SOLID] += 50.0 * cells + (a ? 8.0 * inner : 0.0); }
             } else {                                    // class-predicated solid kernels: per-cell terms come from the class counts below
@@ -2112,14 +2130,21 @@ static int choose_placement(bfd_sim *s)
 // step 1, never see it), runs the class-specialised kernels (variants 0 / 3, in-place update) and keeps solid-only values compact; BFD_SKIP_ZERO=0
 // switches it off. The map starts with the sub-tiles of the source voxels at step 0; when inputs are set again in the middle of a run every sub-tile
 // counts as active from then on.
+static bool quiet_runs_wanted(const bfd_sim *s)          // tile lists built
+{
+    const bfd_dev &d = s->d;
+    const bool whole = d.k0 == 0 && d.nk == d.N3;
+    bool on = s->cfg.rmsFirstStep == 0 && (s->cfg.kernelVariant == 0 || s->cfg.kernelVariant == 3) && !s->pingpong &&
+              (s->tiles.nSolid == 0 || d.cssRow != nullptr) && d.nk >= 3 * bfd_tile_subz();
+    if (const char *ev = getenv("BFD_SKIP_ZERO_SLABS")) on = on && (whole || atoi(ev) != 0);      // 0: whole domains only (the first form of the round)
+    if (const char *ev = getenv("BFD_SKIP_ZERO")) on = on && atoi(ev) != 0;
+    return on;
+}
 static int setup_activity_map(bfd_sim *s)
 {
     bfd_dev &d = s->d;
     const bool whole = d.k0 == 0 && d.nk == d.N3;
-    bool on = s->cfg.rmsFirstStep == 0 && (s->cfg.kernelVariant == 0 || s->cfg.kernelVariant == 3) && !s->pingpong &&
-              s->tilesReady && (s->tiles.nSolid == 0 || d.cssRow != nullptr) && d.nk >= 3 * bfd_tile_subz();
-    if (const char *ev = getenv("BFD_SKIP_ZERO_SLABS")) on = on && (whole || atoi(ev) != 0);      // 0: whole domains only (the first form of the round)
-    if (const char *ev = getenv("BFD_SKIP_ZERO")) on = on && atoi(ev) != 0;
+    const bool on = s->tilesReady && quiet_runs_wanted(s);
     s->actReady = true;
     BFD_HIP(hipSetDevice(s->cfg.device));
     if (!on) { d.act = nullptr; drop_step_graph(s); return 0; }
@@ -2175,6 +2200,50 @@ static int check_ready(bfd_sim *s)
         bind_compact_views(s);        // the state buffers may have changed hands
     }
     if (!s->actReady) { const int rc = setup_activity_map(s); if (rc) return rc; }
+    return 0;
+}
+
+// ---- paired accumulation -------------------------------------------------------------------------------------------------
+// The Pressure sum / peak of the fluid runs costs velocity_fluid a read and a write of the map in every accumulating step. stress_fluid
+// holds, for every cell, the old Szz (the final pressure of the step before: velocity-type sources never touch Szz) and the new one in
+// registers, so accumulating steps go in pairs: in the first velocity_fluid runs its non-accumulating flavour and the engine remembers
+// that the maps lack this step (pendingAcc); in the second the pairing flavour of stress_fluid adds both steps in one read-modify-write,
+// in the order they are added otherwise. Whatever reads or clears the maps, or changes what lies behind them, flushes first
+// (flush_pending: one small kernel adds the Pressure of the current Szz); the next accumulating step then opens a new pair. The solid
+// runs are not paired (their pressure needs Sxx / Syy, which the sparse kernel writes after stress_fluid): velocity_solid accumulates in
+// every step; a cell belongs to one run class, so the two schemes do not meet. Both parts of a split half-step take the same flavour, the
+// state flips where the step counter advances. Bit-identical to accumulating in every step; BFD_PAIR_ACC=0 selects that path.
+// Off with stress-type sources (they change Szz between the two kernels), outside variants 0 / 3, with the second copies of variant 4,
+// and with quiet runs (those flavours accumulate in 2 % of a call's steps). Graph replay covers non-accumulating steps only.
+static int pressure_slot(const bfd_sim *s)
+{
+    int qP = -1;
+    for (int q = 0; q < s->nSelR; q++) if (s->selR[q] == BFD_MAP_PRESSURE) qP = q;
+    return qP;
+}
+// The accumulating steps of this engine pair: ONE predicate for the byte tables (build_tile_lists: quiet = quiet_runs_wanted, the run count just
+// built) and for the launches (pairing_step: quiet = the activity map is in use, the current run count)
+static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid)
+{
+    return s->pairEnv && s->cfg.typeSource < 2 && (s->cfg.kernelVariant == 0 || s->cfg.kernelVariant == 3) && !s->pingpong && !quiet &&
+           nFluid > 0 && (s->acc || s->pk) && pressure_slot(s) >= 0;
+}
+// this step's accumulation of the fluid runs is paired (constant over the parts of a time step; pairDone: its stress half-step has already
+// taken the pairing flavour, so the step stays paired whatever a setter did in between)
+static bool pairing_step(const bfd_sim *s)
+{
+    return s->pairDone || (s->step >= s->accStart && s->tilesReady && pair_engine(s, s->d.act != nullptr, s->tiles.nFluid));
+}
+// st: the stream the following launches go to (default: the engine's)
+static int flush_pending(bfd_sim *s, hipStream_t st)
+{
+    if (!s->pendingAcc) return 0;        // also between the half-steps of the second step of a pair: its stress half-step has added both (pairDone)
+    s->pendingAcc = false;
+    const int qP = pressure_slot(s);
+    if (qP < 0 || !s->tilesReady) return 0;
+    BFD_HIP(hipSetDevice(s->cfg.device));
+    bfd_launch_flush_paired(s->d, st, s->acc ? s->acc + (size_t)qP * s->nloc : nullptr, s->pk ? s->pk + (size_t)qP * s->nloc : nullptr, &s->tiles);
+    BFD_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2235,7 +2304,19 @@ static int stress_part(bfd_sim *s, int part, hipStream_t st)
     }
     if (s->pingpong && part != 0) BFD_FAIL(-2, "split half-steps are not available with kernelVariant 4 on a whole domain");
     if (s->cfg.kernelVariant == 1) { if (part != 1) bfd_launch_stress_v1(s->d, st); }
-    else bfd_launch_stress_v2(s->d, st, &s->tiles, part);
+    else {
+        float *accP = nullptr, *pkP = nullptr;
+        if (s->pendingAcc && !pairing_step(s)) { rc = flush_pending(s, st); if (rc) return rc; }
+        if (s->pendingAcc || s->pairDone) {          // second step of a pair: the maps take the previous step's Pressure and this one's
+            const int qP = pressure_slot(s);
+            accP = s->acc ? s->acc + (size_t)qP * s->nloc : nullptr; pkP = s->pk ? s->pk + (size_t)qP * s->nloc : nullptr;
+            s->pairedLaunches++;
+            // from here on the maps hold this step: a flush between the half-steps must add nothing (the other part of a split half-step
+            // still takes the pairing flavour for its own cells)
+            s->pendingAcc = false; s->pairDone = true;
+        }
+        bfd_launch_stress_v2(s->d, st, &s->tiles, part, accP, pkP);
+    }
     if (e0) { hipEventRecord(e1, st); s->evStress.push_back(e0); s->evStress.push_back(e1); }
     if (s->nSrcVox && s->cfg.typeSource >= 2 && s->step < s->lengthSource) { rc = inject_part(s, part, new_stress_view(s->d), st); if (rc) return rc; }
     BFD_HIP(hipGetLastError());
@@ -2256,6 +2337,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
     }
     const int n = s->step;
     const bool accNow = (s->acc || s->pk) && n >= s->accStart;
+    const bool paired = pairing_step(s);      // the fluid runs' Pressure goes through stress_fluid (paired accumulation)
     int qP = -1;   // Pressure is accumulated inside the tiled velocity kernels
     if (accNow && s->cfg.kernelVariant != 1)
         for (int q = 0; q < s->nSelR; q++) if (s->selR[q] == BFD_MAP_PRESSURE) qP = q;
@@ -2267,7 +2349,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
             if (part != 0) BFD_FAIL(-2, "split half-steps are not available with kernelVariant 4 on a whole domain");
             bfd_launch_fused(d, st, accP, pkP, &s->tiles, 0, s->tiles.nFused);        // both half-steps of its runs: old fields -> W copies
         }
-        bfd_launch_velocity_v2(new_stress_view(d), st, accP, pkP, &s->tiles, part);
+        bfd_launch_velocity_v2(new_stress_view(d), st, accP, pkP, &s->tiles, part, !paired);
     }
     if (e0) { hipEventRecord(e1, st); s->evVelocity.push_back(e0); s->evVelocity.push_back(e1); }
     if (s->nSrcVox && s->cfg.typeSource < 2 && s->step < s->lengthSource) { rc = inject_part(s, part, new_velocity_view(d), st); if (rc) return rc; }
@@ -2306,6 +2388,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
         }
     }
     BFD_HIP(hipGetLastError());
+    if (paired) { s->pendingAcc = !s->pairDone; s->pairDone = false; }      // first step of a pair: the maps lack it; second: settled in its stress half-step
     s->step++;
     s->stepDevValid = false;
     return 0;
@@ -2537,6 +2620,8 @@ int bfd_algorithmic_bytes(bfd_sim *s, int32_t accumulating, double *bytesPerClas
     return 0;
 }
 
+int64_t bfd_paired_launches(bfd_sim *s) { return s ? s->pairedLaunches : -1; }
+
 int bfd_reset(bfd_sim *s)
 {
     if (!s) BFD_FAIL(-1, "null sim");
@@ -2561,6 +2646,7 @@ int bfd_reset(bfd_sim *s)
         if (s->nSensors > 0) hipLaunchKernelGGL(fill_float, dim3(grid_for((long)s->nSelS * s->nSensors)), dim3(256), 0, s->stream, s->dftPk, (long)s->nSelS * s->nSensors, -INFINITY);
     }
     s->step = 0; s->stepDevValid = false; s->actReady = false;         // the activity map starts over with the state
+    s->pendingAcc = s->pairDone = false;                               // the maps were cleared: nothing is outstanding
     BFD_HIP(hipStreamSynchronize(s->stream));
     drain_pack_jobs(s);
     for (int b = 0; b < 2; b++) s->tileLoaded[b] = -1;        // the streamed source table starts over (tiles are re-packed on demand)
@@ -2759,6 +2845,7 @@ int bfd_get_map(bfd_sim *s, int32_t kind, int32_t map, float *out, int64_t s1, i
     for (int a = 0; a < s->nSelR; a++) if (s->selR[a] == map) q = a;
     if (kind != BFD_KIND_LAST && q < 0) BFD_FAIL(-2, "bfd_get_map: map was not selected in selMapsRMS");
     float *tmp = nullptr;
+    if (kind == BFD_KIND_RMS || kind == BFD_KIND_PEAK) { const int rf = flush_pending(s); if (rf) return rf; }
     BFD_HIP(hipMalloc((void **)&tmp, s->nloc * sizeof(float)));
     int rc = 0;
     if (kind == BFD_KIND_RMS) {

@@ -189,6 +189,11 @@ struct bfd_sim {
     // accumulators
     int nSelR; int selR[BFD_MAP_COUNT]; float *acc, *pk;
     int accStart;
+    // Paired Pressure accumulation (bfd_api.hip, "paired accumulation"): pairEnv = BFD_PAIR_ACC is not 0; pendingAcc = the Pressure of the current Szz
+    // has not been added to the maps at the cells of the fluid runs yet (the next stress half-step adds it together with its own, or a flush does);
+    // pairDone = the stress half-step of the current step took the pairing flavour (the maps hold this step already; cleared where the step counter
+    // advances); pairedLaunches counts the launches of the pairing stress flavour (bfd_paired_launches)
+    bool pairEnv, pendingAcc, pairDone; int64_t pairedLaunches;
     // timing
     bool timing, perKernel;
     hipEvent_t evBegin, evEnd;
@@ -253,6 +258,10 @@ int bfd_tile_zchunk(void);
 // placement probe: arrays a and b (pointers to local plane 0) updated in place along all runs of the slab, planes [0, kmax)
 void bfd_launch_probe_pair(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, float *a, float *b, int kmax);
 // part: 0 = every tile, 1 = boundary tiles, 2 = interior tiles (variant 2 lists every tile as solid)
-void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part);
-// accP / pkP: Pressure RMS / peak accumulators of this step (slab-local, x-fastest) or nullptr
-void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int part);
+// accP / pkP not null: the plain fluid runs take the pairing flavour, which adds the Pressure of the previous and of this step to the maps
+void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part, float *accP = nullptr, float *pkP = nullptr);
+// accP / pkP: Pressure RMS / peak accumulators of this step (slab-local, x-fastest) or nullptr; fluidAcc = false: only the solid runs
+// accumulate (the fluid runs are paired in the stress half-step)
+void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc = true);
+// adds the Pressure of the current Szz to the maps at the accumulating cells of the fluid runs (paired accumulation with its partner step outstanding)
+void bfd_launch_flush_paired(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t);

@@ -530,10 +530,15 @@ __device__ __forceinline__ unsigned fbits(float v) { return __float_as_uint(v); 
 // a fluid: the same expression serves every lane, equal to the fluid one up to the sign of an exact zero); everything else a solid cell has --
 // Sxx, Syy, the shear stresses and their memory variables -- is the sparse kernel's (stress_shear_sparse, which runs after this one and reads
 // the absorbing-layer memory variables this kernel has just advanced).
-template <bool LOSSY, bool COLLAPSED, bool UNI, bool PML, bool SOLID = false, bool QUIET = false>
+// PAIR (paired Pressure accumulation; non-SOLID, non-QUIET flavours): the cell's old Szz is the final pressure of the previous step (velocity-type
+// sources never touch Szz) and the new one that of this step, so ONE read-modify-write of the running sum here, in every second accumulating step, adds
+// both squares in the order the velocity kernel adds them, (acc + p_old^2) + p_new^2, and velocity_fluid leaves the sum alone (bfd_api.hip, "paired
+// accumulation"). The sum runs one plane ahead like the other streams; the peak is read where it is used, as in velocity_fluid_body.
+template <bool LOSSY, bool COLLAPSED, bool UNI, bool PML, bool SOLID = false, bool QUIET = false, bool PAIR = false>
 __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int by, int kbeg, int kend, int tm,
-                                                  float (*sV)[2][LH * LW])
+                                                  float (*sV)[2][LH * LW], float *__restrict__ accP = nullptr, float *__restrict__ pkP = nullptr)
 {
+    static_assert(!PAIR || (!SOLID && !QUIET), "paired accumulation: plain fluid flavours only");
     unsigned nzb = 0u;          // QUIET: bits of everything stored
     // The three normal stresses are identical in a FLUID tile; Szz is the one that is read (it is
     // also the one whose ghost planes the Z-neighbour exchange carries), all three are written.
@@ -574,10 +579,13 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
         if (valid && (kg < P || kg >= d.N3 - P)) pz = F4(d.psi[2], (unsigned)((long)(kg < P ? kg : kg - (d.N3 - 2 * P)) * pl + cij) * 4u);
     }
 
-    float vx0 = 0, vy0 = 0, vzm2 = 0, vzm1 = 0, vz0 = 0, vzp1 = 0, szz = 0, rzz = 0;
+    const bool inner = PAIR && valid && i >= d.ND && i < N1 - d.ND && j >= d.ND && j < N2 - d.ND;
+    const bool accA = PAIR && accP != nullptr, accK = PAIR && pkP != nullptr;
+    float vx0 = 0, vy0 = 0, vzm2 = 0, vzm1 = 0, vz0 = 0, vzp1 = 0, szz = 0, rzz = 0, av = 0;
     unsigned mraw = 0;
     if (valid) {
         const float *bVz = d.Vz + kbeg * pl;
+        if (accA) av = LD4((accP + kbeg * pl), cij * 4u);
         vx0 = F4((d.Vx + kbeg * pl), cij * 4u); vy0 = F4((d.Vy + kbeg * pl), cij * 4u);
         vzm2 = LD4((bVz - 2 * pl), cij * 4u); vzm1 = LD4((bVz - pl), cij * 4u); vz0 = LD4(bVz, cij * 4u); vzp1 = LD4((bVz + pl), cij * 4u);
         szz = LD4((d.Szz + kbeg * pl), cij * 4u);
@@ -597,12 +605,13 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
         if (!UNI && valid) { const int m = mraw & BFD_MAT_MASK; AP = d.AP[m]; if (LOSSY) BP = d.BP[m]; if (SOLID) { AS2 = d.AS2[m]; BS2 = d.BS2[m]; } }
         __syncthreads();
 
-        float nvx = 0, nvy = 0, nvz = 0, nh = 0, nszz = 0, nrzz = 0, npx = 0, npy = 0, npz = 0;
+        float nvx = 0, nvy = 0, nvz = 0, nh = 0, nszz = 0, nrzz = 0, npx = 0, npy = 0, npz = 0, nav = 0;
         unsigned nmraw = 0;
         if (kl + 1 < kend) {
             if (valid) {
                 nvx = F4((d.Vx + ko + pl), cij * 4u); nvy = F4((d.Vy + ko + pl), cij * 4u); nvz = LD4((d.Vz + ko + 2 * pl), cij * 4u);
                 nszz = LD4((d.Szz + ko + pl), cij * 4u);
+                if (accA) nav = LD4((accP + ko + pl), cij * 4u);
                 if (LOSSY) nrzz = LD4((d.Rzz + ko + pl), cij * 4u);
                 if (!UNI) nmraw = U2((d.mat + ko + pl), cij * 2u);
             }
@@ -645,6 +654,20 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
             // COLLAPSED (no solid tile in the slab, no per-component stress output selected): nobody
             // reads Sxx/Syy/Rxx/Ryy, so only the Szz/Rzz copy is kept (expanded on demand, bfd_api.hip)
             ST4((d.SzzW + ko), cij * 4u, val);
+            if (PAIR) {
+                if (inner && k >= d.ND && k < d.N3 - d.ND) {
+                    const float so = (szz + szz) + szz, sn = (val + val) + val;
+                    const float po = -so * (1.0f / 3.0f), pn = -sn * (1.0f / 3.0f);
+                    if (accA) ST4((accP + ko), cij * 4u, (av + po * po) + pn * pn);
+                    if (accK) {
+                        const float m0 = F4((pkP + ko), cij * 4u), ao = fabsf(po), an = fabsf(pn);
+                        float m = m0;
+                        if (ao > m) m = ao;
+                        if (an > m) m = an;
+                        if (m > m0) F4((pkP + ko), cij * 4u) = m;
+                    }
+                }
+            }
             if (QUIET) nzb |= fbits(val) | fbits(rn);
             if (!COLLAPSED) { F4((d.Sxx + ko), cij * 4u) = val; F4((d.Syy + ko), cij * 4u) = val; }
             if (LOSSY) {
@@ -654,7 +677,7 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
         }
         vx0 = nvx; vy0 = nvy;
         vzm2 = vzm1; vzm1 = vz0; vz0 = vzp1; vzp1 = nvz;
-        hv = nh; szz = nszz; rzz = nrzz; mraw = nmraw;
+        hv = nh; szz = nszz; rzz = nrzz; mraw = nmraw; av = nav;
         px = npx; py = npy; pz = npz; qx += dqx; qy += dqy;
     }
     if (QUIET) run_mark_active(d, bx, by, kbeg, kend, nzb);
@@ -2288,8 +2311,9 @@ __global__ void shear_material_table(bfd_dev d, float *__restrict__ tab, int nMa
 // ---- dispatchers: one launch for all fluid runs; block-uniform switch on the run's flags ----
 // run = (x: bx + tilesX*by, y: kbeg | kend<<16, z: flags, w: material id of UNI runs)
 // flags: bit0 solid, bit1 lossy, bit2 UNI, bit3 PML, bit4 LEAN
-template <bool COLLAPSED, bool QUIET = false>
-__device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4 &run, int tilesX, float (*sV)[2][LH * LW])
+template <bool COLLAPSED, bool QUIET = false, bool PAIR = false>
+__device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4 &run, int tilesX, float (*sV)[2][LH * LW],
+                                                    float *__restrict__ accP = nullptr, float *__restrict__ pkP = nullptr)
 {
     const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16, tm = run.w;
     if (QUIET && run_all_quiet(d, bx, by, kbeg, kend)) return;
@@ -2299,14 +2323,14 @@ __device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4
         return;
     }
     switch ((run.z >> 1) & 7) {
-    case 0: stress_fluid_body<false, COLLAPSED, false, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 1: stress_fluid_body<true, COLLAPSED, false, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 2: stress_fluid_body<false, COLLAPSED, true, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 3: stress_fluid_body<true, COLLAPSED, true, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 4: stress_fluid_body<false, COLLAPSED, false, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 5: stress_fluid_body<true, COLLAPSED, false, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    case 6: stress_fluid_body<false, COLLAPSED, true, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
-    default: stress_fluid_body<true, COLLAPSED, true, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sV); break;
+    case 0: stress_fluid_body<false, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 1: stress_fluid_body<true, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 2: stress_fluid_body<false, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 3: stress_fluid_body<true, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 4: stress_fluid_body<false, COLLAPSED, false, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 5: stress_fluid_body<true, COLLAPSED, false, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 6: stress_fluid_body<false, COLLAPSED, true, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    default: stress_fluid_body<true, COLLAPSED, true, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
     }
 }
 
@@ -2333,18 +2357,42 @@ __device__ __forceinline__ void xcd_clock_end(int) {}
 
 // COLLAPSED = true: all-fluid slab, every run keeps only Szz/Rzz. false: slab with solid tiles; runs flagged LEAN
 // (bit4) still take the collapsed bodies, the others write all three normal stresses.
-template <bool COLLAPSED, bool QUIET = false>
+template <bool COLLAPSED, bool QUIET = false, bool PAIR = false>
 __global__ __launch_bounds__(NTHREADS, FLUID_WAVES_PER_SIMD) void stress_fluid(bfd_dev d, int tilesX, int nblocks, const int *__restrict__ xmap,
-                                                                               const int4 *__restrict__ runs)
+                                                                               const int4 *__restrict__ runs,
+                                                                               float *__restrict__ accP, float *__restrict__ pkP)
 {
     __shared__ float sV[2][2][LH * LW];
     const int ri = run_index(nblocks, xmap);
     if (ri < 0) return;
     const int4 run = runs[ri];
     xcd_clock_begin(0);
-    if (COLLAPSED || (run.z & 16)) stress_fluid_switch<true, QUIET>(d, run, tilesX, sV);
-    else stress_fluid_switch<false, QUIET>(d, run, tilesX, sV);
+    if (COLLAPSED || (run.z & 16)) stress_fluid_switch<true, QUIET, PAIR>(d, run, tilesX, sV, accP, pkP);
+    else stress_fluid_switch<false, QUIET, PAIR>(d, run, tilesX, sV, accP, pkP);
     xcd_clock_end(0);
+}
+
+// Paired accumulation, flush: the Pressure of the current Szz that the pairing stress flavour has not added yet, at the cells velocity_fluid
+// would have accumulated (fluid runs, inside the accumulation region): same expressions, one workgroup per run.
+__global__ __launch_bounds__(NTHREADS) void flush_paired_pressure(bfd_dev d, int tilesX, int nruns, const int4 *__restrict__ runs,
+                                                                  float *__restrict__ accP, float *__restrict__ pkP)
+{
+    if ((int)blockIdx.x >= nruns) return;
+    const int4 run = runs[blockIdx.x];
+    const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16;
+    const int i = bx * TX + (int)threadIdx.x, j = by * TY + (int)threadIdx.y;
+    if (!(i >= d.ND && i < d.N1 - d.ND && j >= d.ND && j < d.N2 - d.ND)) return;
+    const long cij = (long)j * d.N1 + i;
+    for (int kl = kbeg; kl < kend; kl++) {
+        const int k = d.k0 + kl;
+        if (k < d.ND || k >= d.N3 - d.ND) continue;
+        const long c = (long)kl * d.plane + cij;
+        const float s0 = d.Szz[c];
+        const float s = (s0 + s0) + s0;
+        const float p = -s * (1.0f / 3.0f);
+        if (accP) accP[c] = accP[c] + p * p;
+        if (pkP) { const float ap = fabsf(p); if (ap > pkP[c]) pkP[c] = ap; }
+    }
 }
 
 template <bool ACC, bool QUIET = false>
@@ -2580,8 +2628,16 @@ static inline void part_range(int n, int nB, int part, int *off, int *cnt)
     else { *off = 0; *cnt = n; }
 }
 
-void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, int part)
+void bfd_launch_flush_paired(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t)
 {
+    const int tilesX = (d.N1 + TX - 1) / TX;
+    if (t->nFluid > 0 && (accP || pkP))
+        hipLaunchKernelGGL(flush_paired_pressure, dim3(t->nFluid), dim3(TX, TY, 1), 0, s, d, tilesX, t->nFluid, (const int4 *)t->runs, accP, pkP);
+}
+
+void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, int part, float *accP, float *pkP)
+{
+    const bool pair = (accP || pkP) && !d.act;       // the pairing flavour of the plain fluid runs (quiet runs never pair)
     const int tilesX = (d.N1 + TX - 1) / TX;
     int off, n, offS, nS;
     part_range(t->nFluid, t->nFluidB, part, &off, &n);
@@ -2596,8 +2652,9 @@ void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, 
         part_range(t->nAll, t->nAllB, part, &offA, &nA);
         if (nA) {
             BFD_KT(BFD_K_STRESS_FLUID, 0);
-            if (d.act) BFD_LAUNCH((stress_fluid<true, true>), nA, (const int *)nullptr, t->runsAll + offA);
-            else BFD_LAUNCH((stress_fluid<true>), nA, (const int *)nullptr, t->runsAll + offA);
+            if (d.act) BFD_LAUNCH((stress_fluid<true, true>), nA, (const int *)nullptr, t->runsAll + offA, (float *)nullptr, (float *)nullptr);
+            else if (pair) BFD_LAUNCH((stress_fluid<true, false, true>), nA, (const int *)nullptr, t->runsAll + offA, accP, pkP);
+            else BFD_LAUNCH((stress_fluid<true>), nA, (const int *)nullptr, t->runsAll + offA, (float *)nullptr, (float *)nullptr);
             BFD_KT(BFD_K_STRESS_FLUID, 1);
         }
         n = 0; nS = 0;
@@ -2635,17 +2692,19 @@ void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, 
     s = s0;
     if (n) {
         BFD_KT(BFD_K_STRESS_FLUID, 0);
-        if (d.act) BFD_LAUNCH_X((stress_fluid<true, true>), n, BFD_XM_SF + part, t->runs + off);
-        else BFD_LAUNCH_X((stress_fluid<true>), n, BFD_XM_SF + part, t->runs + off);      // fluid cells keep one copy of their normal stresses (bfd_dev::cls)
+        if (d.act) BFD_LAUNCH_X((stress_fluid<true, true>), n, BFD_XM_SF + part, t->runs + off, (float *)nullptr, (float *)nullptr);
+        else if (pair) BFD_LAUNCH_X((stress_fluid<true, false, true>), n, BFD_XM_SF + part, t->runs + off, accP, pkP);
+        else BFD_LAUNCH_X((stress_fluid<true>), n, BFD_XM_SF + part, t->runs + off, (float *)nullptr, (float *)nullptr);      // fluid cells keep one copy of their normal stresses (bfd_dev::cls)
         BFD_KT(BFD_K_STRESS_FLUID, 1);
     }
     if (conc) for (int q = 0; q < 2; q++) { hipEventRecord(t->sideJoin[q], t->sideStream[q]); hipStreamWaitEvent(s0, t->sideJoin[q], 0); }
 }
 
-void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float *pkP, const bfd_tiles *t, int part)
+void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc)
 {
     const int tilesX = (d.N1 + TX - 1) / TX;
     const bool acc = accP || pkP;
+    const bool accF = acc && fluidAcc;      // paired accumulation: the stress kernel adds the Pressure of the fluid runs
     int offF, nF, off, n;
     part_range(t->nFluid, t->nFluidB, part, &offF, &nF);
     part_range(t->nSolid, t->nSolidB, part, &off, &n);
@@ -2701,9 +2760,9 @@ void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float
     if (nF) {
         BFD_KT(BFD_K_VELOCITY_FLUID, 0);
         if (d.act) {
-            if (acc) BFD_LAUNCH_X((velocity_fluid<true, true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
+            if (accF) BFD_LAUNCH_X((velocity_fluid<true, true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
             else BFD_LAUNCH_X((velocity_fluid<false, true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
-        } else if (acc) BFD_LAUNCH_X((velocity_fluid<true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
+        } else if (accF) BFD_LAUNCH_X((velocity_fluid<true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
         else BFD_LAUNCH_X((velocity_fluid<false>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
         BFD_KT(BFD_K_VELOCITY_FLUID, 1);
     }

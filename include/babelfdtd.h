@@ -213,8 +213,17 @@ int bfd_timing_kernels(bfd_sim *sim, double *msPerClass, int64_t *launchesPerCla
 /* ALGORITHMIC bytes one launch of each kernel class has to move (same class order), from the tile-class counts: every
  * field value of the class's per-cell byte table fetched / stored exactly once (float32 4 B, material id 2 B; absorbing-
  * layer memory variables, coefficient tables and halo re-reads excluded). accumulating != 0 adds the
- * Pressure RMS accumulator (8 B per cell outside the absorbing layer) to the velocity classes. DESIGN.md section 6. */
+ * Pressure RMS accumulator (8 B per cell outside the absorbing layer) to the velocity classes; where the accumulation of the
+ * fluid runs is paired (bfd_paired_launches) it is 4 B per launch of the fluid stress class instead: the average over a step
+ * pair. DESIGN.md section 6. */
 int bfd_algorithmic_bytes(bfd_sim *sim, int32_t accumulating, double *bytesPerClass);
+/* Paired Pressure accumulation (all-fluid runs, velocity-type sources, rmsFirstStep >= 1 or quiet runs off): accumulating steps go in
+ * pairs, the stress half-step of the second adds the Pressure of both to the RMS / peak maps; bfd_get_map, bfd_reset and the
+ * setters settle an open pair first, so results equal accumulating in every step bit for bit. BFD_PAIR_ACC=0 switches it off.
+ * Between the two half-steps of a time step the RMS / peak maps of the fluid runs may already hold that step (second step of a pair;
+ * otherwise they hold the steps before it, as without pairing); after bfd_half_step_velocity they are the same either way.
+ * Returns the number of launches of the pairing stress flavour so far (0: every step accumulated in the velocity kernels). */
+int64_t bfd_paired_launches(bfd_sim *sim);
 /* back to step 0: fields, absorbing-layer memory, accumulators and the sensor block zeroed; inputs are kept */
 int bfd_reset(bfd_sim *sim);
 
