@@ -831,12 +831,6 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     memset(s->algBytes, 0, sizeof s->algBytes); s->tiles.ktimer = nullptr;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; BFD_FAIL(-10, "hipStreamCreate failed"); }
     s->ownStream = true;
-    if (const char *ev = getenv("BFD_CONCURRENT")) if (atoi(ev) != 0) {     // experiment: solid-run kernels beside the fluid kernel (bfd_tiles::sideStream)
-        bfd_tiles &T = s->tiles;
-        bool ok = hipEventCreateWithFlags(&T.sideFork, hipEventDisableTiming) == hipSuccess;
-        for (int q = 0; q < 2 && ok; q++) ok = hipStreamCreateWithFlags(&T.sideStream[q], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&T.sideJoin[q], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { T.sideStream[0] = T.sideStream[1] = nullptr; (void)hipGetLastError(); }
-    }
     if (hipEventCreate(&s->evBegin) != hipSuccess) { hipStreamDestroy(s->stream); delete s; BFD_FAIL(-10, "hipEventCreate failed"); }
     if (hipEventCreate(&s->evEnd) != hipSuccess) { hipEventDestroy(s->evBegin); hipStreamDestroy(s->stream); delete s; BFD_FAIL(-10, "hipEventCreate failed"); }
 
@@ -916,8 +910,6 @@ void bfd_destroy(bfd_sim *s)
     for (hipEvent_t e : s->evVelocity) hipEventDestroy(e);
     for (auto &v : s->evK) for (hipEvent_t e : v) hipEventDestroy(e);
     hipEventDestroy(s->evBegin); hipEventDestroy(s->evEnd);
-    for (int q = 0; q < 2; q++) { if (s->tiles.sideStream[q]) hipStreamDestroy(s->tiles.sideStream[q]); if (s->tiles.sideJoin[q]) hipEventDestroy(s->tiles.sideJoin[q]); }
-    if (s->tiles.sideFork) hipEventDestroy(s->tiles.sideFork);
     if (s->ownStream) hipStreamDestroy(s->stream);
     delete s;
 }
@@ -1242,9 +1234,6 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
 // Build the run lists of the tiled kernels (bfd_kernels_v2.hip). Sub-tiles of 64 x 8 x 8 cells are
 // classified on the device; consecutive sub-tiles of one (bx,by) column with identical class merge into
 // runs that never cross a 32-plane chunk boundary. Variant 2: every sub-tile counts as solid (dense kernels).
-#ifndef BFD_SOLID_MERGED_DEFAULT
-#define BFD_SOLID_MERGED_DEFAULT 0
-#endif
 // where the ten compact arrays live (bfd_tiles::cssHosted); called when the list is built and again whenever the state buffers change hands
 // (choose_placement exchanges them at step 0, when everything is still zero)
 static void bind_compact_views(bfd_sim *s)
@@ -1316,7 +1305,7 @@ static int build_tile_lists(bfd_sim *s)
     T.nMat = s->cfg.nMat;
     // solid runs: normal and shear stresses in one kernel (stress_solid_merged), the sparse list keeps the cells with an edge between
     // different solids. BFD_SOLID_MERGED=0 selects the two-kernel form (stress_solid + stress_shear_sparse over every solid cell).
-    T.merged = BFD_SOLID_MERGED_DEFAULT != 0;
+    T.merged = false;
     if (const char *ev = getenv("BFD_SOLID_MERGED")) T.merged = atoi(ev) != 0;
     if (s->step > 0 && hadList) T.merged = hadListR ? false : wasMerged;       // a list rebuilt in the middle of a run keeps the form it started with (where its shear memory variables live)
     T.nFluid = T.nFluidB = T.nSolid = T.nSolidB = T.nSolidBP = T.nSolidIP = T.nFused = T.nLossless = T.nLossy = T.nSolidSub = T.nUni = T.nPml = T.nLean = T.nFusedSub = 0;
@@ -1339,8 +1328,7 @@ static int build_tile_lists(bfd_sim *s)
     // z-chunk the rows are scanned upwards: where three consecutive tile rows qualify over a z-stretch they form a run and the
     // scan moves on by three rows. A run is UNI when every sub-tile is (one material in the grown regions) and lossy when a
     // cell of a grown region relaxes (bit7); stretches are cut where that class changes (a single sub-tile joins its neighbour).
-    int fusedSub = 32 / SUB;
-    if (const char *ev = getenv("BFD_FUSED_ZRUN")) { const int z = atoi(ev); if (z >= 2 * SUB && z % SUB == 0 && z <= 0x7000) fusedSub = z / SUB; }
+    const int fusedSub = 32 / SUB;
     struct FusedRun { int bx, by, q0, q1, cls, mat; };
     std::vector<FusedRun> fruns;
     if (s->pingpong && s->cfg.typeSource < 2) {
@@ -1426,14 +1414,11 @@ static int build_tile_lists(bfd_sim *s)
         } else if (mode == 0) {     // column order
             for (int txy = 0; txy < tx * ty; txy++) for (int c = 0; c < nChunks; c++) seq.push_back({txy, c});
         } else {                    // 8 y-bands (one per XCD part), inside a band z-chunk slowest
-            // mode 3 (experiment): the two z-chunks of the absorbing layer first, the interior chunks after them -- the cheapest
-            // workgroups at the end of every XCD's part of the list
-            std::vector<int> corder;
-            if (mode == 3 && nChunks > 2) { corder.push_back(0); corder.push_back(nChunks - 1); for (int c = 1; c + 1 < nChunks; c++) corder.push_back(c); }
-            else for (int c = 0; c < nChunks; c++) corder.push_back(c);
+            // (the two z-chunks of the absorbing layer first, so that the cheapest workgroups end every XCD's part of the list: no gain, removed;
+            // profiles/r4/)
             for (int e = 0; e < 8; e++) {
                 const int y0 = (int)((long)ty * e / 8), y1 = (int)((long)ty * (e + 1) / 8);
-                for (int c : corder) for (int by = y0; by < y1; by++) for (int bx = 0; bx < tx; bx++) seq.push_back({by * tx + bx, c});
+                for (int c = 0; c < nChunks; c++) for (int by = y0; by < y1; by++) for (int bx = 0; bx < tx; bx++) seq.push_back({by * tx + bx, c});
             }
         }
     }
@@ -1498,8 +1483,7 @@ static int build_tile_lists(bfd_sim *s)
         s->tiles.xmap = nullptr;
         memset(s->tiles.xmapH, 0, sizeof s->tiles.xmapH);
         if (on) {
-            double wPml = 0.25, wLossy = 8, wMulti = 2, wRun = 2.0;
-            if (const char *ev = getenv("BFD_XCD_WEIGHTS")) sscanf(ev, "%lf,%lf,%lf,%lf", &wPml, &wLossy, &wMulti, &wRun);
+            const double wPml = 0.25, wLossy = 8, wMulti = 2, wRun = 2.0;
             // cost of run r for kernel class c: 0 fluid stress, 1 fluid velocity, 2 solid stress, 3 solid velocity
             auto cost = [&](const int4 &r, int c) {
                 const double planes = (double)((r.y >> 16) - (r.y & 0xFFFF)) + wRun;
@@ -1538,13 +1522,6 @@ static int build_tile_lists(bfd_sim *s)
             make(BFD_XM_VS + 0, S0 + bp, S0 + SN - ip, 3); make(BFD_XM_VS + 1, S0 + bp, S0 + SB, 3); make(BFD_XM_VS + 2, S0 + SB, S0 + SN - ip, 3);
             make(BFD_XM_VSP_LO, S0, S0 + bp, 3); make(BFD_XM_VSP_HI, S0 + SN - ip, S0 + SN, 3);
             make(BFD_XM_FUSED, S0 + SN, S0 + SN + T.nFused, 0);
-            if (getenv("BFD_XCD_VERBOSE"))
-                for (int m = 0; m < BFD_XMAP_COUNT; m++) {
-                    const int *g = s->tiles.xmapH[m];
-                    fprintf(stderr, "xcd map %2d: runs %d, parts", m, g[8]);
-                    for (int x = 0; x < 8; x++) fprintf(stderr, " %d", g[x + 1] - g[x]);
-                    fprintf(stderr, " (longest %d)\n", g[9]);
-                }
             rc = dev_alloc(s, &s->tiles.xmap, (size_t)BFD_XMAP_COUNT * 10, false);
             if (rc) return rc;
             BFD_HIP(hipMemcpy(s->tiles.xmap, s->tiles.xmapH, sizeof s->tiles.xmapH, hipMemcpyHostToDevice));
@@ -1573,17 +1550,15 @@ static int build_tile_lists(bfd_sim *s)
         std::vector<unsigned> hostCells((size_t)count);
         if (e == hipSuccess && count) e = hipMemcpy(hostCells.data(), sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost);
         // list order (bfd_kernels_v2.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
-        // touched one band-plane earlier instead of one whole plane of the shell; BFD_SHEAR_ORDER=0 keeps the ascending index, 1 = by tiles
-        int orderMode = 2;
-        if (const char *ev = getenv("BFD_SHEAR_ORDER")) orderMode = atoi(ev);
-        const bool reorder = count > 0 && orderMode != 0;
+        // touched one band-plane earlier instead of one whole plane of the shell
+        const bool reorder = count > 0;
         if (e == hipSuccess && reorder) {
             unsigned long long *k0 = nullptr, *k1 = nullptr; unsigned *v1 = nullptr; void *w2 = nullptr; size_t w2b = 0;
             e = hipMalloc((void **)&k0, (size_t)count * 8);
             if (e == hipSuccess) e = hipMalloc((void **)&k1, (size_t)count * 8);
             if (e == hipSuccess) e = hipMalloc((void **)&v1, (size_t)count * 4);
             if (e == hipSuccess) {
-                bfd_launch_shear_order_keys(s->d, s->stream, sel, k0, count, lowPlanes, hiStart, orderMode);
+                bfd_launch_shear_order_keys(s->d, s->stream, sel, k0, count, lowPlanes, hiStart);
                 e = hipcub::DeviceRadixSort::SortPairs(nullptr, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
             }
             if (e == hipSuccess) e = hipMalloc(&w2, std::max<size_t>(w2b, 1));
@@ -1593,10 +1568,10 @@ static int build_tile_lists(bfd_sim *s)
             if (k0) hipFree(k0); if (k1) hipFree(k1); if (v1) hipFree(v1); if (w2) hipFree(w2);
         }
         // Compact solid state (bfd_dev::cssRow): Sxx, Syy, the shear stresses and the five memory variables Rxx, Ryy, Rxy, Rxz, Ryz of the listed cells in
-        // list order. Needs the row-contiguous list order (mode 2) and the two-kernel form. In a Z-slab the ghost planes of Sxz / Syz stay in the
+        // list order. Needs the row-contiguous list order and the two-kernel form. In a Z-slab the ghost planes of Sxz / Syz stay in the
         // full-volume arrays (the sparse kernel keeps full-volume copies of the planes a neighbour reads, the velocity kernel takes ghost planes from
         // there): the halo exchange is unchanged. BFD_COMPACT_SOLID=0 keeps the full-volume arrays.
-        bool compact = count > 0 && orderMode == 2 && !T.merged && s->d.N1 <= 4095 && bfd_css_supported();
+        bool compact = count > 0 && !T.merged && s->d.N1 <= 4095;
         if (const char *ev = getenv("BFD_COMPACT_SOLID")) compact = compact && atoi(ev) != 0;
         if (e == hipSuccess) {
             rc = dev_alloc(s, &s->tiles.shearCells, (size_t)std::max(count, 1), false);
@@ -1864,7 +1839,6 @@ static int choose_placement(bfd_sim *s)
     s->placementNote = "off";
     bool on = s->placementMode != 0;
     if (const char *ev = getenv("BFD_PLACEMENT")) on = atoi(ev) != 0;
-    if (const char *ev = getenv("BFD_PLACEMENT_TRIALS")) on = on && atoi(ev) != 0;
     // below ~32 M voxels the arrays a kernel streams (5 x 4 B per voxel and up) fit the 256 MB memory-side cache, where they lie
     // in DRAM stops mattering, and the probe (0.02 ms at 256^3) cannot tell the regions apart any more
     size_t minVoxels = (size_t)32 << 20;
@@ -2001,9 +1975,7 @@ static int choose_placement(bfd_sim *s)
             else { hipStreamSynchronize(s->stream); hipFree(c); }
         }
     }
-    int forcedWalk = 0;                                                        // BFD_PLACEMENT_FORCE_WALK=n (experiments): n more candidates are drawn, held and released, as an unlucky search does
-    if (const char *ev = getenv("BFD_PLACEMENT_FORCE_WALK")) forcedWalk = atoi(ev);
-    while ((need[0] > 0 || need[1] > 0 || forcedWalk-- > 0) && !gaveUp && probeTells) {            // draw candidates until both sides have enough
+    while ((need[0] > 0 || need[1] > 0) && !gaveUp && probeTells) {            // draw candidates until both sides have enough
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < 2 * bytes + totalB / 8 || heldBytes + bytes > heldCap) { gaveUp = true; break; }
         if (defaultRule) {
@@ -2705,15 +2677,12 @@ static hipError_t copy_out_large(int device, void *dst, const void *src, size_t 
     T = std::min(T, 16);
     hipError_t e = hipStreamSynchronize(after);
     if (e != hipSuccess) return e;
-    const bool traceCopy = getenv("BFD_TRACE_COPY") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
     std::vector<char *> pin(2 * (size_t)T, nullptr);
     bool ok = true;
     for (auto &q : pin) if (ok && !(q = pin_take(PIECE))) ok = false;
     std::vector<float *> dpiece(produce ? 2 * (size_t)T : 0, nullptr);
     for (auto &q : dpiece) if (ok && hipMalloc((void **)&q, PIECE) != hipSuccess) { q = nullptr; ok = false; (void)hipGetLastError(); }
     std::vector<int> failed((size_t)T, 0);
-    const auto tc1 = std::chrono::steady_clock::now();
     if (ok) {
         std::vector<std::thread> th;
         for (int t = 0; t < T; t++)
@@ -2743,11 +2712,8 @@ static hipError_t copy_out_large(int device, void *dst, const void *src, size_t 
         for (auto &x : th) x.join();
         for (int t = 0; t < T; t++) if (failed[t]) ok = false;
     }
-    const auto tc2 = std::chrono::steady_clock::now();
     for (auto &q : pin) pin_give(q, PIECE);
     for (auto &q : dpiece) if (q) hipFree(q);
-    if (traceCopy) fprintf(stderr, "copy_out_large: %.2f GB, %d threads: buffers %.3f s, copy %.3f s, release %.3f s\n", bytes * 1e-9, T, std::chrono::duration<double>(tc1 - tc0).count(),
-                           std::chrono::duration<double>(tc2 - tc1).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - tc2).count());
     if (ok) return hipSuccess;
     (void)hipGetLastError();
     if (produce) return hipErrorNotSupported;
@@ -2781,24 +2747,15 @@ int bfd_sensors_into(bfd_sim *s, float *out, int64_t rowElems)
         (void)hipGetLastError();      // declined (small block, BFD_D2H_THREADS < 2) or failed on the way: the whole block through a scratch copy
     }
     float *tmp = nullptr;
-    const bool trace = getenv("BFD_TRACE_SENSORS") != nullptr;
-    auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tt[5]; tt[0] = tnow();
     BFD_HIP(hipMalloc((void **)&tmp, n * sizeof(float)));
-    tt[1] = tnow();
     hipLaunchKernelGGL(transpose_sensors, dim3(grid_for((long)n)), dim3(256), 0, s->stream, s->sensOut, tmp, (long)s->nSensors, s->nTs, s->nSelS);
-    if (trace) hipStreamSynchronize(s->stream);
-    tt[2] = tnow();
     hipError_t e = hipSuccess;
     for (int q = 0; q < s->nSelS; q++) bfd_advise_result_buffer(out + (size_t)q * rowElems, row * sizeof(float));
     if ((size_t)rowElems == row) e = copy_out_large(s->cfg.device, out, tmp, n * sizeof(float), s->stream);
     else
         for (int q = 0; q < s->nSelS && e == hipSuccess; q++)
             e = copy_out_large(s->cfg.device, out + (size_t)q * rowElems, tmp + (size_t)q * row, row * sizeof(float), s->stream);
-    tt[3] = tnow();
     hipFree(tmp);
-    tt[4] = tnow();
-    if (trace) fprintf(stderr, "bfd_get_sensors: %.2f GB: hipMalloc %.3f s, transpose %.3f s, copy %.3f s, hipFree %.3f s\n", n * 4e-9, tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2], tt[4] - tt[3]);
     if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_get_sensors: ") + hipGetErrorString(e));
     return 0;
 }

@@ -13,29 +13,16 @@
 // launch (round 6: bhte_stepNg; stretches it cannot take go to the two-step kernel bhte_step2g and the one-step kernel) and moves those bytes
 // once for all of them. x-fastest layout.
 #include "bfd_internal.h"
+#include "bfd_device.h"
 #include <math.h>
 #include <vector>
 
 // steps per pass of the default path (bhte_stepNg): four (bhte_run_core says how that was chosen)
-#ifndef BFD_BHTE_STEPS_HEATING
-#define BFD_BHTE_STEPS_HEATING 4
-#endif
-#ifndef BFD_BHTE_STEPS_COOLING
-#define BFD_BHTE_STEPS_COOLING 4
-#endif
+constexpr int BFD_BHTE_STEPS_HEATING = 4, BFD_BHTE_STEPS_COOLING = 4;
 
 namespace {
 
-// (wave-uniform plane base) + (32-bit byte offset in a VGPR): see bfd_kernels_v2.hip, uni() / F4()
-template <typename T>
-__device__ __forceinline__ T *uni(T *p)
-{
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (T *)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ float &F4(float *base, unsigned byteOfs) { return *(float *)((char *)uni(base) + byteOfs); }
-__device__ __forceinline__ const float &F4(const float *base, unsigned byteOfs) { return *(const float *)((const char *)uni(base) + byteOfs); }
+// uni() / F4(): (wave-uniform plane base) + (32-bit byte offset in a VGPR), from bfd_device.h
 
 // One cell, one step, in the oracle's operation order (oracle/bhte_oracle.py); the roundings are pinned so that the one-step
 // kernel, the two-step kernel and the monitors of an intermediate step give the same bits.
@@ -174,14 +161,22 @@ __device__ __forceinline__ void bhte_step2_body(int b, B2_ARGS)
     }
 }
 
-template <bool REV>
-__global__ __launch_bounds__(B2_T) void bhte_step2(B2_ARGS)
+// workgroups go to the 8 XCDs round-robin: give each XCD a contiguous piece of the tile order (xcdOrder: always 1, the launchers pass it;
+// 372-378 -> 386-389 Gvoxel-steps/s at 384^3, profiles/r3/bhte_two_steps_per_launch.txt)
+__device__ __forceinline__ int xcd_block(int nBlocks, int xcdOrder)
 {
     int b = blockIdx.x;
-    if (xcdOrder) {                               // workgroups go to the 8 XCDs round-robin: give each XCD a contiguous piece of the tile order
+    if (xcdOrder) {
         const int per = nBlocks >> 3, rem = nBlocks & 7, x = b & 7, slot = b >> 3;
         b = x * per + (x < rem ? x : rem) + slot;
     }
+    return b;
+}
+
+template <bool REV>
+__global__ __launch_bounds__(B2_T) void bhte_step2(B2_ARGS)
+{
+    const int b = xcd_block(nBlocks, xcdOrder);
     bhte_step2_body<REV>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
 }
 
@@ -221,10 +216,6 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
     __shared__ float A[2][G2_CELLS + 2 * G2_W], B[2][G2_CELLS + 2 * G2_W];
     __shared__ float2 sC[256];
     for (int m = threadIdx.x; m < nMat; m += G2_T) sC[m] = make_float2(cd[m], cp[m]);
-#ifdef G2_EXP_LDS_PAD      // experiment: fewer workgroups per CU
-    __shared__ float sPad[G2_EXP_LDS_PAD];
-    if (nMat < 0) { sPad[threadIdx.x] = 1.f; sC[0].x = sPad[(threadIdx.x + 1) % 512]; }
-#endif
     // 476 threads own the 4 x 476 region cells; the last 36 repeat the work of threads 0..35 without storing (same LDS values)
     const bool mirror = threadIdx.x >= G2_ACT;
     const int tid = mirror ? threadIdx.x - G2_ACT : threadIdx.x;
@@ -297,9 +288,7 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
             const int e = e0 + n * G2_ACT;
             const float2 cc = sC[mi[n][c]];
             float T1 = bhte_update<REV>(t0[n][c], Ap[e - 1], Ap[e + 1], Ap[e - G2_W], Ap[e + G2_W], t0[n][m1], t0[n][p1], cc.x, cc.y, Tcore, heatA, qv[n][c]);
-#ifndef G2_BRANCHY
             asm volatile("" : "+v"(T1));            // computed by every lane: no branch around the update (the select below masks it)
-#endif
             t1[n][c] = (inner && fC1[n]) ? T1 : t0[n][c];
             Bp[e] = t1[n][c];
         }
@@ -319,9 +308,7 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
                 const float2 cc = sC[mi[n][m1]];
                 const float qq = QM == 1 ? qv[n][m1] : q2[n];
                 float U = bhte_update<REV>(t1[n][m1], Bq[e - 1], Bq[e + 1], Bq[e - G2_W], Bq[e + G2_W], t1[n][p1], t1[n][c], cc.x, cc.y, Tcore, heatB, qq);
-#ifndef G2_BRANCHY
                 asm volatile("" : "+v"(U));
-#endif
                 const float T2 = (innerOut && !fFace[n]) ? U : t1[n][m1];
                 if (fOut[n]) {
                     gs4(Tout + kO, g[n], T2);
@@ -336,17 +323,11 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
     if (p + 1 <= z1) plane(Ph3<1>(), p + 1);
 }
 
-#ifndef G2_WAVES
-#define G2_WAVES 6           // waves per SIMD the register budget is held to (6: 80 VGPRs, three workgroups per CU)
-#endif
+constexpr int G2_WAVES = 6;  // waves per SIMD the register budget is held to (6: 80 VGPRs, three workgroups per CU)
 template <bool REV, int QM>
 __global__ __launch_bounds__(G2_T, G2_WAVES) void bhte_step2g(B2_ARGS)
 {
-    int b = blockIdx.x;
-    if (xcdOrder) {
-        const int per = nBlocks >> 3, rem = nBlocks & 7, x = b & 7, slot = b >> 3;
-        b = x * per + (x < rem ? x : rem) + slot;
-    }
+    const int b = xcd_block(nBlocks, xcdOrder);
     bhte_step2g_body<REV, QM>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
 }
 // ---- round 6: S = 3 or 4 steps per pass (bhte_stepNg) ----
@@ -492,17 +473,11 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
     if (p + 1 <= pend) plane(Ph3<1>(), p + 1);
 }
 
-#ifndef GN_WAVES
-#define GN_WAVES 4           // 128 registers: two workgroups of 8 waves per CU, or one of 16
-#endif
+constexpr int GN_WAVES = 4;  // 128 registers: two workgroups of 8 waves per CU, or one of 16
 template <bool REV, int QM, int S>
 __global__ __launch_bounds__((GN<S, GNCells<QM, S>::v>::T), GN_WAVES) void bhte_stepNg(B2_ARGS)
 {
-    int b = blockIdx.x;
-    if (xcdOrder) {
-        const int per = nBlocks >> 3, rem = nBlocks & 7, x = b & 7, slot = b >> 3;
-        b = x * per + (x < rem ? x : rem) + slot;
-    }
+    const int b = xcd_block(nBlocks, xcdOrder);
     bhte_stepNg_body<REV, QM, S>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
 }
 
@@ -771,8 +746,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
                 if (best < 0 || cost <= best) { best = cost; zrun = z; }
             }
         }
-        ev = getenv("BFD_BHTE_XCD_ORDER");
-        const int xcdOrder = (ev && atoi(ev) == 0) ? 0 : 1;
+        const int xcdOrder = 1;
         const int runsZ = (N3 + zrun - 1) / zrun;
         const long nBlocks2 = (long)tilesX * tilesY * runsZ;
         auto Q = [&](int f) { return f < 0 ? (const float *)nullptr : dq + (size_t)f * n; };

@@ -33,13 +33,9 @@
 // classification in sub-tiles of BFD_SUBZ planes
 #define BFD_TILE_X 64
 #define BFD_TILE_Y 8
-#ifndef BFD_SUBZ
 #define BFD_SUBZ 8
-#endif
 // output rows of a workgroup of the fused time step (bfd_kernels_fused.hip): three tiles of the classification grid
-#ifndef BFD_FUSED_ROWS
 #define BFD_FUSED_ROWS 24
-#endif
 // multi-material runs of the fused time step keep AP, BP, 1/rho of every material in LDS: media with more materials fuse only their one-material runs
 #define BFD_FUSED_MAX_MATERIALS 1024
 
@@ -138,10 +134,7 @@ struct bfd_tiles { bfd_sim *ktimer; int nMat; bool merged /* solid runs: normal 
                    /* cost-balanced block -> run maps (round 4): block b of a launch runs on XCD slot b & 7 and takes run seg[slot] + (b >> 3) of
                       the launched range if that is below seg[slot + 1]; the launch has 8 x maxcnt blocks. One map of 10 ints (seg[0..8], maxcnt)
                       per launched range and kernel class, on the device in xmap, on the host in xmapH. */
-                   int *xmap; int xmapH[BFD_XMAP_COUNT][10];
-                   /* experiment (BFD_CONCURRENT=1): the solid-run kernels of a half-step on side streams beside the fluid kernel (they write
-                      disjoint cells); fork / join through events. Null = everything on the engine's stream. */
-                   hipStream_t sideStream[2]; hipEvent_t sideFork, sideJoin[2]; };
+                   int *xmap; int xmapH[BFD_XMAP_COUNT][10]; };
 
 struct bfd_sim {
     bfd_config cfg;
@@ -234,17 +227,16 @@ void bfd_launch_fused(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, 
 int bfd_fused_rows(void);
 int bfd_fused_max_materials(void);
 int bfd_tile_subz(void);
-bool bfd_css_supported(void);     // false in the experiment builds whose solid-run kernels have no compact form
 void bfd_launch_classify(const bfd_dev &d, hipStream_t s, int *flagsDev, int *tileMatDev);
 void bfd_launch_mark_source_subtiles(const bfd_dev &d, hipStream_t s, const uint32_t *lin, long n);
 // flags the cells of the sparse shear list: solid, non-reflector centre; mixedOnly: only those with BFD_CLS_MIXED (merged solid stress kernel)
 void bfd_launch_mark_solid(const bfd_dev &d, hipStream_t s, unsigned char *flag, long n, bool mixedOnly);
-void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart, int mode);
+void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart);
 void bfd_launch_shear_coefficients(const bfd_dev &d, hipStream_t s, const unsigned *cells, float *coef, unsigned *codes, float *tab, int nMat, long n);
 // copies the list-ordered shear memory variables into the full-volume arrays Rxy, Rxz, Ryz (outputs only)
 void bfd_launch_scatter_shear_memory(const bfd_dev &d, hipStream_t s, const bfd_tiles *t);
 void bfd_launch_gather_shear_memory(const bfd_dev &d, hipStream_t s, const bfd_tiles *t);
-// compact solid state: the row table of a list in order mode 2 (lowPlanes / hiStart as for bfd_launch_shear_order_keys)
+// compact solid state: the row table of the ordered list (lowPlanes / hiStart as for bfd_launch_shear_order_keys)
 void bfd_launch_css_row_table(const bfd_dev &d, hipStream_t s, const unsigned *cells, long n, unsigned *rowTable, int stride, int lowPlanes, int hiStart);
 // dstFull (pointer to local plane 0 of a full-volume buffer) [cell] = compact array a [entry], a = 0..9 in the order Sxx Syy Sxy Sxz Syz Rxx Ryy Rxy Rxz Ryz;
 // the reverse into dstCompact from a full-volume source. cells / n: the list the entries belong to.

@@ -35,19 +35,14 @@ constexpr int FR_W = FT_X + 3, FR_H = FT_Y + 3;         // region of the new str
 constexpr int FP = FR_W + 3;                            // LDS pitch 70: column t <-> x = i0-3+t (Vx needs x-2 .. x+1 of every region cell)
 constexpr int FS_N = FR_H * FP;                         // Vx, new-stress and 1/rho tiles: region rows
 constexpr int FVY_N = (FR_H + 3) * FP;                  // Vy tile: rows u <-> y = j0-3+u
-#ifndef FUSED_CPT
-#define FUSED_CPT 4
-#endif
-constexpr int NT = 512, CPT = FUSED_CPT;       // region cells per thread
+constexpr int NT = 512, CPT = 4;               // region cells per thread
 constexpr int RSTEP = (FR_H + CPT - 1) / CPT;           // 7: thread (r, col) owns the region cells (r + 7 c, col), c = 0 .. 3
 constexpr int NCELLT = RSTEP * FR_W;                    // 469 threads hold cells
 static_assert(NCELLT <= NT && RSTEP * CPT >= FR_H, "four region cells per thread");
 constexpr int NTX = 3 * FR_H;                           // extra Vx columns t = 0, 1, 69: 81 tasks (waves 0-1)
 constexpr int NTY = 3 * FR_W;                           // extra Vy rows u = 0, 1, 29: 201 tasks (waves 2-5)
 static_assert(NTX <= 128 && NTY <= 256, "halo tasks fit their waves");
-#ifndef FUSED_WAVES_PER_SIMD
-#define FUSED_WAVES_PER_SIMD 4
-#endif
+constexpr int FUSED_WAVES_PER_SIMD = 4;
 constexpr int FUSED_TAB_MAX = BFD_FUSED_MAX_MATERIALS;  // materials whose AP, BP, 1/rho fit the LDS table of the multi-material flavour
 
 // Accesses of this kernel are GLOBAL instructions (wave-uniform base in SGPRs + 32-bit byte offset), not the FLAT ones of
@@ -67,12 +62,8 @@ __device__ __forceinline__ float GLNT(const float *base, unsigned ofs) { return 
 __device__ __forceinline__ unsigned GL2(const uint16_t *base, unsigned ofs) { return *(BFD_GLOBAL const uint16_t *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
 __device__ __forceinline__ void GS4(float *base, unsigned ofs, float v) { *(BFD_GLOBAL float *)((BFD_GLOBAL char *)guni(base) + pin(ofs)) = v; }
 // Stores are plain in this kernel: non-temporal ones wrote 1.98 GB per launch where 1.78 are needed and cost 7 % (C1 512^3, same
-// box: 0.953 -> 0.889 ms; profiles/r4/fused_experiments.txt). -DFUSED_EXP_NT_STORES builds the non-temporal ones.
-#ifndef FUSED_EXP_NT_STORES
+// box: 0.953 -> 0.889 ms; profiles/r4/fused_experiments.txt).
 __device__ __forceinline__ void GSNT(float *base, unsigned ofs, float v) { GS4(base, ofs, v); }
-#else
-__device__ __forceinline__ void GSNT(float *base, unsigned ofs, float v) { __builtin_nontemporal_store(v, (BFD_GLOBAL float *)((BFD_GLOBAL char *)guni(base) + pin(ofs))); }
-#endif
 
 template <int K> struct Ph { static constexpr int v = K; };
 
@@ -97,11 +88,7 @@ __device__ __forceinline__ void fused_body(const bfd_dev &d, int bx, int by, int
     const bool active = tid < NCELLT;
     const int tt = active ? tid : 0, r = tt / FR_W, col = tt - r * FR_W;
     const int l0 = r * FP + col + 2;
-#ifdef FUSED_EXP_NORING     // experiment (wrong results): every cell reads inside the own 64 x 24 outputs -- what the ring lines cost
-    const unsigned g0 = (unsigned)((j0 + min(max(r - 1, 0), 5)) * N1 + (i0 + min(max(col - 1, 0), FT_X - 1))) * 4u;
-#else
     const unsigned g0 = (unsigned)((j0 - 1 + r) * N1 + (i0 - 1 + col)) * 4u;
-#endif
     const long cstep = (long)RSTEP * N1;
     const bool colOut = active && col >= 1 && col <= FT_X;
     bool has[CPT], out[CPT];
@@ -123,9 +110,6 @@ __device__ __forceinline__ void fused_body(const bfd_dev &d, int bx, int by, int
         const int u = hasT ? u0 : 0, rr = u / FR_W, cc = u - rr * FR_W, ur = rr < 2 ? rr : FR_H + 2;
         lT = ur * FP + cc + 2; gT = (unsigned)((j0 - 3 + ur) * N1 + (i0 - 1 + cc)) * 4u;
     } else gT = g0;
-#ifdef FUSED_EXP_NORING
-    gT = g0;
-#endif
     const float *aT = wv < 2 ? d.Vx : d.Vy;
     float *sT = (wv < 2 ? sVx : sVy) + lT;
 
@@ -299,10 +283,6 @@ __global__ __launch_bounds__(NT, FUSED_WAVES_PER_SIMD) void fused_fluid(bfd_dev 
     __shared__ float sVx[FS_N], sVy[FVY_N], sS[FS_N], sR[3 * FS_N], sTab[3 * FUSED_TAB_MAX];
     const int4 run = runs[remap_block(blockIdx.x, nblocks)];
     const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16, tm = run.w;
-#ifdef FUSED_EXP_LDS_PAD    // experiment: one workgroup per CU
-    __shared__ float sPad[FUSED_EXP_LDS_PAD];
-    if (nMat < 0) sPad[threadIdx.x] = 1.f, sTab[0] = sPad[(threadIdx.x + 1) % 512];
-#endif
     if (!(run.z & 4)) {              // ids per cell: AP, BP, 1/rho of every material in LDS (runs of media with more materials are not fused)
         for (int m = threadIdx.x; m < nMat; m += NT) { sTab[m] = d.AP[m]; sTab[FUSED_TAB_MAX + m] = d.BP[m]; sTab[2 * FUSED_TAB_MAX + m] = d.invRho[m]; }
         __syncthreads();

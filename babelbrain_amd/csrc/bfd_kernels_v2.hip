@@ -18,6 +18,7 @@
 #include "bfd_internal.h"
 #include "bfd_device.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -28,23 +29,12 @@ constexpr int LH = TY + 4;          // LDS rows
 constexpr int NTHREADS = TX * TY;   // 512
 constexpr int YT = 4 * TX;          // y-halo tasks per array (4 rows x 64)
 constexpr int XT = 4 * TY;          // x-halo tasks per array (4 cols x TY)
-#ifndef BFD_ZCHUNK
-#define BFD_ZCHUNK 32
-#endif
-constexpr int ZCHUNK = BFD_ZCHUNK;  // longest z-run one workgroup marches
-constexpr int SUBZ = BFD_SUBZ;             // z granularity of the fluid/solid classification (runs are merged sub-tiles)
-#ifndef STRESS_WAVES_PER_SIMD
-#define STRESS_WAVES_PER_SIMD 4     // 2 workgroups of 8 waves per CU (<= 128 VGPRs); 6 or 8 spill and run 1.4-2.4x slower (measured)
-#endif
-#ifndef FLUID_WAVES_PER_SIMD
-#define FLUID_WAVES_PER_SIMD 8      // 57 / 64 VGPRs since the plane bases live in SGPRs (uni()); round 1, with 64-bit per-lane addresses: 6 -> 61 Gvoxel-steps/s, 8 (spills) -> 47
-#endif
-#ifndef VELOCITY_WAVES_PER_SIMD
-#define VELOCITY_WAVES_PER_SIMD 4
-#endif
-#ifndef VELOCITY_FLUID_WAVES_PER_SIMD
-#define VELOCITY_FLUID_WAVES_PER_SIMD FLUID_WAVES_PER_SIMD     // of velocity_fluid alone (64 VGPRs + one 8-byte spill at 8 waves; at 7 no spill): A/B in profiles/r4/
-#endif
+constexpr int ZCHUNK = 32;        // longest z-run one workgroup marches
+constexpr int SUBZ = BFD_SUBZ;     // z granularity of the fluid/solid classification (runs are merged sub-tiles)
+constexpr int STRESS_WAVES_PER_SIMD = 4;     // 2 workgroups of 8 waves per CU (<= 128 VGPRs); 6 or 8 spill and run 1.4-2.4x slower (measured)
+constexpr int FLUID_WAVES_PER_SIMD = 8;      // 57 / 64 VGPRs since the plane bases live in SGPRs (uni()); round 1, with 64-bit per-lane addresses: 6 -> 61 Gvoxel-steps/s, 8 (spills) -> 47
+constexpr int VELOCITY_WAVES_PER_SIMD = 4;
+constexpr int VELOCITY_FLUID_WAVES_PER_SIMD = FLUID_WAVES_PER_SIMD;     // of velocity_fluid alone (64 VGPRs + one 8-byte spill at 8 waves; at 7 no spill): A/B in profiles/r4/
 
 struct HaloTask {
     int lofs;       // offset inside one LDS tile (floats), -1 = no task
@@ -980,12 +970,9 @@ __device__ __forceinline__ void stress_solid_body(const bfd_dev &d, const int4 &
     }
 }
 
-#ifndef SOLID_STRESS_WAVES_PER_SIMD
-#define SOLID_STRESS_WAVES_PER_SIMD 4
-#endif
-// (-DBFD_STRESS_SOLID_GLOBAL builds the GLOBAL / branch-free-prefetch body below instead: measured 1 % slower, 0.308-0.311 against
-// 0.305 ms at the shear medium 512^3 -- this kernel is at the rate of the bytes it moves; profiles/r4/experiment_solid_kernels_prefetch.txt)
-#ifndef BFD_STRESS_SOLID_GLOBAL
+constexpr int SOLID_STRESS_WAVES_PER_SIMD = 4;
+// (a GLOBAL / branch-free-prefetch body like velocity_solid_body_g was built and measured 1 % slower, 0.308-0.311 against 0.305 ms at the shear medium
+// 512^3 -- this kernel is at the rate of the bytes it moves; removed; profiles/r4/experiment_solid_kernels_prefetch.txt)
 __global__ __launch_bounds__(NTHREADS, SOLID_STRESS_WAVES_PER_SIMD) void stress_solid(bfd_dev d, int tilesX, int nblocks, const int *__restrict__ xmap, const int4 *__restrict__ runs)
 {
     __shared__ float sV[2][2][LH * LW];
@@ -995,7 +982,6 @@ __global__ __launch_bounds__(NTHREADS, SOLID_STRESS_WAVES_PER_SIMD) void stress_
     if (run.z & 8) stress_solid_body<true>(d, run, tilesX, sV);
     else stress_solid_body<false>(d, run, tilesX, sV);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // SOLID runs, normal AND shear stresses in one pass (BFD_SOLID_MERGED=1): stress_solid_body plus the shear update of the
@@ -1199,9 +1185,7 @@ __device__ __forceinline__ void stress_solid_merged_body(const bfd_dev &d, const
     }
 }
 
-#ifndef SOLID_MERGED_WAVES_PER_SIMD
-#define SOLID_MERGED_WAVES_PER_SIMD 4
-#endif
+constexpr int SOLID_MERGED_WAVES_PER_SIMD = 4;
 __global__ __launch_bounds__(NTHREADS, SOLID_MERGED_WAVES_PER_SIMD) void stress_solid_merged(bfd_dev d, int tilesX, int nblocks, const int *__restrict__ xmap, const int4 *__restrict__ runs,
                                                                                              const float *__restrict__ shearTab)
 {
@@ -1211,213 +1195,6 @@ __global__ __launch_bounds__(NTHREADS, SOLID_MERGED_WAVES_PER_SIMD) void stress_
     const int4 run = runs[ri];
     if (run.z & 8) stress_solid_merged_body<true>(d, run, tilesX, shearTab, sV);
     else stress_solid_merged_body<false>(d, run, tilesX, shearTab, sV);
-}
-
-// one halo value of the solid velocity kernel: SUBST (Sxx / Syy halos): Szz where the halo cell is fluid; otherwise a
-// shear array, loaded only where its edge bit is set. base / alt are wave-uniform (SGPR) plane bases.
-__device__ __forceinline__ float halo_value(const float *__restrict__ base, const float *__restrict__ alt, bool subst, unsigned bit,
-                                            unsigned hc, unsigned off)
-{
-    if (subst) return (hc & BFD_CLS_FLUID) ? F4(alt, off * 4u) : F4(base, off * 4u);
-    return (hc & bit) ? F4(base, off * 4u) : 0.0f;
-}
-
-// LDS set: 0 Sxx (x halo), 1 Syy (y halo), 2 Sxy (x and y halo), 3 Sxz (x halo), 4 Syz (y halo)
-// PML: the run touches an absorbing-layer zone (otherwise no CPML code, pointers or registers)
-template <bool ACC, bool PML>
-__device__ __forceinline__ void velocity_solid_body(const bfd_dev &d, const int4 &run, int tilesX, float (*sS)[5][LH * LW],
-                                                    float *__restrict__ accP, float *__restrict__ pkP)
-{
-    const int N1 = d.N1, N2 = d.N2;
-    const int bx = run.x % tilesX, by = run.x / tilesX;
-    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TX + tx;
-    const int wv = __builtin_amdgcn_readfirstlane(ty);      // wave index = tile row (uniform)
-    const int i0 = bx * TX, j0 = by * TY;
-    const int i = i0 + tx, j = j0 + ty;
-    const bool valid = (i < N1) && (j < N2);
-    const long pl = d.plane;
-    const int kbeg = run.y & 0xFFFF, kend = run.y >> 16;
-    const int P = d.P;
-    const int own = (ty + 2) * LW + tx + 2;
-    const unsigned cij = valid ? (unsigned)(j * N1 + i) : 0u;
-    // ids of the cells (i+1, j) and (i, j+1), clamped at the domain edge: byte offsets derived from cij when needed (the two
-    // comparisons live in scalar masks, not in registers)
-    const bool hasX = valid && i + 1 < N1, hasY = valid && j + 1 < N2;
-    const unsigned rowBytes = (unsigned)N1 * 2u;
-    const bool accA = ACC && accP != nullptr, accK = ACC && pkP != nullptr;
-
-    // halo tasks, the array of a task is uniform per wave (its plane base stays in SGPRs):
-    //   A: waves 0-3 the 4 halo rows of Syy, waves 4-7 those of Sxy
-    //   B: waves 0-3 the 4 halo rows of Syz; lanes 0..31 of wave 4 / 5 / 6 the halo columns of Sxx / Sxy / Sxz
-    HaloTask ta, tb;
-    const int arrA = wv < 4 ? 1 : 2;
-    ytask(tid & 255, arrA, i0, j0, N1, N2, ta);
-    const int arrB = wv < 4 ? 4 : (wv == 4 ? 0 : (wv == 5 ? 2 : 3));
-    if (wv < 4) ytask(tid, 4, i0, j0, N1, N2, tb);
-    else if (wv < 7 && tx < XT) xtask(tx, arrB, i0, j0, N1, N2, tb);
-    else { tb.lofs = -1; tb.ok = false; tb.arr = arrB; tb.gofs = 0; }
-    const float *baseA = arrA == 1 ? d.Syy : d.Sxy;
-    const float *baseB = arrB == 4 ? d.Syz : (arrB == 0 ? d.Sxx : (arrB == 2 ? d.Sxy : d.Sxz));
-    const bool substA = arrA == 1, substB = arrB == 0;
-    const unsigned bitA = BFD_CLS_EXY, bitB = arrB == 4 ? BFD_CLS_EYZ : (arrB == 2 ? BFD_CLS_EXY : BFD_CLS_EXZ);
-    const unsigned offA = ta.ok ? (unsigned)ta.gofs : 0u, offB = tb.ok ? (unsigned)tb.gofs : 0u;
-    float *la = &sS[0][ta.arr][ta.lofs];
-    float *lb = &sS[0][tb.arr][tb.lofs < 0 ? 0 : tb.lofs];
-    const bool hasB = tb.lofs >= 0;
-    const int bufStride = 5 * LH * LW;
-
-    const bool zi = PML && valid && (i < P || i >= N1 - P);
-    const bool zj = PML && valid && (j < P || j >= N2 - P);
-    const bool inner = valid && i >= d.ND && i < N1 - d.ND && j >= d.ND && j < N2 - d.ND;
-
-    // z queues: Szz k-1..k+2 ; Sxz, Syz k-2..k+1 ; in-plane arrays one plane ahead. Class bytes of the own column:
-    // cB = plane kl+1, cC = plane kl+2 (they steer the loads of the coming iterations)
-    float zzm1 = 0, zz0 = 0, zzp1 = 0, zzp2 = 0, xzm2 = 0, xzm1 = 0, xz0 = 0, xzp1 = 0, yzm2 = 0, yzm1 = 0, yz0 = 0, yzp1 = 0;
-    unsigned cB = BFD_CLS_FLUID, cC = BFD_CLS_FLUID;
-    {
-    float sxx = 0, syy = 0, sxy = 0;
-    if (valid) {
-        const float *bzz = d.Szz + kbeg * pl, *bxz = d.Sxz + kbeg * pl, *byz = d.Syz + kbeg * pl;
-        const uint8_t *bc = d.cls + kbeg * pl;
-        const unsigned cm2 = U1((bc - 2 * pl), cij), cm1 = U1((bc - pl), cij), c0 = U1(bc, cij);
-        cB = U1((bc + pl), cij); cC = U1((bc + 2 * pl), cij);
-        zzm1 = F4((bzz - pl), cij * 4u); zz0 = F4(bzz, cij * 4u); zzp1 = F4((bzz + pl), cij * 4u); zzp2 = F4((bzz + 2 * pl), cij * 4u);
-        if (cm2 & BFD_CLS_EXZ) xzm2 = F4((bxz - 2 * pl), cij * 4u);
-        if (cm1 & BFD_CLS_EXZ) xzm1 = F4((bxz - pl), cij * 4u);
-        if (c0 & BFD_CLS_EXZ) xz0 = F4(bxz, cij * 4u);
-        if (cB & BFD_CLS_EXZ) xzp1 = F4((bxz + pl), cij * 4u);
-        if (cm2 & BFD_CLS_EYZ) yzm2 = F4((byz - 2 * pl), cij * 4u);
-        if (cm1 & BFD_CLS_EYZ) yzm1 = F4((byz - pl), cij * 4u);
-        if (c0 & BFD_CLS_EYZ) yz0 = F4(byz, cij * 4u);
-        if (cB & BFD_CLS_EYZ) yzp1 = F4((byz + pl), cij * 4u);
-        if (c0 & BFD_CLS_FLUID) { sxx = zz0; syy = zz0; }
-        else { sxx = F4((d.Sxx + kbeg * pl), cij * 4u); syy = F4((d.Syy + kbeg * pl), cij * 4u); }
-        if (c0 & BFD_CLS_EXY) sxy = F4((d.Sxy + kbeg * pl), cij * 4u);
-    }
-    // the values of a plane are staged in LDS at the end of the iteration before it (here: plane kbeg into buffer kbeg & 1)
-    const int bo0 = (kbeg & 1) * bufStride;
-    sS[0][0][bo0 + own] = sxx; sS[0][1][bo0 + own] = syy; sS[0][2][bo0 + own] = sxy; sS[0][3][bo0 + own] = xz0; sS[0][4][bo0 + own] = yz0;
-    }
-    // V and the accumulators are loaded in the iteration that uses them (their latency hides behind the barrier and the
-    // other waves; prefetching them one plane ahead costs 5 registers this kernel does not have)
-    float r0 = 0;
-    unsigned mraw = 0, mraw1 = 0, mx = 0, my = 0;
-    if (valid) {
-        const uint16_t *bM = d.mat + kbeg * pl;
-        mraw = U2(bM, cij * 2u); mraw1 = U2((bM + pl), cij * 2u); mx = U2(bM, cij * 2u + (hasX ? 2u : 0u)); my = U2(bM, cij * 2u + (hasY ? rowBytes : 0u));
-        r0 = d.invRho[mraw & BFD_MAT_MASK];
-    }
-    // halo values of plane kbeg and the class bytes of the halo cells one plane ahead
-    unsigned hcA = 0, hcB = 0;
-    {
-        float ha = 0.f, hb = 0.f;
-        if (ta.ok) { ha = halo_value(baseA + kbeg * pl, d.Szz + kbeg * pl, substA, bitA, U1((d.cls + kbeg * pl), offA), offA); hcA = U1((d.cls + kbeg * pl + pl), offA); }
-        if (tb.ok) { hb = halo_value(baseB + kbeg * pl, d.Szz + kbeg * pl, substB, bitB, U1((d.cls + kbeg * pl), offB), offB); hcB = U1((d.cls + kbeg * pl + pl), offB); }
-        la[(kbeg & 1) * bufStride] = ha;
-        if (hasB) lb[(kbeg & 1) * bufStride] = hb;
-    }
-
-    for (int kl = kbeg; kl < kend; kl++) {
-        const int b = kl & 1;
-        // opaque to loop strength reduction: otherwise every array gets a 64-bit per-lane pointer that is bumped each plane
-        // (a VGPR pair per array); this way the plane bases are recomputed on the scalar unit and stay in SGPRs
-        const long ko = (long)__builtin_amdgcn_readfirstlane(kl) * pl;
-        const int k = d.k0 + kl;
-        const int bn = (b ^ 1) * bufStride;     // buffer of plane kl+1 (free: every thread is past the barrier of iteration kl-1's reads)
-        float nzz = 0, nxz = 0, nyz = 0, nxx = 0, nyy = 0, nxy = 0, nha = 0, nhb = 0;
-        unsigned nm2 = 0, nmx = 0, nmy = 0, nc3 = BFD_CLS_FLUID, nhcA = 0, nhcB = 0;
-        auto prefetch_next = [&]() {
-        if (valid) nm2 = U2((d.mat + ko + 2 * pl), cij * 2u);              // ghost planes make kl+2 addressable
-        if (valid && kl + 2 < kend) nc3 = U1((d.cls + ko + 3 * pl), cij);       // steers the Sxz / Syz loads of iteration kl+1 (plane kl+3 <= nk+1)
-            if (kl + 1 < kend) {
-                if (valid) {
-                    nzz = F4((d.Szz + ko + 3 * pl), cij * 4u);
-                    if (cC & BFD_CLS_EXZ) nxz = F4((d.Sxz + ko + 2 * pl), cij * 4u);
-                    if (cC & BFD_CLS_EYZ) nyz = F4((d.Syz + ko + 2 * pl), cij * 4u);
-                    if (cB & BFD_CLS_FLUID) { nxx = zzp1; nyy = zzp1; }
-                    else { nxx = F4((d.Sxx + ko + pl), cij * 4u); nyy = F4((d.Syy + ko + pl), cij * 4u); }
-                    if (cB & BFD_CLS_EXY) nxy = F4((d.Sxy + ko + pl), cij * 4u);
-                    nmx = U2((d.mat + ko + pl), cij * 2u + (hasX ? 2u : 0u)); nmy = U2((d.mat + ko + pl), cij * 2u + (hasY ? rowBytes : 0u));
-                }
-                if (ta.ok) { nha = halo_value(baseA + ko + pl, d.Szz + ko + pl, substA, bitA, hcA, offA); nhcA = U1((d.cls + ko + 2 * pl), offA); }
-                if (tb.ok) { nhb = halo_value(baseB + ko + pl, d.Szz + ko + pl, substB, bitB, hcB, offB); nhcB = U1((d.cls + ko + 2 * pl), offB); }
-            }
-        };
-        float r1 = 0, rx = 0, ry = 0, vx = 0, vy = 0, vz = 0, av = 0, pv = 0;
-        if (valid) {
-            r1 = d.invRho[mraw1 & BFD_MAT_MASK];       // plane kl+1, becomes r0 of the next iteration
-            rx = d.invRho[mx & BFD_MAT_MASK];
-            ry = d.invRho[my & BFD_MAT_MASK];
-            vx = LD4((d.Vx + ko), cij * 4u); vy = LD4((d.Vy + ko), cij * 4u); vz = LD4((d.Vz + ko), cij * 4u);
-            if (accA) av = LD4((accP + ko), cij * 4u);
-            if (accK) pv = F4((pkP + ko), cij * 4u);
-        }
-        __syncthreads();
-
-        float *wVx = d.VxW + ko, *wVy = d.VyW + ko, *wVz = d.VzW + ko;
-        prefetch_next();        // after the barrier (issuing these loads before it was measured slower: 2.37 -> 2.52 ms per step at C2-medium 512^3)
-        if (valid) {
-            const float sxx = sS[b][0][own], syy = sS[b][1][own], sxy = sS[b][2][own];
-            if (ACC) {
-                if (inner && k >= d.ND && k < d.N3 - d.ND) {
-                    const float s = (sxx + syy) + zz0;
-                    const float p = -s * (1.0f / 3.0f);
-                    if (accA) F4((accP + ko), cij * 4u) = av + p * p;
-                    if (accK) { const float ap = fabsf(p); if (ap > pv) F4((pkP + ko), cij * 4u) = ap; }
-                }
-            }
-            if (mraw & BFD_REFLECTOR_BIT) {
-                F4(wVx, cij * 4u) = 0.f; F4(wVy, cij * 4u) = 0.f; F4(wVz, cij * 4u) = 0.f;
-            } else {
-                const float *pxx = &sS[b][0][own], *pyy = &sS[b][1][own], *pxy = &sS[b][2][own];
-                const float *pxz = &sS[b][3][own], *pyz = &sS[b][4][own];
-                float dxSxx = dplus4(pxx[-1], sxx, pxx[1], pxx[2]);
-                float dySxy = dminus4(pxy[-2 * LW], pxy[-LW], sxy, pxy[LW]);
-                float dzSxz = dminus4(xzm2, xzm1, xz0, xzp1);
-                float dxSxy = dminus4(pxy[-2], pxy[-1], sxy, pxy[1]);
-                float dySyy = dplus4(pyy[-LW], syy, pyy[LW], pyy[2 * LW]);
-                float dzSyz = dminus4(yzm2, yzm1, yz0, yzp1);
-                float dxSxz = dminus4(pxz[-2], pxz[-1], xz0, pxz[1]);
-                float dySyz = dminus4(pyz[-2 * LW], pyz[-LW], yz0, pyz[LW]);
-                float dzSzz = dplus4(zzm1, zz0, zzp1, zzp2);
-                if (zi) {
-                    const int xi = i < P ? i : i - (N1 - 2 * P);
-                    const unsigned q = (unsigned)((kl * N2 + j) * (2 * P) + xi);
-                    dxSxx = cpml(d.psi[9], q, d.axH[i], d.bxH[i], dxSxx);
-                    dxSxy = cpml(d.psi[12], q, d.axI[i], d.bxI[i], dxSxy);
-                    dxSxz = cpml(d.psi[15], q, d.axI[i], d.bxI[i], dxSxz);
-                }
-                if (zj) {
-                    const int yj = j < P ? j : j - (N2 - 2 * P);
-                    const unsigned q = (unsigned)((kl * (2 * P) + yj) * N1 + i);
-                    dySxy = cpml(d.psi[10], q, d.ayI[j], d.byI[j], dySxy);
-                    dySyy = cpml(d.psi[13], q, d.ayH[j], d.byH[j], dySyy);
-                    dySyz = cpml(d.psi[16], q, d.ayI[j], d.byI[j], dySyz);
-                }
-                if (PML && (k < P || k >= d.N3 - P)) {
-                    const int zk = k < P ? k : k - (d.N3 - 2 * P);
-                    const unsigned q = (unsigned)(zk * d.plane) + cij;
-                    dzSxz = cpml(d.psi[11], q, d.azI[k], d.bzI[k], dzSxz);
-                    dzSyz = cpml(d.psi[14], q, d.azI[k], d.bzI[k], dzSyz);
-                    dzSzz = cpml(d.psi[17], q, d.azH[k], d.bzH[k], dzSzz);
-                }
-                const float bxv = 0.5f * (r0 + rx), byv = 0.5f * (r0 + ry), bzv = 0.5f * (r0 + r1);
-                ST4(wVx, cij * 4u, vx + bxv * ((dxSxx + dySxy) + dzSxz));
-                ST4(wVy, cij * 4u, vy + byv * ((dxSxy + dySyy) + dzSyz));
-                ST4(wVz, cij * 4u, vz + bzv * ((dxSxz + dySyz) + dzSzz));
-            }
-        }
-        zzm1 = zz0; zz0 = zzp1; zzp1 = zzp2; zzp2 = nzz;
-        xzm2 = xzm1; xzm1 = xz0; xz0 = xzp1; xzp1 = nxz;
-        yzm2 = yzm1; yzm1 = yz0; yz0 = yzp1; yzp1 = nyz;
-        // stage plane kl+1 (the loads were issued before this plane's arithmetic)
-        sS[0][0][bn + own] = nxx; sS[0][1][bn + own] = nyy; sS[0][2][bn + own] = nxy; sS[0][3][bn + own] = xz0; sS[0][4][bn + own] = yz0;
-        la[bn] = nha;
-        if (hasB) lb[bn] = nhb;
-        hcA = nhcA; hcB = nhcB;
-        r0 = r1; mraw = mraw1; mraw1 = nm2; mx = nmx; my = nmy;
-        cB = cC; cC = nc3;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1448,11 +1225,7 @@ __device__ __forceinline__ float glp(const float *b, unsigned ofs, bool c) { con
 __device__ __forceinline__ void gs4(float *b, unsigned ofs, float v) { *(BFD_GA float *)((BFD_GA char *)gbase(b) + gpin(ofs)) = v; }
 __device__ __forceinline__ void gs4nt(float *b, unsigned ofs, float v)
 {
-#ifndef BFD_NT_STORES_OFF
     __builtin_nontemporal_store(v, (BFD_GA float *)((BFD_GA char *)gbase(b) + gpin(ofs)));
-#else
-    gs4(b, ofs, v);
-#endif
 }
 // one halo value: SUBST (Sxx / Syy halos): Szz where the halo cell is fluid, the array itself otherwise; else a shear array where its
 // edge bit is set, 0 elsewhere. One load on every path: the plane base is chosen per lane, the offset falls back to dword 0.
@@ -1475,144 +1248,6 @@ __device__ __forceinline__ float halo_value_c(const float *cbase, const float *a
     const unsigned long long pp = fromAlt ? (unsigned long long)gbase(alt) : (unsigned long long)gbase(cbase);
     const float v = *(BFD_GA const float *)(pp + (take ? (fromAlt ? off4 : e4) : 0u));
     return take ? v : 0.0f;
-}
-
-template <bool PML>
-__device__ __forceinline__ void stress_solid_body_g(const bfd_dev &d, const int4 &run, int tilesX, float (*sV)[2][LH * LW])
-{
-    const int N1 = d.N1, N2 = d.N2;
-    const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16;
-    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TX + tx;
-    const int i0 = bx * TX, j0 = by * TY;
-    const int i = i0 + tx, j = j0 + ty;
-    const bool valid = (i < N1) && (j < N2);
-    const long pl = d.plane;
-    const int P = d.P;
-    const int own = (ty + 2) * LW + tx + 2;
-    const unsigned cij = valid ? (unsigned)(j * N1 + i) : 0u;
-    const unsigned c4 = cij * 4u;
-
-    HaloTask t; t.lofs = -1; t.ok = false; t.arr = 0; t.gofs = 0;
-    if (tid < YT) ytask(tid, 1, i0, j0, N1, N2, t);
-    else if (tid < YT + XT) xtask(tid - YT, 0, i0, j0, N1, N2, t);
-    const bool has = t.lofs >= 0;
-    const float *ph = __builtin_amdgcn_readfirstlane(t.arr) == 0 ? d.Vx : d.Vy;
-    const unsigned hofs = t.ok ? (unsigned)t.gofs * 4u : 0u;
-    float *lh = &sV[0][t.arr][has ? t.lofs : 0];
-    const float c1 = d.c1;
-
-    const bool zi = PML && valid && (i < P || i >= N1 - P);
-    const bool zj = PML && valid && (j < P || j >= N2 - P);
-    float ax = 0, bxc = 0, ay = 0, byc = 0, px = 0, py = 0, pz = 0;
-    unsigned qx = 0, qy = 0;
-    const unsigned dqx = (unsigned)(N2 * 2 * P), dqy = (unsigned)(2 * P * N1);
-    if (zi) { ax = d.axI[i]; bxc = d.bxI[i]; qx = (unsigned)((kbeg * N2 + j) * (2 * P) + (i < P ? i : i - (N1 - 2 * P))); px = F4(d.psi[0], (unsigned)(qx) * 4u); }
-    if (zj) { ay = d.ayI[j]; byc = d.byI[j]; qy = (unsigned)((kbeg * (2 * P) + (j < P ? j : j - (N2 - 2 * P))) * N1 + i); py = F4(d.psi[1], (unsigned)(qy) * 4u); }
-    if (PML) {
-        const int kg = d.k0 + kbeg;
-        if (valid && (kg < P || kg >= d.N3 - P)) pz = F4(d.psi[2], (unsigned)((unsigned)((kg < P ? kg : kg - (d.N3 - 2 * P)) * d.plane) + cij) * 4u);
-    }
-
-    float vx0 = 0, vy0 = 0, vzm2 = 0, vzm1 = 0, vz0 = 0, vzp1 = 0;
-    float sxx = 0, syy = 0, szz = 0, rxx = 0, ryy = 0, rzz = 0;
-    unsigned mraw = 0, cl = BFD_CLS_FLUID | BFD_CLS_NOMEM, cl1 = BFD_CLS_FLUID | BFD_CLS_NOMEM;
-    if (valid) {
-        const float *bVz = d.Vz + kbeg * pl;
-        cl = gl1(d.cls + kbeg * pl, cij); cl1 = gl1(d.cls + kbeg * pl + pl, cij);
-        vx0 = gl4(d.Vx + kbeg * pl, c4); vy0 = gl4(d.Vy + kbeg * pl, c4);
-        vzm2 = gl4(bVz - 2 * pl, c4); vzm1 = gl4(bVz - pl, c4); vz0 = gl4(bVz, c4); vzp1 = gl4(bVz + pl, c4);
-        mraw = gl2(d.mat + kbeg * pl, cij * 2u);
-        szz = gl4(d.Szz + kbeg * pl, c4);
-        const bool fl = cl & BFD_CLS_FLUID, mem = !(cl & BFD_CLS_NOMEM) || !fl;
-        rzz = glp(d.Rzz + kbeg * pl, c4, mem);
-        sxx = glp(d.Sxx + kbeg * pl, c4, !fl); syy = glp(d.Syy + kbeg * pl, c4, !fl);
-        rxx = glp(d.Rxx + kbeg * pl, c4, !fl); ryy = glp(d.Ryy + kbeg * pl, c4, !fl);
-    }
-    float hv = glp(ph + kbeg * pl, hofs, t.ok);
-
-    for (int kl = kbeg; kl < kend; kl++) {
-        const int b = kl & 1;
-        const long ko = (long)__builtin_amdgcn_readfirstlane(kl) * pl;
-        const int k = d.k0 + kl;
-        sV[b][0][own] = vx0; sV[b][1][own] = vy0;
-        if (has) lh[b * (2 * LH * LW)] = hv;
-        const int m = mraw & BFD_MAT_MASK;
-        const bool fl = cl & BFD_CLS_FLUID, mem = !(cl & BFD_CLS_NOMEM) || !fl;
-        float AP = 0, BP = 0, AS2 = 0, BS2 = 0;
-        if (valid) { AP = d.AP[m]; if (mem) BP = d.BP[m]; if (!fl) { AS2 = d.AS2[m]; BS2 = d.BS2[m]; } }
-        __syncthreads();
-
-        // everything plane kl+1 needs: the same loads in every iteration (a predicate that is off reads dword 0 of the plane); the raw
-        // values are not touched before the end of the iteration
-        const bool more = kl + 1 < kend;
-        const long kn = more ? pl : 0;
-        const bool nfl = cl1 & BFD_CLS_FLUID, nmem = !(cl1 & BFD_CLS_NOMEM) || !nfl;
-        const bool pM = more && valid && nmem, pS = more && valid && !nfl, pH = more && t.ok;
-        const unsigned ncl2R = gl1(d.cls + ko + 2 * pl, cij);           // ghost planes make kl+2 addressable
-        const float nvxR = gl4(d.Vx + ko + kn, c4), nvyR = gl4(d.Vy + ko + kn, c4), nvzR = gl4(d.Vz + ko + pl + kn, c4);
-        const unsigned nmrawR = gl2(d.mat + ko + kn, cij * 2u);
-        const float nszzR = gl4(d.Szz + ko + kn, c4);
-        const float nrzzR = gl4(d.Rzz + ko + kn, pM ? c4 : 0u);
-        const float nsxxR = gl4(d.Sxx + ko + kn, pS ? c4 : 0u), nsyyR = gl4(d.Syy + ko + kn, pS ? c4 : 0u);
-        const float nrxxR = gl4(d.Rxx + ko + kn, pS ? c4 : 0u), nryyR = gl4(d.Ryy + ko + kn, pS ? c4 : 0u);
-        const float nhR = gl4(ph + ko + kn, pH ? hofs : 0u);
-        float npx = 0, npy = 0, npz = 0;
-        if (PML) {
-            if (more && zi) npx = F4(d.psi[0], (unsigned)(qx + dqx) * 4u);
-            if (more && zj) npy = F4(d.psi[1], (unsigned)(qy + dqy) * 4u);
-            const int kq = k + 1;
-            if (more && valid && (kq < P || kq >= d.N3 - P)) npz = F4(d.psi[2], (unsigned)((unsigned)((kq < P ? kq : kq - (d.N3 - 2 * P)) * d.plane) + cij) * 4u);
-        }
-
-        if (valid) {
-            const float *sx = &sV[b][0][own], *sy = &sV[b][1][own];
-            float dxVx = dminus4(sx[-2], sx[-1], vx0, sx[1]);
-            float dyVy = dminus4(sy[-2 * LW], sy[-LW], vy0, sy[LW]);
-            float dzVz = dminus4(vzm2, vzm1, vz0, vzp1);
-            if (cl & BFD_CLS_REFL) {
-                gs4(d.Sxx + ko, c4, 0.f); gs4(d.Syy + ko, c4, 0.f); gs4(d.SzzW + ko, c4, 0.f);
-                gs4(d.Rxx + ko, c4, 0.f); gs4(d.Ryy + ko, c4, 0.f); gs4(d.RzzW + ko, c4, 0.f);
-                gs4(d.Sxy + ko, c4, 0.f); gs4(d.Sxz + ko, c4, 0.f); gs4(d.Syz + ko, c4, 0.f);
-                gs4(d.Rxy + ko, c4, 0.f); gs4(d.Rxz + ko, c4, 0.f); gs4(d.Ryz + ko, c4, 0.f);
-            } else {
-                if (zi) { const float pn = bxc * px + ax * dxVx; F4(d.psi[0], (unsigned)(qx) * 4u) = pn; dxVx = dxVx + pn; }
-                if (zj) { const float pn = byc * py + ay * dyVy; F4(d.psi[1], (unsigned)(qy) * 4u) = pn; dyVy = dyVy + pn; }
-                if (PML && (k < P || k >= d.N3 - P)) {
-                    const float pn = d.bzI[k] * pz + d.azI[k] * dzVz;
-                    F4(d.psi[2], (unsigned)((unsigned)((k < P ? k : k - (d.N3 - 2 * P)) * d.plane) + cij) * 4u) = pn;
-                    dzVz = dzVz + pn;
-                }
-                const float sXY = dxVx + dyVy;
-                const float div = sXY + dzVz;
-                if (fl) {               // fluid cell: one copy of the identical normal stresses
-                    float val;
-                    if (!mem) val = szz + AP * div;
-                    else {
-                        const float rn = c1 * rzz - BP * div;
-                        val = szz + (AP * div + 0.5f * (rzz + rn));
-                        gs4nt(d.RzzW + ko, c4, rn);
-                    }
-                    gs4nt(d.SzzW + ko, c4, val);
-                } else {
-                    const float sYZ = dyVy + dzVz, sXZ = dxVx + dzVz;
-                    float rn;
-                    rn = c1 * rxx - (BP * div - BS2 * sYZ);
-                    gs4nt(d.Sxx + ko, c4, sxx + ((AP * div - AS2 * sYZ) + 0.5f * (rxx + rn))); gs4nt(d.Rxx + ko, c4, rn);
-                    rn = c1 * ryy - (BP * div - BS2 * sXZ);
-                    gs4nt(d.Syy + ko, c4, syy + ((AP * div - AS2 * sXZ) + 0.5f * (ryy + rn))); gs4nt(d.Ryy + ko, c4, rn);
-                    rn = c1 * rzz - (BP * div - BS2 * sXY);
-                    gs4nt(d.SzzW + ko, c4, szz + ((AP * div - AS2 * sXY) + 0.5f * (rzz + rn))); gs4nt(d.RzzW + ko, c4, rn);
-                }
-            }
-        }
-        // masks of the prefetched values, queues
-        const bool mv = more && valid;
-        vx0 = mv ? nvxR : 0.0f; vy0 = mv ? nvyR : 0.0f;
-        vzm2 = vzm1; vzm1 = vz0; vz0 = vzp1; vzp1 = mv ? nvzR : 0.0f;
-        hv = pH ? nhR : 0.0f; mraw = mv ? nmrawR : 0u; cl = cl1; cl1 = valid ? ncl2R : (unsigned)(BFD_CLS_FLUID | BFD_CLS_NOMEM);
-        sxx = pS ? nsxxR : 0.0f; syy = pS ? nsyyR : 0.0f; szz = mv ? nszzR : 0.0f; rxx = pS ? nrxxR : 0.0f; ryy = pS ? nryyR : 0.0f; rzz = pM ? nrzzR : 0.0f;
-        px = npx; py = npy; pz = npz; qx += dqx; qy += dqy;
-    }
 }
 
 // CSS: Sxx, Syy and the three shear stresses of listed cells come from the compact arrays (bfd_dev::cssRow). Entry of a cell = base of its
@@ -1772,44 +1407,37 @@ __device__ __forceinline__ void velocity_solid_body_g(const bfd_dev &d, const in
         const long ko = (long)__builtin_amdgcn_readfirstlane(kl) * pl;
         const int k = d.k0 + kl;
         const int bn = (b ^ 1) * bufStride;     // buffer of plane kl+1
-#ifndef BFD_VS_HOLD_BASES
         // Round 6: the array bases are re-read from the kernel argument segment (d is the kernel's first argument; scalar loads, in the scalar cache
         // after the first plane) at three points of every plane instead of being held in scalar registers across the loop: ~19 pairs + ~10 lane
         // masks did not fit (17 scalars spilled to vector lanes, scalar address arithmetic done in vector registers). Spills 17 -> 8 (accumulating
         // flavour) / 27 -> 0 (Z-slab flavour) / 96 -> 34 (absorbing layer), 92 -> 80-82 vector registers: with the bound of 6 waves per SIMD every
         // flavour outside the layer fits 80 registers WITHOUT scratch (the round-5 build spilled 6-7 registers to scratch there and lost 12 %), so
         // three workgroups share a CU instead of two: 0.386 -> 0.362 ms at the shear medium 512^3 (the reload alone, at 5 waves: 0.386).
-        // -DBFD_VS_HOLD_BASES restores the round-5 form. profiles/r6/velocity_solid_bases_reloaded.txt
+        // profiles/r6/velocity_solid_bases_reloaded.txt
         const __attribute__((address_space(4))) bfd_dev *kd = (const __attribute__((address_space(4))) bfd_dev *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(kd));
-#define DD (*kd)
-#else
-#define DD d
-#endif
         // own V and sums of this plane (before the barrier), then, after it, everything plane kl+1 needs: always the same loads
-        const float vx = gl4nt(DD.Vx + ko, c4), vy = gl4nt(DD.Vy + ko, c4), vz = gl4nt(DD.Vz + ko, c4);
+        const float vx = gl4nt(kd->Vx + ko, c4), vy = gl4nt(kd->Vy + ko, c4), vz = gl4nt(kd->Vz + ko, c4);
         float av = 0, pv = 0;
         if (accA) av = gl4nt(accP + ko, c4);
         if (accK) pv = gl4(pkP + ko, c4);
         float r1 = 0, rx = 0, ry = 0;
         if (valid) {
-            r1 = DD.invRho[mraw1 & BFD_MAT_MASK];       // plane kl+1, becomes r0 of the next iteration
-            rx = DD.invRho[mx & BFD_MAT_MASK];
-            ry = DD.invRho[my & BFD_MAT_MASK];
+            r1 = kd->invRho[mraw1 & BFD_MAT_MASK];       // plane kl+1, becomes r0 of the next iteration
+            rx = kd->invRho[mx & BFD_MAT_MASK];
+            ry = kd->invRho[my & BFD_MAT_MASK];
         }
         __syncthreads();
-#ifndef BFD_VS_HOLD_BASES
         asm volatile("" : "+s"(kd));
-#endif
 
         // The raw values are not touched before the end of the iteration (their class masks are applied there): nothing between
         // here and the staging waits for them.
         const bool more = kl + 1 < kend;                // uniform
-        const unsigned nm2 = gl2(DD.mat + ko + 2 * pl, c2);                       // ghost planes make kl+2 addressable
-        const unsigned nc3raw = gl1(DD.cls + ko + (kl + 2 < kend ? 3 : 2) * pl, cij);
+        const unsigned nm2 = gl2(kd->mat + ko + 2 * pl, c2);                       // ghost planes make kl+2 addressable
+        const unsigned nc3raw = gl1(kd->cls + ko + (kl + 2 < kend ? 3 : 2) * pl, cij);
         const bool bfl = (cB & BFD_CLS_FLUID) != 0;
         const long kn = more ? pl : 0;                  // the last iteration reads its own plane again (addressable, unused)
-        const float nzzR = gl4(DD.Szz + ko + 2 * pl + kn, c4);
+        const float nzzR = gl4(kd->Szz + ko + 2 * pl + kn, c4);
         bool pXZ, pYZ, pNN, pXY, takeA, takeB;
         float nxzR, nyzR, nxxR, nyyR, nxyR, nhaR, nhbR;
         unsigned nrb = BFD_CSS_NONE, nrbA = 0, nrbx = 0;
@@ -1819,42 +1447,40 @@ __device__ __forceinline__ void velocity_solid_body_g(const bfd_dev &d, const in
             const unsigned eB = (rbB + css_rank(lB)) * 4u, eC = (rbC + css_rank(css_listed(cC))) * 4u;
             nrb = rowbase(rowp, kl + (kl + 2 < kend ? 3 : 2));
             nrbA = rowbase(rowpA, kl + (more ? 2 : 1));
-            nrbx = *(BFD_GA const unsigned *)((BFD_GA const char *)gbase(DD.cssRow + (kl + (more ? 2 : 1)) * rs) + gpin(rtOfs));
+            nrbx = *(BFD_GA const unsigned *)((BFD_GA const char *)gbase(kd->cssRow + (kl + (more ? 2 : 1)) * rs) + gpin(rtOfs));
             const bool gC = rbC != BFD_CSS_NONE;        // plane kl+2 may be the ghost plane nk: full-volume arrays there (uniform choice)
             pXZ = more && (cC & BFD_CLS_EXZ) && (!WHOLE || gC); pYZ = more && (cC & BFD_CLS_EYZ) && (!WHOLE || gC);
             pNN = more && lB; pXY = more && (cB & BFD_CLS_EXY);
             const unsigned eZ = (WHOLE || gC) ? eC : c4;
-            if (WHOLE) { nxzR = gl4(DD.cSxz, pXZ ? eZ : 0u); nyzR = gl4(DD.cSyz, pYZ ? eZ : 0u); }
-            else { nxzR = gl4(gC ? DD.cSxz : DD.Sxz + ko + pl + kn, pXZ ? eZ : 0u); nyzR = gl4(gC ? DD.cSyz : DD.Syz + ko + pl + kn, pYZ ? eZ : 0u); }
-            nxxR = gl4(DD.cSxx, pNN ? eB : 0u); nyyR = gl4(DD.cSyy, pNN ? eB : 0u); nxyR = gl4(DD.cSxy, pXY ? eB : 0u);
+            if (WHOLE) { nxzR = gl4(kd->cSxz, pXZ ? eZ : 0u); nyzR = gl4(kd->cSyz, pYZ ? eZ : 0u); }
+            else { nxzR = gl4(gC ? kd->cSxz : kd->Sxz + ko + pl + kn, pXZ ? eZ : 0u); nyzR = gl4(gC ? kd->cSyz : kd->Syz + ko + pl + kn, pYZ ? eZ : 0u); }
+            nxxR = gl4(kd->cSxx, pNN ? eB : 0u); nyyR = gl4(kd->cSyy, pNN ? eB : 0u); nxyR = gl4(kd->cSxy, pXY ? eB : 0u);
             const unsigned eA = (rbA + css_rank(ta.ok && css_listed(hcA))) * 4u, eH = entryB(rbA, rbx, hcB) * 4u;
             const bool flA = substA && (hcA & BFD_CLS_FLUID), flB = substB && (hcB & BFD_CLS_FLUID);
             takeA = more && ta.ok && (flA || (substA ? css_listed(hcA) : (hcA & bitA) != 0));
             takeB = more && tb.ok && (flB || (substB ? css_listed(hcB) : (hcB & bitB) != 0));
-            const unsigned long long paA = (unsigned long long)gbase(DD.Szz + ko + kn);
+            const unsigned long long paA = (unsigned long long)gbase(kd->Szz + ko + kn);
             nhaR = *(BFD_GA const float *)((flA ? paA : (unsigned long long)gbase(cbaseA)) + (takeA ? (flA ? offA * 4u : eA) : 0u));
             nhbR = *(BFD_GA const float *)((flB ? paA : (unsigned long long)gbase(cbaseB)) + (takeB ? (flB ? offB * 4u : eH) : 0u));
         } else {
             pXZ = more && valid && (cC & BFD_CLS_EXZ); pYZ = more && valid && (cC & BFD_CLS_EYZ);
             pNN = more && valid && !bfl; pXY = more && valid && (cB & BFD_CLS_EXY);
             takeA = more && ta.ok && (substA || (hcA & bitA)); takeB = more && tb.ok && (substB || (hcB & bitB));
-            nxzR = gl4(DD.Sxz + ko + pl + kn, pXZ ? c4 : 0u);
-            nyzR = gl4(DD.Syz + ko + pl + kn, pYZ ? c4 : 0u);
-            nxxR = gl4(DD.Sxx + ko + kn, pNN ? c4 : 0u);
-            nyyR = gl4(DD.Syy + ko + kn, pNN ? c4 : 0u);
-            nxyR = gl4(DD.Sxy + ko + kn, pXY ? c4 : 0u);
-            const unsigned long long pbA = (unsigned long long)gbase(baseA + ko + kn), paA = (unsigned long long)gbase(DD.Szz + ko + kn);
+            nxzR = gl4(kd->Sxz + ko + pl + kn, pXZ ? c4 : 0u);
+            nyzR = gl4(kd->Syz + ko + pl + kn, pYZ ? c4 : 0u);
+            nxxR = gl4(kd->Sxx + ko + kn, pNN ? c4 : 0u);
+            nyyR = gl4(kd->Syy + ko + kn, pNN ? c4 : 0u);
+            nxyR = gl4(kd->Sxy + ko + kn, pXY ? c4 : 0u);
+            const unsigned long long pbA = (unsigned long long)gbase(baseA + ko + kn), paA = (unsigned long long)gbase(kd->Szz + ko + kn);
             const unsigned long long pbB = (unsigned long long)gbase(baseB + ko + kn);
             nhaR = *(BFD_GA const float *)(((substA && (hcA & BFD_CLS_FLUID)) ? paA : pbA) + (takeA ? offA * 4u : 0u));
             nhbR = *(BFD_GA const float *)(((substB && (hcB & BFD_CLS_FLUID)) ? paA : pbB) + (takeB ? offB * 4u : 0u));
         }
-        const unsigned nmx = gl2(DD.mat + ko + kn, cx2), nmy = gl2(DD.mat + ko + kn, cy2);
-        const unsigned nhcA = gl1(DD.cls + ko + pl + kn, offA), nhcB = gl1(DD.cls + ko + pl + kn, offB);
+        const unsigned nmx = gl2(kd->mat + ko + kn, cx2), nmy = gl2(kd->mat + ko + kn, cy2);
+        const unsigned nhcA = gl1(kd->cls + ko + pl + kn, offA), nhcB = gl1(kd->cls + ko + pl + kn, offB);
 
-#ifndef BFD_VS_HOLD_BASES
         asm volatile("" : "+s"(kd));
-#endif
-        float *wVx = (WHOLE ? DD.Vx : DD.VxW) + ko, *wVy = (WHOLE ? DD.Vy : DD.VyW) + ko, *wVz = (WHOLE ? DD.Vz : DD.VzW) + ko;
+        float *wVx = (WHOLE ? kd->Vx : kd->VxW) + ko, *wVy = (WHOLE ? kd->Vy : kd->VyW) + ko, *wVz = (WHOLE ? kd->Vz : kd->VzW) + ko;
         if (valid) {
             const float sxx = sS[b][0][own], syy = sS[b][1][own], sxy = sS[b][2][own];
             if (ACC) {
@@ -1924,45 +1550,22 @@ __device__ __forceinline__ void velocity_solid_body_g(const bfd_dev &d, const in
     }
     if (QUIET) run_mark_active(d, run.x % tilesX, run.x / tilesX, run.y & 0xFFFF, run.y >> 16, nzb);
 }
-#undef DD
-
-#ifdef BFD_STRESS_SOLID_GLOBAL
-__global__ __launch_bounds__(NTHREADS, SOLID_STRESS_WAVES_PER_SIMD) void stress_solid(bfd_dev d, int tilesX, int nblocks, const int *__restrict__ xmap, const int4 *__restrict__ runs)
-{
-    __shared__ float sV[2][2][LH * LW];
-    const int ri = run_index(nblocks, xmap);
-    if (ri < 0) return;
-    const int4 run = runs[ri];
-    if (run.z & 8) stress_solid_body_g<true>(d, run, tilesX, sV);
-    else stress_solid_body_g<false>(d, run, tilesX, sV);
-}
-#endif
 
 // two kernels (the absorbing-layer flavour needs ~18 registers more and would spill inside a common one); the solid run
 // list keeps the runs that touch the layer at its two ends (bfd_tiles::nSolidBP / nSolidIP)
-#ifndef SOLID_VELOCITY_WAVES_PER_SIMD
-#define SOLID_VELOCITY_WAVES_PER_SIMD 6      // 80 registers = three workgroups per CU; no scratch since the bases are re-read per plane (round 6). The absorbing-layer flavour needs 106 registers and gets 4
-#endif
+constexpr int SOLID_VELOCITY_WAVES_PER_SIMD = 6;      // 80 registers = three workgroups per CU; no scratch since the bases are re-read per plane (round 6). The absorbing-layer flavour needs 106 registers and gets 4
 template <bool ACC, bool PML, bool CSS, bool WHOLE = false, bool QUIET = false>
 __global__ __launch_bounds__(NTHREADS, PML ? 4 : SOLID_VELOCITY_WAVES_PER_SIMD) void velocity_solid(bfd_dev d, int tilesX, int nblocks, const int *__restrict__ xmap,
                                                         float *__restrict__ accP, float *__restrict__ pkP,
                                                         const int4 *__restrict__ runs)
 {
     __shared__ float sS[2][5][LH * LW];
-#ifdef VELOCITY_SOLID_LDS_PAD     // experiment: caps the workgroups per CU through the LDS footprint
-    __shared__ float sPad[VELOCITY_SOLID_LDS_PAD];
-    if (nblocks < 0) { sPad[threadIdx.x] = 1.f; sS[0][0][0] = sPad[(threadIdx.x + 1) & 511]; }
-#endif
     const int ri = run_index(nblocks, xmap);
     if (ri < 0) return;
     const int4 run = runs[ri];
     if (QUIET && run_all_quiet(d, run.x % tilesX, run.x / tilesX, run.y & 0xFFFF, run.y >> 16)) return;
-#ifndef BFD_VELOCITY_SOLID_FLAT      // default since round 4: GLOBAL loads, prefetch without branches (0.405 -> 0.378 ms at the shear medium 512^3)
+    // GLOBAL loads, prefetch without branches: since round 4 (0.405 -> 0.378 ms at the shear medium 512^3 against the FLAT body, removed)
     velocity_solid_body_g<ACC, PML, CSS, WHOLE, QUIET>(d, run, tilesX, sS, accP, pkP);
-#else
-    static_assert(!CSS, "the FLAT body has no compact form");
-    velocity_solid_body<ACC, PML>(d, run, tilesX, sS, accP, pkP);
-#endif
 }
 
 // placement probe (bfd_api.hip, choose_placement): two float32 arrays updated in place at the same cell offset along the
@@ -2052,12 +1655,7 @@ __device__ __forceinline__ float ldv(const float *__restrict__ a, int N1, int N2
 struct FastDiv { unsigned M, s; };
 __device__ __forceinline__ unsigned fdiv(unsigned x, FastDiv f) { return __umulhi(x, f.M) >> f.s; }
 
-#ifndef SPARSE_WAVES_PER_SIMD
-#define SPARSE_WAVES_PER_SIMD 5
-#endif
-#ifndef SPARSE_HOIST
-#define SPARSE_HOIST 1
-#endif
+constexpr int SPARSE_WAVES_PER_SIMD = 5;
 // NORMAL (compact solid state): the kernel also updates Sxx, Syy and their memory variables of its cell (compact arrays, entry t of this launch's
 // part of the list) -- Szz / Rzz of the cell were written by the fluid stress kernel, which ran before and has advanced the absorbing-layer
 // memory variables of dxVx, dyVy, dzVz: they are read here, not advanced.
@@ -2078,7 +1676,7 @@ __global__ __launch_bounds__(256, SPARSE_WAVES_PER_SIMD) void stress_shear_spars
     const unsigned c = LDNT(cells + t);
     // compact solid state: the ten values of the cell are dense streams in list order and depend on nothing -- in flight before the gathers start
     float oSxx = 0.f, oSyy = 0.f, oRxx = 0.f, oRyy = 0.f, oSxy = 0.f, oSxz = 0.f, oSyz = 0.f, oRxy = 0.f, oRxz = 0.f, oRyz = 0.f;
-    if (NORMAL && SPARSE_HOIST) {
+    if (NORMAL) {
         oSxx = LDNT(cSxx + t); oSyy = LDNT(cSyy + t); oRxx = LDNT(cRxx + t); oRyy = LDNT(cRyy + t);
         oSxy = LDNT(cSxy + t); oSxz = LDNT(cSxz + t); oSyz = LDNT(cSyz + t);
         oRxy = LDNT(cRxy + t); oRxz = LDNT(cRxz + t); oRyz = LDNT(cRyz + t);
@@ -2117,7 +1715,7 @@ __global__ __launch_bounds__(256, SPARSE_WAVES_PER_SIMD) void stress_shear_spars
     float dyVx, dxVy, dxVz, dyVz, dxVx = 0.f, dyVy = 0.f, dzVz = 0.f;
     const bool inside = i >= 2 && i + 2 < N1 && j >= 2 && j + 2 < N2;
     if (inside) {
-#ifndef SPARSE_NO_X4  // round 6: the four x-taps of a component as ONE unaligned 16-byte load: 12 of the 30 gathers become 3 (0.245 -> 0.232 ms at the shear medium 512^3)
+        // round 6: the four x-taps of a component as ONE unaligned 16-byte load: 12 of the 30 gathers become 3 (0.245 -> 0.232 ms at the shear medium 512^3)
         typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
         const f4u qx = *(const f4u *)((const char *)uni(d.Vx) + (c4 - 8u));        // Vx at i-2 .. i+1
         const f4u qy = *(const f4u *)((const char *)uni(d.Vy) + (c4 - 4u));        // Vy at i-1 .. i+2
@@ -2128,14 +1726,6 @@ __global__ __launch_bounds__(256, SPARSE_WAVES_PER_SIMD) void stress_shear_spars
         dxVz = dplus4(qz.x, vz0, qz.z, qz.w);
         dyVz = dplus4(F4(d.Vz, c4 - r4), vz0, F4(d.Vz, c4 + r4), F4(d.Vz, c4 + 2 * r4));
         if (NORMAL) { dxVx = dminus4(qx.x, qx.y, vx0, qx.w); dyVy = dminus4(F4(d.Vy, c4 - 2 * r4), F4(d.Vy, c4 - r4), vy0, F4(d.Vy, c4 + r4)); }
-#else
-        vx0 = F4(d.Vx, c4); vy0 = F4(d.Vy, c4); vz0 = F4(d.Vz, c4);
-        dyVx = dplus4(F4(d.Vx, c4 - r4), vx0, F4(d.Vx, c4 + r4), F4(d.Vx, c4 + 2 * r4));
-        dxVy = dplus4(F4(d.Vy, c4 - 4u), vy0, F4(d.Vy, c4 + 4u), F4(d.Vy, c4 + 8u));
-        dxVz = dplus4(F4(d.Vz, c4 - 4u), vz0, F4(d.Vz, c4 + 4u), F4(d.Vz, c4 + 8u));
-        dyVz = dplus4(F4(d.Vz, c4 - r4), vz0, F4(d.Vz, c4 + r4), F4(d.Vz, c4 + 2 * r4));
-        if (NORMAL) { dxVx = dminus4(F4(d.Vx, c4 - 8u), F4(d.Vx, c4 - 4u), vx0, F4(d.Vx, c4 + 4u)); dyVy = dminus4(F4(d.Vy, c4 - 2 * r4), F4(d.Vy, c4 - r4), vy0, F4(d.Vy, c4 + r4)); }
-#endif
     } else {
         vx0 = F4(d.Vx, c4); vy0 = F4(d.Vy, c4); vz0 = F4(d.Vz, c4);
         dyVx = dplus4(ldv(d.Vx, N1, N2, i, j - 1, ko), vx0, ldv(d.Vx, N1, N2, i, j + 1, ko), ldv(d.Vx, N1, N2, i, j + 2, ko));
@@ -2176,7 +1766,6 @@ __global__ __launch_bounds__(256, SPARSE_WAVES_PER_SIMD) void stress_shear_spars
         const float sXY = dxVx + dyVy;
         const float div = sXY + dzVz;
         const float sYZ = dyVy + dzVz, sXZ = dxVx + dzVz;
-        if (!SPARSE_HOIST) { oSxx = LDNT(cSxx + t); oSyy = LDNT(cSyy + t); oRxx = LDNT(cRxx + t); oRyy = LDNT(cRyy + t); }
         float rn = c1 * oRxx - (BP * div - BS2 * sYZ);
         __builtin_nontemporal_store(oSxx + ((AP * div - AS2 * sYZ) + 0.5f * (oRxx + rn)), cSxx + t); __builtin_nontemporal_store(rn, cRxx + t);
         rn = c1 * oRyy - (BP * div - BS2 * sXZ);
@@ -2189,23 +1778,23 @@ __global__ __launch_bounds__(256, SPARSE_WAVES_PER_SIMD) void stress_shear_spars
     float *pSxy = cSxy ? cSxy + t : d.Sxy + c, *pSxz = cSxz ? cSxz + t : d.Sxz + c, *pSyz = cSyz ? cSyz + t : d.Syz + c;
     if (Axy != 0.f) {
         const float e = dyVx + dxVy;
-        const float r = (NORMAL && SPARSE_HOIST) ? oRxy : LDNT(pRxy), rn = c1 * r - Bxy * e;
-        *pSxy = ((NORMAL && SPARSE_HOIST) ? oSxy : LDNT(pSxy)) + (Axy * e + 0.5f * (r + rn)); *pRxy = rn;
+        const float r = NORMAL ? oRxy : LDNT(pRxy), rn = c1 * r - Bxy * e;
+        *pSxy = (NORMAL ? oSxy : LDNT(pSxy)) + (Axy * e + 0.5f * (r + rn)); *pRxy = rn;
     }
     // compact solid state in a Z-slab: the planes a neighbour reads (its ghost planes: my plane 0 and my last two) also go to the full-volume
     // Sxz / Syz, which is where the halo exchange takes them from
     const bool shared = NORMAL && (kl == 0 || kl >= d.nk - 2);
     if (Axz != 0.f) {
         const float e = dzVx + dxVz;
-        const float r = (NORMAL && SPARSE_HOIST) ? oRxz : LDNT(pRxz), rn = c1 * r - Bxz * e;
-        const float v = ((NORMAL && SPARSE_HOIST) ? oSxz : LDNT(pSxz)) + (Axz * e + 0.5f * (r + rn));
+        const float r = NORMAL ? oRxz : LDNT(pRxz), rn = c1 * r - Bxz * e;
+        const float v = (NORMAL ? oSxz : LDNT(pSxz)) + (Axz * e + 0.5f * (r + rn));
         *pSxz = v; *pRxz = rn;
         if (shared) d.Sxz[c] = v;
     }
     if (Ayz != 0.f) {
         const float e = dzVy + dyVz;
-        const float r = (NORMAL && SPARSE_HOIST) ? oRyz : LDNT(pRyz), rn = c1 * r - Byz * e;
-        const float v = ((NORMAL && SPARSE_HOIST) ? oSyz : LDNT(pSyz)) + (Ayz * e + 0.5f * (r + rn));
+        const float r = NORMAL ? oRyz : LDNT(pRyz), rn = c1 * r - Byz * e;
+        const float v = (NORMAL ? oSyz : LDNT(pSyz)) + (Ayz * e + 0.5f * (r + rn));
         *pSyz = v; *pRyz = rn;
         if (shared) d.Syz[c] = v;
     }
@@ -2334,27 +1923,6 @@ __device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4
     }
 }
 
-#ifdef BFD_EXP_XCD_CLOCK
-// Experiment build: when does each XCD finish its part of a fluid launch? Every block leaves the wall clock (100 MHz) of its start and of
-// its end in its own slot (plain stores: atomics on a few shared addresses serialise in one L2 channel and triple the launch time), the
-// end together with the XCC_ID hardware register, so that the assumption remap_block rests on (block b runs on XCD b & 7) can be checked.
-// kind 0 / 1 = stress_fluid / velocity_fluid. bfd_debug_xcd_clock() copies the slots out.
-constexpr int XCLK_MAX = 1 << 17;
-__device__ unsigned long long g_blkStart[2][XCLK_MAX], g_blkEnd[2][XCLK_MAX];
-__device__ __forceinline__ void xcd_clock_begin(int kind) { if (threadIdx.x == 0 && blockIdx.x < XCLK_MAX) g_blkStart[kind][blockIdx.x] = wall_clock64(); }
-__device__ __forceinline__ void xcd_clock_end(int kind)
-{
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < XCLK_MAX) {
-        const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;          // HW_REG_XCC_ID, bits 3:0
-        g_blkEnd[kind][blockIdx.x] = (wall_clock64() << 4) | xcc;
-    }
-}
-#else
-__device__ __forceinline__ void xcd_clock_begin(int) {}
-__device__ __forceinline__ void xcd_clock_end(int) {}
-#endif
-
 // COLLAPSED = true: all-fluid slab, every run keeps only Szz/Rzz. false: slab with solid tiles; runs flagged LEAN
 // (bit4) still take the collapsed bodies, the others write all three normal stresses.
 template <bool COLLAPSED, bool QUIET = false, bool PAIR = false>
@@ -2366,10 +1934,8 @@ __global__ __launch_bounds__(NTHREADS, FLUID_WAVES_PER_SIMD) void stress_fluid(b
     const int ri = run_index(nblocks, xmap);
     if (ri < 0) return;
     const int4 run = runs[ri];
-    xcd_clock_begin(0);
     if (COLLAPSED || (run.z & 16)) stress_fluid_switch<true, QUIET, PAIR>(d, run, tilesX, sV, accP, pkP);
     else stress_fluid_switch<false, QUIET, PAIR>(d, run, tilesX, sV, accP, pkP);
-    xcd_clock_end(0);
 }
 
 // Paired accumulation, flush: the Pressure of the current Szz that the pairing stress flavour has not added yet, at the cells velocity_fluid
@@ -2405,7 +1971,6 @@ __global__ __launch_bounds__(NTHREADS, VELOCITY_FLUID_WAVES_PER_SIMD) void veloc
     if (ri < 0) return;
     const int4 run = runs[ri];
     const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16, tm = run.w;
-    xcd_clock_begin(1);
     if (QUIET && run_all_quiet(d, bx, by, kbeg, kend)) return;
     switch ((run.z >> 2) & 3) {
     case 0: velocity_fluid_body<ACC, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
@@ -2413,7 +1978,6 @@ __global__ __launch_bounds__(NTHREADS, VELOCITY_FLUID_WAVES_PER_SIMD) void veloc
     case 2: velocity_fluid_body<ACC, false, true, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
     default: velocity_fluid_body<ACC, true, true, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
     }
-    xcd_clock_end(1);
 }
 
 // one workgroup per 64 x 8 x SUBZ sub-tile. flags: bit0 = a solid cell within the sub-tile grown by 2 cells;
@@ -2467,14 +2031,6 @@ void bfd_tile_grid(const bfd_dev &d, int *tilesX, int *tilesY, int *subZ)
 }
 int bfd_tile_zchunk(void) { return ZCHUNK; }
 int bfd_tile_subz(void) { return SUBZ; }
-bool bfd_css_supported(void)
-{
-#if defined(BFD_VELOCITY_SOLID_FLAT) || defined(BFD_STRESS_SOLID_GLOBAL)
-    return false;
-#else
-    return true;
-#endif
-}
 
 void bfd_launch_probe_pair(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, float *a, float *b, int kmax)
 {
@@ -2495,31 +2051,26 @@ void bfd_launch_count_solid_cells(const bfd_dev &d, hipStream_t s, const int4 *s
 // Order of the sparse shear list. Ascending in the cell index (k, j, i), a cell's z neighbours (planes k-2 .. k+2, 9 of its 21
 // gathered V values) were touched a whole plane of listed cells earlier: 1 MB of traffic at 512^2 planes, 3.8 MB at 1024^2, five
 // planes of that beyond the 4 MB L2 of an XCD -- at 1024^3 the kernel moved 1.68 x its algorithmic bytes (8.58 GB per launch).
-// Mode 2 (default): (z-chunk of 16 planes, band of 8 rows, plane, row, i): rows keep their whole length in x, the z neighbours are
+// The order kept: (z-chunk of 16 planes, band of 8 rows, plane, row, i): rows keep their whole length in x, the z neighbours are
 // one band-plane away: 6.21 GB = 1.21 x at 1024^3, unchanged at 512^3 (0.89 GB, where the planes fitted), kernel time unchanged:
 // it follows neither the bytes nor the number of gathers (the six x neighbours taken from the neighbouring lanes by shuffles: 4-9 %
-// slower). Mode 1 cuts the rows at the 64-wide tiles as well: same bytes, 3 % slower.
+// slower). Cutting the rows at the 64-wide tiles as well: same bytes, 3 % slower (removed, like the ascending order).
 // The three plane ranges the split half-steps launch separately (first / middle / last planes of a slab) stay contiguous: their
 // number leads the key. profiles/r3/shear_list_order.txt
-// mode 2: rows keep their whole length in x: (part of the slab, z-chunk, band of 8 rows, plane, row, i)
+// rows keep their whole length in x: (part of the slab, z-chunk, band of 8 rows, plane, row, i)
 __device__ __forceinline__ unsigned long long shear_key2(unsigned i, unsigned j, unsigned k, int lowPlanes, int hiStart)
 {
     const unsigned long long seg = (int)k < lowPlanes ? 0ull : ((int)k >= hiStart ? 2ull : 1ull);
     return (seg << 44) | ((unsigned long long)(k >> 4) << 32) | ((unsigned long long)(j >> 3) << 19) |
            ((unsigned long long)(k & 15u) << 15) | ((unsigned long long)(j & 7u) << 12) | (unsigned long long)(i & 4095u);
 }
-__global__ void shear_order_keys(bfd_dev d, const unsigned *__restrict__ cells, unsigned long long *__restrict__ keys, long n, int lowPlanes, int hiStart, int mode)
+__global__ void shear_order_keys(bfd_dev d, const unsigned *__restrict__ cells, unsigned long long *__restrict__ keys, long n, int lowPlanes, int hiStart)
 {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const unsigned c = cells[t];
     const unsigned i = c % (unsigned)d.N1, j = (c / (unsigned)d.N1) % (unsigned)d.N2, k = c / (unsigned)d.plane;
-    const unsigned long long seg = (int)k < lowPlanes ? 0ull : ((int)k >= hiStart ? 2ull : 1ull);
-    if (mode == 2)
-        keys[t] = shear_key2(i, j, k, lowPlanes, hiStart);
-    else
-        keys[t] = (seg << 44) | ((unsigned long long)(k >> 4) << 32) | ((unsigned long long)(j >> 3) << 19) | ((unsigned long long)(i >> 6) << 13) |
-                  ((unsigned long long)(k & 15u) << 9) | ((unsigned long long)(j & 7u) << 6) | (unsigned long long)(i & 63u);
+    keys[t] = shear_key2(i, j, k, lowPlanes, hiStart);
 }
 // Row table of the compact solid state (bfd_dev::cssRow) for a list in order mode 2: entry (plane kk = kl + 2, row j, tile bx) = number of listed
 // cells that precede cell (64 bx, j, kl) in list order = lower bound of its key in the sorted list (the keys are recomputed from the cells). A
@@ -2567,9 +2118,9 @@ void bfd_launch_css_gather(hipStream_t s, const unsigned *cells, long n, const f
     if (n > 0) hipLaunchKernelGGL(css_gather, dim3((unsigned)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, s, cells, n, srcFull, dstCompact);
 }
 
-void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart, int mode)
+void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart)
 {
-    if (n) hipLaunchKernelGGL(shear_order_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cells, keys, n, lowPlanes, hiStart, mode);
+    if (n) hipLaunchKernelGGL(shear_order_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cells, keys, n, lowPlanes, hiStart);
 }
 
 void bfd_launch_mark_solid(const bfd_dev &d, hipStream_t s, unsigned char *flag, long n, bool mixedOnly)
@@ -2618,6 +2169,15 @@ void bfd_launch_classify(const bfd_dev &d, hipStream_t s, int *flagsDev, int *ti
         hipLaunchKernelGGL(K, dim3(xm_ ? 8 * t->xmapH[m][9] : (n)), dim3(TX, TY, 1), 0, s, d, tilesX, n, xm_, __VA_ARGS__); } while (0)
 #define BFD_KT(cls, end) do { if (t->ktimer) bfd_kmark(t->ktimer, cls, end, s); } while (0)
 
+// run-time flags into template arguments: lift(f, a, b, ...) calls f(std::bool_constant<a>(), std::bool_constant<b>(), ...). A kernel flavour is
+// instantiated for every combination f's body names, so f guards the combinations that are never launched with if constexpr.
+template <typename F> static inline void lift(F &&f) { f(); }
+template <typename F, typename... B> static inline void lift(F &&f, bool b, B... rest)
+{
+    if (b) lift([&](auto... c) { f(std::true_type(), c...); }, rest...);
+    else lift([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
+
 // run list layout: [fluid boundary | fluid interior | solid boundary | solid interior]; "boundary" = runs
 // inside the first and the last ZCHUNK planes of the slab (the planes a Z-neighbour reads).
 // part: 0 = every run, 1 = boundary runs, 2 = interior runs
@@ -2635,32 +2195,35 @@ void bfd_launch_flush_paired(const bfd_dev &d, hipStream_t s, float *accP, float
         hipLaunchKernelGGL(flush_paired_pressure, dim3(t->nFluid), dim3(TX, TY, 1), 0, s, d, tilesX, t->nFluid, (const int4 *)t->runs, accP, pkP);
 }
 
-void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, int part, float *accP, float *pkP)
+void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part, float *accP, float *pkP)
 {
     const bool pair = (accP || pkP) && !d.act;       // the pairing flavour of the plain fluid runs (quiet runs never pair)
     const int tilesX = (d.N1 + TX - 1) / TX;
     int off, n, offS, nS;
     part_range(t->nFluid, t->nFluidB, part, &off, &n);
     part_range(t->nSolid, t->nSolidB, part, &offS, &nS);
-    hipStream_t s = s0;
     // Compact solid state: Szz / Rzz of EVERY run, solid ones included, in one launch of the fluid kernel over the combined list (natural order:
     // a solid run sits between its fluid neighbours, their ring lines are shared in L2), then the sparse kernel with everything that exists
     // only at solid cells. It must come second: it reads the absorbing-layer memory variables the fluid kernel advances.
     const bool all = d.cssRow && t->runsAll;
+    // fluid kernel over cnt runs; m = index of the cost-balanced map of the range, -1 = none. Flavours: plain, QUIET, PAIR (never both)
+    auto stressFluid = [&](int cnt, int m, const int4 *runs) {
+        BFD_KT(BFD_K_STRESS_FLUID, 0);
+        const int *xm = (m >= 0 && t->xmap) ? t->xmap + 10 * m : nullptr;
+        lift([&](auto QUIET, auto PAIR) {
+            constexpr bool Q = decltype(QUIET)::value, P = decltype(PAIR)::value;
+            if constexpr (!(Q && P))       // fluid cells keep one copy of their normal stresses (bfd_dev::cls): COLLAPSED
+                hipLaunchKernelGGL((stress_fluid<true, Q, P>), dim3(xm ? 8 * t->xmapH[m][9] : cnt), dim3(TX, TY, 1), 0, s, d, tilesX, cnt, xm, runs,
+                                   P ? accP : (float *)nullptr, P ? pkP : (float *)nullptr);
+        }, d.act != nullptr, pair);
+        BFD_KT(BFD_K_STRESS_FLUID, 1);
+    };
     if (all) {
         int offA, nA;
         part_range(t->nAll, t->nAllB, part, &offA, &nA);
-        if (nA) {
-            BFD_KT(BFD_K_STRESS_FLUID, 0);
-            if (d.act) BFD_LAUNCH((stress_fluid<true, true>), nA, (const int *)nullptr, t->runsAll + offA, (float *)nullptr, (float *)nullptr);
-            else if (pair) BFD_LAUNCH((stress_fluid<true, false, true>), nA, (const int *)nullptr, t->runsAll + offA, accP, pkP);
-            else BFD_LAUNCH((stress_fluid<true>), nA, (const int *)nullptr, t->runsAll + offA, (float *)nullptr, (float *)nullptr);
-            BFD_KT(BFD_K_STRESS_FLUID, 1);
-        }
+        if (nA) stressFluid(nA, -1, t->runsAll + offA);
         n = 0; nS = 0;
     }
-    const bool conc = t->sideStream[0] && !t->ktimer && (nS || (t->shearCells && t->nShear)) && n;
-    if (conc) { hipEventRecord(t->sideFork, s0); hipStreamWaitEvent(t->sideStream[0], t->sideFork, 0); hipStreamWaitEvent(t->sideStream[1], t->sideFork, 0); s = t->sideStream[0]; }
     if (nS) {
         BFD_KT(BFD_K_STRESS_SOLID, 0);
         if (t->shearCells && t->merged) BFD_LAUNCH_X(stress_solid_merged, nS, BFD_XM_SS + part, t->runs + t->nFluid + offS, (const float *)t->shearTab);
@@ -2668,7 +2231,6 @@ void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, 
         else BFD_LAUNCH(stress_v2, nS, t->runs + t->nFluid + offS, (const unsigned short *)nullptr);     // variant 2: monolithic, dense
         BFD_KT(BFD_K_STRESS_SOLID, 1);
     }
-    if (conc) s = t->sideStream[1];
     if (t->shearCells && t->nShear) {     // sparse shear: cells sorted by index; [0,lowEnd) and [highBeg,n) are the boundary chunks
         long b0 = 0, e0 = t->nShear, b1 = 0, e1 = 0;
         if (part == 1) { e0 = t->shearLowEnd; b1 = t->shearHighBeg; e1 = t->nShear; }
@@ -2689,18 +2251,10 @@ void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s0, const bfd_tiles *t, 
         sparse(b0, e0, R0); sparse(b1, e1, R1);
         BFD_KT(BFD_K_STRESS_SHEAR, 1);
     }
-    s = s0;
-    if (n) {
-        BFD_KT(BFD_K_STRESS_FLUID, 0);
-        if (d.act) BFD_LAUNCH_X((stress_fluid<true, true>), n, BFD_XM_SF + part, t->runs + off, (float *)nullptr, (float *)nullptr);
-        else if (pair) BFD_LAUNCH_X((stress_fluid<true, false, true>), n, BFD_XM_SF + part, t->runs + off, accP, pkP);
-        else BFD_LAUNCH_X((stress_fluid<true>), n, BFD_XM_SF + part, t->runs + off, (float *)nullptr, (float *)nullptr);      // fluid cells keep one copy of their normal stresses (bfd_dev::cls)
-        BFD_KT(BFD_K_STRESS_FLUID, 1);
-    }
-    if (conc) for (int q = 0; q < 2; q++) { hipEventRecord(t->sideJoin[q], t->sideStream[q]); hipStreamWaitEvent(s0, t->sideJoin[q], 0); }
+    if (n) stressFluid(n, BFD_XM_SF + part, t->runs + off);
 }
 
-void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc)
+void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc)
 {
     const int tilesX = (d.N1 + TX - 1) / TX;
     const bool acc = accP || pkP;
@@ -2708,9 +2262,6 @@ void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float
     int offF, nF, off, n;
     part_range(t->nFluid, t->nFluidB, part, &offF, &nF);
     part_range(t->nSolid, t->nSolidB, part, &off, &n);
-    hipStream_t s = s0;
-    const bool conc = t->sideStream[0] && !t->ktimer && n && nF && t->shearCells;
-    if (conc) { hipEventRecord(t->sideFork, s0); hipStreamWaitEvent(t->sideStream[0], t->sideFork, 0); s = t->sideStream[0]; }
     if (n) {
         BFD_KT(BFD_K_VELOCITY_SOLID, 0);
         if (t->shearCells) {
@@ -2720,61 +2271,30 @@ void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s0, float *accP, float
             if (part != 2) { pb = 0; pe = t->nSolidBP; }
             if (part != 1) { qb = t->nSolid - t->nSolidIP; qe = t->nSolid; }
             const int nb = part == 2 ? t->nSolidB : t->nSolidBP, ne = part == 1 ? t->nSolidB : t->nSolid - t->nSolidIP;
+            // CSS: compact solid state; WHOLE: V updated in place on a whole domain, or the interior runs of a Z-slab (part 2 of a split half-step: they
+            // reach no ghost plane); QUIET: runs without activity return at entry (production calls). WHOLE and QUIET exist in the compact form only.
+            const bool css = d.cssRow != nullptr, inPlace = css && d.VxW == d.Vx && d.VyW == d.Vy && d.VzW == d.Vz;
+            const bool whole = inPlace && ((d.k0 == 0 && d.nk == d.N3) || part == 2), quiet = inPlace && d.act != nullptr;
             auto go = [&](bool pml, int a0, int a1, int m) {
                 const int cnt = a1 - a0;
                 if (cnt <= 0) return;
-#ifndef BFD_VELOCITY_SOLID_FLAT
-                // a whole domain, or the interior runs of a Z-slab (part 2 of a split half-step: they reach no ghost plane), V in place
-                if (d.act && d.cssRow && d.VxW == d.Vx && d.VyW == d.Vy && d.VzW == d.Vz) {       // quiet runs return at entry (production calls)
-                    if ((d.k0 == 0 && d.nk == d.N3) || part == 2) {
-                        if (pml) { if (acc) BFD_LAUNCH_X((velocity_solid<true, true, true, true, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, true, true, true, true>), cnt, m, accP, pkP, base + a0); }
-                        else { if (acc) BFD_LAUNCH_X((velocity_solid<true, false, true, true, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, false, true, true, true>), cnt, m, accP, pkP, base + a0); }
-                    } else {
-                        if (pml) { if (acc) BFD_LAUNCH_X((velocity_solid<true, true, true, false, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, true, true, false, true>), cnt, m, accP, pkP, base + a0); }
-                        else { if (acc) BFD_LAUNCH_X((velocity_solid<true, false, true, false, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, false, true, false, true>), cnt, m, accP, pkP, base + a0); }
-                    }
-                    return;
-                }
-                if (d.cssRow && d.VxW == d.Vx && d.VyW == d.Vy && d.VzW == d.Vz && ((d.k0 == 0 && d.nk == d.N3) || part == 2)) {
-                    if (pml) { if (acc) BFD_LAUNCH_X((velocity_solid<true, true, true, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, true, true, true>), cnt, m, accP, pkP, base + a0); }
-                    else { if (acc) BFD_LAUNCH_X((velocity_solid<true, false, true, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, false, true, true>), cnt, m, accP, pkP, base + a0); }
-                    return;
-                }
-                if (d.cssRow) {
-                    if (pml) { if (acc) BFD_LAUNCH_X((velocity_solid<true, true, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, true, true>), cnt, m, accP, pkP, base + a0); }
-                    else { if (acc) BFD_LAUNCH_X((velocity_solid<true, false, true>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, false, true>), cnt, m, accP, pkP, base + a0); }
-                    return;
-                }
-#endif
-                if (pml) { if (acc) BFD_LAUNCH_X((velocity_solid<true, true, false>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, true, false>), cnt, m, accP, pkP, base + a0); }
-                else { if (acc) BFD_LAUNCH_X((velocity_solid<true, false, false>), cnt, m, accP, pkP, base + a0); else BFD_LAUNCH_X((velocity_solid<false, false, false>), cnt, m, accP, pkP, base + a0); }
+                lift([&](auto ACC, auto PML, auto CSS, auto WHOLE, auto QUIET) {
+                    constexpr bool C = decltype(CSS)::value, W = decltype(WHOLE)::value, Q = decltype(QUIET)::value;
+                    if constexpr (C || (!W && !Q))
+                        BFD_LAUNCH_X((velocity_solid<decltype(ACC)::value, decltype(PML)::value, C, W, Q>), cnt, m, accP, pkP, base + a0);
+                }, acc, pml, css, whole, quiet);
             };
             go(false, nb, ne, BFD_XM_VS + part); go(true, pb, pe, BFD_XM_VSP_LO); go(true, qb, qe, BFD_XM_VSP_HI);
         } else {                                                     // variant 2: dense
-            if (acc) BFD_LAUNCH((velocity_v2<true>), n, accP, pkP, t->runs + t->nFluid + off);
-            else BFD_LAUNCH((velocity_v2<false>), n, accP, pkP, t->runs + t->nFluid + off);
+            lift([&](auto ACC) { BFD_LAUNCH((velocity_v2<decltype(ACC)::value>), n, accP, pkP, t->runs + t->nFluid + off); }, acc);
         }
         BFD_KT(BFD_K_VELOCITY_SOLID, 1);
     }
-    s = s0;
     if (nF) {
         BFD_KT(BFD_K_VELOCITY_FLUID, 0);
-        if (d.act) {
-            if (accF) BFD_LAUNCH_X((velocity_fluid<true, true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
-            else BFD_LAUNCH_X((velocity_fluid<false, true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
-        } else if (accF) BFD_LAUNCH_X((velocity_fluid<true>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
-        else BFD_LAUNCH_X((velocity_fluid<false>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
+        lift([&](auto ACC, auto QUIET) {
+            BFD_LAUNCH_X((velocity_fluid<decltype(ACC)::value, decltype(QUIET)::value>), nF, BFD_XM_VF + part, t->runs + offF, accP, pkP);
+        }, accF, d.act != nullptr);
         BFD_KT(BFD_K_VELOCITY_FLUID, 1);
     }
-    if (conc) { hipEventRecord(t->sideJoin[0], t->sideStream[0]); hipStreamWaitEvent(s0, t->sideJoin[0], 0); }
 }
-
-#ifdef BFD_EXP_XCD_CLOCK
-// experiment build only: copies the first n block slots of a kind out: start[n], end[n] (end << 4 | xcc id)
-extern "C" int bfd_debug_xcd_clock(int kind, int n, unsigned long long *start, unsigned long long *end)
-{
-    if (kind < 0 || kind > 1 || n < 0 || n > XCLK_MAX) return -1;
-    if (hipMemcpyFromSymbol(start, HIP_SYMBOL(g_blkStart), (size_t)n * 8, (size_t)kind * XCLK_MAX * 8) != hipSuccess) return -1;
-    return hipMemcpyFromSymbol(end, HIP_SYMBOL(g_blkEnd), (size_t)n * 8, (size_t)kind * XCLK_MAX * 8) == hipSuccess ? 0 : -1;
-}
-#endif

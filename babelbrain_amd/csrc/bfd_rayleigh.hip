@@ -17,10 +17,6 @@
 #include "bfd_internal.h"
 #include <math.h>
 
-#ifndef BFD_RAYLEIGH_UNROLL
-#define BFD_RAYLEIGH_UNROLL 2
-#endif
-
 namespace {
 
 constexpr int RB = 256;      // threads per workgroup
@@ -68,22 +64,17 @@ __global__ __launch_bounds__(RB) void rayleigh_forward(const float *__restrict__
         float br[PPL], bi[PPL];
 #pragma unroll
         for (int p = 0; p < PPL; p++) { br[p] = 0.f; bi[p] = 0.f; }
-#pragma unroll BFD_RAYLEIGH_UNROLL
+#pragma unroll 2
         for (int q = q0; q < q1; q++) {
             const float4 s = sA[q];
             const float sim = sB[q];
 #pragma unroll
             for (int p = 0; p < PPL; p++) {
                 const double dx = px[p] - (double)s.x, dy = py[p] - (double)s.y, dz = pz[p] - (double)s.z;
-#ifdef BFD_RAYLEIGH_NO_FMA
-                const double r2 = dx * dx + dy * dy + dz * dz;
-                double inv = (double)rsqrtf((float)r2);
-                inv = inv * (1.5 - 0.5 * r2 * inv * inv);
-#else           // explicit fused multiply-adds (the build contracts nothing by itself): 11 float64 operations per pair instead of 15
+                // explicit fused multiply-adds (the build contracts nothing by itself): 11 float64 operations per pair instead of 15
                 const double r2 = __builtin_fma(dx, dx, __builtin_fma(dy, dy, dz * dz));
                 double inv = (double)rsqrtf((float)r2);
                 inv = __builtin_fma(inv, __builtin_fma(-0.5 * r2, inv * inv, 0.5), inv);          // y + y (1 - r2 y^2) / 2
-#endif
                 const double R = r2 * inv;
                 const double rev = R * krev;
                 // hardware sine / cosine: v_sin_f32 / v_cos_f32 take their argument in revolutions (a float32 Taylor polynomial on
@@ -98,13 +89,8 @@ __global__ __launch_bounds__(RB) void rayleigh_forward(const float *__restrict__
                 if (ATT) amp *= __expf(kif * (float)R);              // exp(-i k R) with complex k: Im k < 0 attenuates
                 // (re + i im) * amp * (cos - i sin)
                 const float er = amp * cs, ei = amp * sn;
-#ifdef BFD_RAYLEIGH_NO_FMA
-                br[p] += s.w * er + sim * ei;
-                bi[p] += sim * er - s.w * ei;
-#else
                 br[p] = __builtin_fmaf(s.w, er, __builtin_fmaf(sim, ei, br[p]));
                 bi[p] = __builtin_fmaf(sim, er, __builtin_fmaf(-s.w, ei, bi[p]));
-#endif
             }
         }
 #pragma unroll
@@ -150,8 +136,7 @@ extern "C" int bfd_rayleigh_forward(int32_t device, int64_t nSrc, const float *c
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e == hipSuccess) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, 0); }
     if (e == hipSuccess) {
-        int ppl = nPts >= (1 << 20) ? 4 : nPts >= (1 << 18) ? 2 : 1;
-        if (const char *ev = getenv("BFD_RAYLEIGH_PPL")) { const int v = atoi(ev); if (v == 1 || v == 2 || v == 4) ppl = v; }
+        const int ppl = nPts >= (1 << 20) ? 4 : nPts >= (1 << 18) ? 2 : 1;
         const dim3 grid((unsigned)((nPts + RB * ppl - 1) / (RB * ppl)));
 #define RAYLEIGH_LAUNCH(P, A) hipLaunchKernelGGL((rayleigh_forward<P, A>), grid, dim3(RB), 0, 0, dc, dd, du, (long)nSrc, kReal, kImag, dr, (long)nPts, dout)
         const bool att = kImag != 0.0;

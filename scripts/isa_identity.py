@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Per-kernel comparison of the gfx950 machine code of two builds of babelbrain_amd/csrc (refactor check).
+
+    make -C <tree>/babelbrain_amd/csrc -j16 EXTRA=-Rpass-analysis=kernel-resource-usage > <tree>.log 2>&1     (both trees)
+    scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log
+
+The fat binary section of every object is unbundled (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler --unbundle),
+disassembled (llvm-objdump -d) and cut at the kernel symbols; the instruction text of a kernel (addresses and encodings dropped) and its resource remarks (registers, spills, scratch, occupancy, LDS) must be equal on both sides.
+Exit status 0 = nothing differs and no kernel exists only in the second build."""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get('LLVM_BIN', '/opt/rocm/lib/llvm/bin')
+SRC = ['bfd_api', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte']
+
+
+def kernels(obj, tmp):
+    fb, co = os.path.join(tmp, 'x.fb'), os.path.join(tmp, 'x.co')
+    if subprocess.call([os.path.join(LLVM, 'llvm-objcopy'), '--dump-section', '.hip_fatbin=' + fb, obj, os.devnull], stderr=subprocess.DEVNULL) != 0:
+        return {}       # an object without device code
+    subprocess.check_call([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
+                           '--input=' + fb, '--output=' + co])
+    text = subprocess.check_output([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', co], text=True)
+    out, cur = {}, None
+    for line in text.split('\n'):
+        m = re.match(r'^[0-9a-f]+ <(.+)>:$', line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            cur.append(re.sub(r'\s*//.*$', '', line).strip())
+    return out
+
+
+def resources(log):
+    """remarks of a (possibly parallel) build: per source file in order, Function Name opens a record"""
+    res, cur = {}, {}
+    for line in open(log, errors='replace'):
+        m = re.match(r'^(\S+?\.hip):\d+:\d+: remark: (.*?) \[-Rpass-analysis=kernel-resource-usage\]', line)
+        if not m:
+            continue
+        f, body = m.group(1), m.group(2).strip()
+        if body.startswith('Function Name:'):
+            cur[f] = res.setdefault((os.path.basename(f), body.split(':', 1)[1].strip()), [])
+        elif f in cur:
+            cur[f].append(body)
+    return res
+
+
+def main():
+    dirA, logA, dirB, logB = sys.argv[1:5]
+    with tempfile.TemporaryDirectory() as tmp:
+        A, B = {}, {}
+        for s in SRC:
+            for d, K in ((dirA, A), (dirB, B)):
+                for name, ins in kernels(os.path.join(d, s + '.o'), tmp).items():
+                    K[(s, name)] = ins
+    RA, RB = resources(logA), resources(logB)
+    onlyA, onlyB = sorted(set(A) - set(B)), sorted(set(B) - set(A))
+    print('code symbols: first build %d, second build %d, in both %d' % (len(A), len(B), len(set(A) & set(B))))
+    print('instructions compared: %d' % sum(len(A[k]) for k in set(A) & set(B)))
+    print('only in the first build (%d):' % len(onlyA))
+    for k in onlyA:
+        print('    %s  %s' % k)
+    print('only in the second build (%d):' % len(onlyB))
+    for k in onlyB:
+        print('    %s  %s' % k)
+    diff = [k for k in sorted(set(A) & set(B)) if A[k] != B[k]]
+    print('kernels whose instruction stream differs: %d' % len(diff))
+    for k in diff:
+        n = next((i for i, (x, y) in enumerate(zip(A[k], B[k])) if x != y), min(len(A[k]), len(B[k])))
+        print('    %s  %s: %d / %d instructions, first difference at %d' % (k[0], k[1], len(A[k]), len(B[k]), n))
+    ra = {k: v for k, v in RA.items() if k in RB}
+    rdiff = [k for k in sorted(ra) if RA[k] != RB[k]]
+    print('resource records: first build %d, second build %d; differing among the common %d: %d' % (len(RA), len(RB), len(ra), len(rdiff)))
+    for k in rdiff:
+        print('    %s %s\n      first:  %s\n      second: %s' % (k[0], k[1], '; '.join(RA[k]), '; '.join(RB[k])))
+    hist = collections.Counter(s for s, _ in A)
+    print('symbols per object (first build): ' + ', '.join('%s %d' % (s, hist[s]) for s in SRC))
+    return 1 if (diff or rdiff or onlyB) else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
