@@ -18,7 +18,7 @@ import pytest
 from babelbrain_amd import harness as H
 from babelbrain_amd import slab
 from babelbrain_amd._engine import HALO_STRESS, HALO_VELOCITY
-from tests.util import compare_runs, oracle_dt
+from tests.util import compare_runs, geometry_of, oracle_dt
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ def test_c1_full_size_against_oracle():
     assert a[0].shape == (128, 128, 128) and info['nt'] == 500
     out_h = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out_o = O.StaggeredFDTD_3D_with_relaxation(*a, **k)
-    worst = compare_runs(out_h, out_o, tol=1e-5)
+    worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
     assert out_o[2]['Pressure'].max() > 0 and out_h[0]['Pressure'].shape[0] == 104 * 104 * 103
     print('C1 128^3 x 500 steps: worst rel L2 vs oracle %.3e' % worst)
 
@@ -51,7 +51,7 @@ def test_c2_full_size_against_oracle():
     assert a[0].shape == (256, 256, 256) and info['nt'] == 2000 and len(a[1]) == 3 and a[1][1][2] > 0
     out_h = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out_o = O.StaggeredFDTD_3D_with_relaxation(*a, **k)
-    worst = compare_runs(out_h, out_o, tol=1e-5)
+    worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
     rms = out_o[2]['Pressure']
     inside = rms[128, 128, 150]              # behind the skull: the wave went through bone
     assert rms.max() > 0 and inside > 0
@@ -69,7 +69,7 @@ def test_c2_medium_at_320_cubed_against_oracle():
     assert a[0].shape == (320, 320, 320) and info['nt'] == 400
     out_h = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out_o = O.StaggeredFDTD_3D_with_relaxation(*a, **k)
-    worst = compare_runs(out_h, out_o, tol=1e-5)
+    worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
     assert out_o[2]['Pressure'].max() > 0
     print('C2 medium 320^3 x 400 steps: worst rel L2 vs oracle %.3e (oracle step loop %.1f s)' % (worst, out_o[-1]['stepLoopSeconds']))
 
@@ -89,7 +89,7 @@ def test_c3_full_size_against_oracle():
     assert out_o[2]['Pressure'].max() > 0 and np.count_nonzero(out_o[1]['Pressure']) > 1e6
     for variant in (0, 4):
         out_h = PropagationModel(kernelVariant=variant).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-        worst = compare_runs(out_h, out_o, tol=1e-5)
+        worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
         print('C3 512^3 x 140 steps, variant %d: worst rel L2 vs oracle %.3e (oracle step loop %.1f s)' % (variant, worst, out_o[-1]['stepLoopSeconds']))
         del out_h
 
@@ -109,7 +109,7 @@ def _reduced_against_oracle(config, N, steps):
     assert bone.sum() > 1e4 and rms[bone].max() > 0 and rms[brain].max() > 0, 'the wave should have gone through bone'
     for variant in (0, 2):
         out_h = PropagationModel(kernelVariant=variant).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-        worst = compare_runs(out_h, out_o, tol=1e-5)
+        worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
         print('%s at %s x %d steps, variant %d: worst rel L2 vs oracle %.3e' % (config, N, steps, variant, worst))
     return info, out_o
 
@@ -142,7 +142,7 @@ def test_c4_full_size_first_steps_against_oracle():
     assert a[0].shape == (512, 512, 1024) and info['tx'] == 'h317' and info['n_sources'] > 1e5
     out_h = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out_o = O.StaggeredFDTD_3D_with_relaxation(*a, **k)
-    worst = compare_runs(out_h, out_o, tol=1e-5)
+    worst = compare_runs(out_h, out_o, geometry=geometry_of(a, k))
     rms = out_o[2]['Pressure']
     assert rms[a[0] == 1].max() > 0 and np.count_nonzero(out_o[1]['Pressure']) > 1e6
     print('C4 512x512x1024 x 80 steps: worst rel L2 vs oracle %.3e (oracle step loop %.1f s)' % (worst, out_o[-1]['stepLoopSeconds']))

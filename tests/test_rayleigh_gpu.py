@@ -1,6 +1,8 @@
 """HIP Rayleigh integral (bfd_rayleigh_forward through babelbrain_amd.RayleighAndBHTE.ForwardSimple)
 against the float64 numpy oracle. Tolerance 1e-5 relative L2 (the north-star bar for field outputs):
 geometry and phase reduction are float64 on the device, so the observed error is ~1e-7."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -30,6 +32,114 @@ def test_forward_simple_matches_oracle(rings, N, kimag):
     e = max(rel_l2(got.real, ref.real), rel_l2(got.imag, ref.imag))
     assert e <= 1e-5, e
     print('M=%d N=%d: rel L2 %.2e, %.3f ms, %.2f Gpairs/s' % (M, N, e, ms, M * N / ms / 1e6))
+
+
+# ---- the six instantiations of the kernel (PPL = 1, 2, 4 field points per lane, with and without attenuation), point by point ----
+# Bound of |got_n - ref_n| / s_n in test_wide_templates_point_by_point: 4 x the largest ratio measured on the MI355X over its
+# 32 cases, 3.552e-7 (one source, attenuated; 3.2e-7 without attenuation, 1.6e-7 .. 2.0e-7 on 15 - 17 sources, 2.0e-8 .. 3.3e-8
+# on 511 - 1100). Inputs are seeded: the factor 4 only has to cover compiler and driver versions. Why the figure is plausible
+# (u = 2^-24 = 6.0e-8): per term one rounding each of the u0 dS product, the amplitude 1 / R, amplitude x cosine / sine and the
+# float32 result, the phase in revolutions rounded to float32 (2^-25 of a revolution = 1.9e-7 rad), the hardware sine and
+# cosine, and with attenuation exp(Im k R) on a float32 argument; the roundings of the float32 sub-sums of 16 average out
+# over many terms, which is why the ratio falls with the source count.
+RAYLEIGH_MEASURED = 3.552e-7
+RAYLEIGH_C = 4 * RAYLEIGH_MEASURED
+
+
+def _template_of(n_points):
+    """field points per lane the library picks for a launch of that many points (bfd_rayleigh.hip)"""
+    return 4 if n_points >= 1 << 20 else 2 if n_points >= 1 << 18 else 1
+
+
+@functools.lru_cache(maxsize=None)
+def _bowl_1mhz():
+    """F = 60 mm, aperture 55 mm, 24 rings: 1100 and more records, ring by ring from the apex (z = 0) outwards. The first 28
+    records (three rings, radius 3 mm) lie within 0.08 mm of the plane z = 0: a flat patch."""
+    pts, ds = H._bowl_points(60e-3, 55e-3, 24, 0.0)
+    assert len(ds) > 1100 and pts[:28, 2].max() < 0.08e-3
+    rng = np.random.default_rng(11)
+    u0 = (rng.normal(size=len(ds)) + 1j * rng.normal(size=len(ds))).astype(np.complex64)
+    return pts.astype(np.float32), ds.astype(np.float32), u0
+
+
+@functools.lru_cache(maxsize=None)
+def _field_points(N):
+    """N seeded field points and the indices held point by point. In launch order: a 32 x 32 plane z = 0.5 mm (one spatial
+    step of a 1 MHz grid) over the flat centre of the bowl, +-5 mm, the bowl's surface below it (nearest record 0.19 mm away); the
+    mid-field cloud of _case; 2048 points 0.25 m from the bowl (k R near 1000 rad at 1 MHz). The subset: the first 1024
+    points (the plane), the last 256 x PPL + 64 (the far points; the launch's last, partly filled workgroup and the one
+    before it), 4096 random ones."""
+    rng = np.random.default_rng(N)
+    g = (np.arange(32) - 15.5) * (10e-3 / 32)
+    X, Y = np.meshgrid(g, g, indexing='ij')
+    plane = np.stack([X.ravel(), Y.ravel(), np.full(X.size, 0.5e-3)], 1)
+    nfar = 2048
+    n = N - len(plane) - nfar
+    cloud = np.stack([rng.uniform(-40e-3, 40e-3, n), rng.uniform(-40e-3, 40e-3, n), rng.uniform(20e-3, 160e-3, n)], 1)
+    far = np.stack([rng.uniform(-20e-3, 20e-3, nfar), rng.uniform(-20e-3, 20e-3, nfar), rng.uniform(0.25, 0.26, nfar)], 1)
+    rf = np.concatenate([plane, cloud, far]).astype(np.float32)
+    tail = 256 * _template_of(N) + 64
+    sub = np.unique(np.concatenate([np.arange(1024), np.arange(N - tail, N), rng.integers(0, N, 4096)]))
+    assert rf.shape == (N, 3) and tail < nfar and N % (256 * _template_of(N)) != 0
+    return rf, sub
+
+
+def _term_scale(k, cen, ds, u0, rf):
+    """s_n = |k| / 2 pi  sum_m |u0_m ds_m| exp(Im k R_nm) / R_nm: the sum of the magnitudes of a point's terms (float64)"""
+    R = np.sqrt(((rf.astype(np.float64)[:, None, :] - cen.astype(np.float64)[None, :, :]) ** 2).sum(axis=2))
+    w = np.abs(u0.astype(np.complex128)) * ds.astype(np.float64)
+    return abs(k) / (2 * np.pi) * ((np.exp(k.imag * R) / R) @ w)
+
+
+def template_case(N, M, kimag):
+    """One launch of N points on the first M records of the bowl. Returns (values of the subset out of the large launch,
+    values of a launch of the subset alone, float64 oracle, term scale s_n)."""
+    import os
+    from babelbrain_amd import RayleighAndBHTE as R
+    # one device, one launch: points shared among several devices would reach narrower templates than _template_of says
+    assert R._devices is None and not os.environ.get('BABELFDTD_DEVICES')
+    cen, ds, u0 = (v[:M] for v in _bowl_1mhz())
+    rf, sub = _field_points(N)
+    k = complex(np.array(2 * np.pi * 1e6 / 1500.0 + 1j * kimag).astype(np.complex64))
+    big = R.ForwardSimple(k, cen, ds, u0, rf)
+    assert big.shape == (N,) and big.dtype == np.complex64
+    small = R.ForwardSimple(k, cen, ds, u0, rf[sub])
+    ref = RO.ForwardSimple(k, cen, ds, u0, rf[sub])
+    return big[sub], small, ref, _term_scale(k, cen, ds, u0, rf[sub])
+
+
+@pytest.mark.parametrize('M', [1, 15, 16, 17, 511, 512, 513, 1100])
+@pytest.mark.parametrize('kimag', [0.0, -4.5])
+@pytest.mark.parametrize('N', [(1 << 18) + 37, (1 << 20) + 1029])
+def test_wide_templates_point_by_point(N, kimag, M, monkeypatch):
+    """Point sets of 2^18 + 37 and 2^20 + 1029 points reach the kernels with 2 and 4 field points per lane (the suite's other
+    cases stay below 2^18 points: one per lane), with and without attenuation, on source counts at the edges of the kernel's
+    blocks (float32 sub-sums of 16, LDS blocks of 512). On a fixed subset of the points:
+    (i) the values out of the large launch equal, bit for bit, those of a launch of the subset alone (one point per lane):
+    a point's sum visits the sources in the same order with the same explicit fused multiply-adds in every template;
+    (ii) against the float64 oracle, per point: |got_n - ref_n| <= C s_n with s_n the sum of the magnitudes of the point's
+    terms (_term_scale), which bounds term by term what float32 trigonometry and amplitudes can cost -- a point in the near
+    field or in a node of the far field is held to its own scale, not to the norm of the whole array. C = RAYLEIGH_C =
+    1.42e-6 = 4 x 3.552e-7, the largest ratio measured on the MI355X over these 32 cases (one source, PPL = 2, attenuated).
+    A single term of M = 1100 equal ones dropped or doubled would move a point by 1 / M = 9.1e-4 of s_n: 640 times C (and
+    the ratio measured at M = 1100 is 2.0e-8)."""
+    from babelbrain_amd import RayleighAndBHTE as R
+    monkeypatch.delenv('BABELFDTD_DEVICES', raising=False)
+    R.set_devices(None)
+    ppl = _template_of(N)
+    got, alone, ref, s = template_case(N, M, kimag)
+    assert _template_of(len(alone)) == 1 and ppl == (2 if N < 1 << 20 else 4)
+    assert np.isfinite(got.view(np.float32)).all() and np.abs(ref).min() > 0
+    same = got.view(np.uint32) == alone.view(np.uint32)
+    assert same.all(), '%d of %d values differ between the PPL = %d launch and the PPL = 1 launch, first at subset position %d' % (
+        same.size - same.sum(), same.size, ppl, np.flatnonzero(~same)[0] // 2)
+    ratio = np.abs(got.astype(np.complex128) - ref) / s
+    worst = int(np.argmax(ratio))
+    print('N=%d (PPL=%d, ATT=%d) M=%d: max |err| / s_n = %.3e at subset position %d of %d; 1 / M = %.1e' % (
+        N, ppl, kimag != 0, M, ratio[worst], worst, len(ratio), 1.0 / M))
+    assert ratio[worst] <= RAYLEIGH_C, (ratio[worst], worst)
+    e = max(rel_l2(got.real, ref.real), rel_l2(got.imag, ref.imag))
+    assert e <= 1e-5, e
 
 
 def test_source_plane_matches_harness():
