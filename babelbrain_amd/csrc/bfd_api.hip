@@ -1231,9 +1231,6 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
     return 0;
 }
 
-// Build the run lists of the tiled kernels (bfd_kernels_v2.hip). Sub-tiles of 64 x 8 x 8 cells are
-// classified on the device; consecutive sub-tiles of one (bx,by) column with identical class merge into
-// runs that never cross a 32-plane chunk boundary. Variant 2: every sub-tile counts as solid (dense kernels).
 // where the ten compact arrays live (bfd_tiles::cssHosted); called when the list is built and again whenever the state buffers change hands
 // (choose_placement exchanges them at step 0, when everything is still zero)
 static void bind_compact_views(bfd_sim *s)
@@ -1248,33 +1245,18 @@ static void bind_compact_views(bfd_sim *s)
 static bool quiet_runs_wanted(const bfd_sim *s);
 static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid);
 
-static int build_tile_lists(bfd_sim *s)
+// The tile grid of one build: tx x ty columns of nsub sub-tiles (n in all) of SUB planes; a z-chunk, the longest run, is perChunk sub-tiles.
+// "boundary" sub-tiles hold the 2 first / 2 last planes of the slab (what a Z-neighbour reads): they form the
+// small part 1 of a split half-step; everything else is part 2. lowPlanes / hiStart delimit them in planes.
+struct TileGrid {
+    int tx, ty, nsub, n, SUB, perChunk, nChunks, nk, lowPlanes, hiStart;
+    bool subBnd(int q) const { return q * SUB < lowPlanes || std::min((q + 1) * SUB, nk) > hiStart; }
+};
+// Not a getter: it chooses the run length of this build and stores it in s->zchunk (bfd_sim keeps the choice; perChunk is derived from it).
+static TileGrid choose_tile_grid(bfd_sim *s)
 {
     int tx, ty, nsub; bfd_tile_grid(s->d, &tx, &ty, &nsub);
     const int n = tx * ty * nsub;
-    // a list rebuilt in the middle of a run (inputs set again at step > 0): the shear memory variables travel through the
-    // full-volume arrays
-    const bool carryShearMemory = s->step > 0 && s->tilesReady == false && s->tiles.shearR && s->tiles.nShear > 0;
-    const bool hadList = s->tiles.shearCells != nullptr, hadListR = s->tiles.shearR != nullptr, wasMerged = s->tiles.merged;
-    if (carryShearMemory) { bfd_launch_scatter_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
-    // the same for a compact solid state: its ten arrays are set aside with their list (the full-volume buffers may host the compact arrays
-    // themselves) and re-entered into the new list through one full-volume temporary, array by array, once that list exists
-    const bool carryCompact = s->step > 0 && s->d.cssRow && s->tiles.nShear > 0;
-    unsigned *oldCells = nullptr; float *oldComp = nullptr; const long oldN = s->tiles.nShear;
-    struct FreeOnExit { float **p; ~FreeOnExit() { if (*p) hipFree(*p); } } freeOldComp{&oldComp};       // also on the error returns below
-    if (carryCompact) {
-        float *src[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
-        BFD_HIP(hipMalloc((void **)&oldComp, 10 * (size_t)oldN * sizeof(float)));
-        for (int a = 0; a < 10; a++) BFD_HIP(hipMemcpyAsync(oldComp + (size_t)a * oldN, src[a], (size_t)oldN * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-        BFD_HIP(hipStreamSynchronize(s->stream));
-        oldCells = s->tiles.shearCells; s->tiles.shearCells = nullptr;       // released below, after the new list has taken the values over
-    }
-    s->sensEntValid = false;
-    s->d.cssRow = nullptr; s->d.cSxx = s->d.cSyy = s->d.cSxy = s->d.cSxz = s->d.cSyz = s->d.cRxx = s->d.cRyy = s->d.cRxy = s->d.cRxz = s->d.cRyz = nullptr;
-    dev_release(s, &s->tiles.cssRow); dev_release(s, &s->tiles.css); s->tiles.cssCap = 0; s->tiles.cssHosted = false;
-    dev_release(s, &s->tiles.runsAll); s->tiles.nAll = s->tiles.nAllB = 0;
-    dev_release(s, &s->tiles.runs); dev_release(s, &s->tiles.xmap); dev_release(s, &s->tiles.shearCells); dev_release(s, &s->tiles.shearCoef); dev_release(s, &s->tiles.shearR);    // lists of an earlier build
-    dev_release(s, &s->tiles.shearCodes); dev_release(s, &s->tiles.shearTab);
     const int SUB = bfd_tile_subz();
     // longest run one workgroup marches: 16 planes; 8 on small grids so that the launch still has a few thousand
     // workgroups (measured: 256^3 49 -> 58, 128^3 29 -> 46 Gvoxel-steps/s). 32 was best at 512^3 while the z-chunks of
@@ -1287,47 +1269,38 @@ static int build_tile_lists(bfd_sim *s)
     if (s->zchunk > bfd_tile_zchunk()) s->zchunk = bfd_tile_zchunk();
     const int perChunk = s->zchunk / SUB;
     const int nChunks = (nsub + perChunk - 1) / perChunk;
-    std::vector<int> flags(n, 1), mats(n, 0);
-    if (s->cfg.kernelVariant != 2) {
-        int *dflags = nullptr, *dmats = nullptr;
-        BFD_HIP(hipMalloc((void **)&dflags, n * sizeof(int)));
-        hipError_t e = hipMalloc((void **)&dmats, n * sizeof(int));
-        if (e == hipSuccess) {
-            bfd_launch_classify(s->d, s->stream, dflags, dmats);
-            e = hipMemcpyAsync(flags.data(), dflags, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(mats.data(), dmats, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        hipFree(dflags); if (dmats) hipFree(dmats);
-        if (e != hipSuccess) BFD_FAIL(-10, std::string("classify tiles: ") + hipGetErrorString(e));
-    }
-    bfd_tiles &T = s->tiles;
-    T.nMat = s->cfg.nMat;
-    // solid runs: normal and shear stresses in one kernel (stress_solid_merged), the sparse list keeps the cells with an edge between
-    // different solids. BFD_SOLID_MERGED=0 selects the two-kernel form (stress_solid + stress_shear_sparse over every solid cell).
-    T.merged = false;
-    if (const char *ev = getenv("BFD_SOLID_MERGED")) T.merged = atoi(ev) != 0;
-    if (s->step > 0 && hadList) T.merged = hadListR ? false : wasMerged;       // a list rebuilt in the middle of a run keeps the form it started with (where its shear memory variables live)
-    T.nFluid = T.nFluidB = T.nSolid = T.nSolidB = T.nSolidBP = T.nSolidIP = T.nFused = T.nLossless = T.nLossy = T.nSolidSub = T.nUni = T.nPml = T.nLean = T.nFusedSub = 0;
-    s->d.tilesX = tx; s->d.tilesY = ty;
-    // Every fluid sub-tile is LEAN (bit4): fluid cells keep a single copy of their identical normal stresses, whatever
-    // tile they sit in and whatever reads them (bfd_dev::cls)
-    if (s->cfg.kernelVariant != 2) for (int id = 0; id < n; id++) if (!(flags[id] & 1)) flags[id] |= 16;
-    // "boundary" sub-tiles hold the 2 first / 2 last planes of the slab (what a Z-neighbour reads): they form the
-    // small part 1 of a split half-step; everything else is part 2. lowPlanes / hiStart delimit them in planes.
     const int nkl = s->d.nk;
     const int lowPlanes = std::min(SUB, nkl);
     const int hiStart = std::max(((nkl - 2) / SUB) * SUB, lowPlanes);
-    auto subBnd = [&](int q) { return q * SUB < lowPlanes || std::min((q + 1) * SUB, nkl) > hiStart; };
-    std::vector<int4> lists[5];      // fluid boundary, fluid interior, solid boundary, solid interior, fused fluid
-    std::vector<int4> listsAll[2];   // every run of the two-kernel path in list order: boundary, interior (bfd_tiles::runsAll)
-    std::vector<char> taken((size_t)n, 0);
-    // Runs of the fused time step (variant 4, bfd_kernels_fused.hip): 64 x 24 cells = three tiles of this grid in y, a z-run of
-    // 2 .. fusedSub sub-tiles. A sub-tile qualifies (bit5) when it is fluid, has nothing of the absorbing layer or the domain
-    // edge within 2 cells (bit6), is not a boundary sub-tile of the slab, and the sources are of velocity type. Per column and
-    // z-chunk the rows are scanned upwards: where three consecutive tile rows qualify over a z-stretch they form a run and the
-    // scan moves on by three rows. A run is UNI when every sub-tile is (one material in the grown regions) and lossy when a
-    // cell of a grown region relaxes (bit7); stretches are cut where that class changes (a single sub-tile joins its neighbour).
+    return {tx, ty, nsub, n, SUB, perChunk, nChunks, nkl, lowPlanes, hiStart};
+}
+
+// class flags and material of every sub-tile, from the device
+static int fetch_tile_classes(bfd_sim *s, int n, std::vector<int> &flags, std::vector<int> &mats)
+{
+    int *dflags = nullptr, *dmats = nullptr;
+    BFD_HIP(hipMalloc((void **)&dflags, n * sizeof(int)));
+    hipError_t e = hipMalloc((void **)&dmats, n * sizeof(int));
+    if (e == hipSuccess) {
+        bfd_launch_classify(s->d, s->stream, dflags, dmats);
+        e = hipMemcpyAsync(flags.data(), dflags, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(mats.data(), dmats, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    hipFree(dflags); if (dmats) hipFree(dmats);
+    if (e != hipSuccess) BFD_FAIL(-10, std::string("classify tiles: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// Runs of the fused time step (variant 4, bfd_kernels_fused.hip): 64 x 24 cells = three tiles of this grid in y, a z-run of
+// 2 .. fusedSub sub-tiles. A sub-tile qualifies (bit5) when it is fluid, has nothing of the absorbing layer or the domain
+// edge within 2 cells (bit6), is not a boundary sub-tile of the slab, and the sources are of velocity type. Per column and
+// z-chunk the rows are scanned upwards: where three consecutive tile rows qualify over a z-stretch they form a run and the
+// scan moves on by three rows. A run is UNI when every sub-tile is (one material in the grown regions) and lossy when a
+// cell of a grown region relaxes (bit7); stretches are cut where that class changes (a single sub-tile joins its neighbour).
+static void form_fused_runs(bfd_sim *s, const TileGrid &G, std::vector<int> &flags, const std::vector<int> &mats, std::vector<char> &taken, std::vector<int4> &fused)
+{
+    const int tx = G.tx, ty = G.ty, nsub = G.nsub, SUB = G.SUB;
     const int fusedSub = 32 / SUB;
     struct FusedRun { int bx, by, q0, q1, cls, mat; };
     std::vector<FusedRun> fruns;
@@ -1335,7 +1308,7 @@ static int build_tile_lists(bfd_sim *s)
         const int FRW = bfd_fused_rows() / 8;
         const size_t layer = (size_t)tx * ty;
         for (int q = 0; q < nsub; q++)
-            for (size_t txy = 0; txy < layer; txy++) { int &f = flags[(size_t)q * layer + txy]; if (!(f & 1) && !(f & 64) && !(f & 256) && !subBnd(q)) f |= 32; }
+            for (size_t txy = 0; txy < layer; txy++) { int &f = flags[(size_t)q * layer + txy]; if (!(f & 1) && !(f & 64) && !(f & 256) && !G.subBnd(q)) f |= 32; }
         for (int bx = 0; bx < tx; bx++)
             for (int qc = 0; qc < nsub; qc += fusedSub) {
                 const int qe = std::min(qc + fusedSub, nsub), L = qe - qc;
@@ -1380,7 +1353,7 @@ static int build_tile_lists(bfd_sim *s)
                             for (const auto &rq : seg) {
                                 fruns.push_back({bx, by, qc + rq[0], qc + rq[1], rq[2], mats[(size_t)(qc + rq[0]) * layer + (size_t)by * tx + bx]});
                                 for (int q = qc + rq[0]; q < qc + rq[1]; q++)
-                                    for (int r = 0; r < FRW; r++) { taken[(size_t)q * layer + (size_t)(by + r) * tx + bx] = 1; T.nFusedSub++; }
+                                    for (int r = 0; r < FRW; r++) { taken[(size_t)q * layer + (size_t)(by + r) * tx + bx] = 1; s->tiles.nFusedSub++; }
                             }
                         }
                         a = b;
@@ -1394,9 +1367,17 @@ static int build_tile_lists(bfd_sim *s)
         for (const auto &r : fruns) {
             int4 run; run.x = r.by * tx + r.bx; run.y = (r.q0 * SUB) | (std::min(r.q1 * SUB, s->d.nk) << 16);
             run.z = 32 | 16 | ((r.cls & 2) ? 2 : 0) | ((r.cls & 1) ? 4 : 0); run.w = r.mat;
-            lists[4].push_back(run);
+            fused.push_back(run);
         }
     }
+}
+
+// The runs of the two-kernel path: fluid boundary / interior (lists[0], [1]), solid boundary / interior (lists[2], [3]) and all of them in list
+// order (listsAll: boundary, interior); sub-tiles the fused runs have taken are left out.
+static void form_two_kernel_runs(bfd_sim *s, const TileGrid &G, const std::vector<int> &flags, const std::vector<int> &mats, std::vector<char> &taken, std::vector<int4> *lists, std::vector<int4> *listsAll)
+{
+    const int tx = G.tx, ty = G.ty, nsub = G.nsub, SUB = G.SUB, perChunk = G.perChunk, nChunks = G.nChunks;
+    bfd_tiles &T = s->tiles;
     // List order = what is in flight together. The launch gives XCD e the e-th contiguous eighth of the list
     // (remap_block) and an XCD keeps ~100 workgroups in flight, all marching in z at the same pace; a halo line
     // (128 B for 2 or 3 floats of a neighbour tile's row) is an L2 hit only if that neighbour is in flight on the
@@ -1424,43 +1405,339 @@ static int build_tile_lists(bfd_sim *s)
     }
     for (const auto &pc : seq) {
         const int txy = pc.first, c = pc.second;
-            const int sb = c * perChunk, se0 = std::min(sb + perChunk, nsub);
-            int q = sb;
-            while (q < se0) {
-                if (taken[(size_t)q * tx * ty + txy]) { q++; continue; }
-                const int f = flags[(size_t)q * tx * ty + txy], m = mats[(size_t)q * tx * ty + txy];
-                const bool solid = f & 1;
-                const bool bnd = subBnd(q);
-                const int se = se0;
-                int r = q + 1, pmlAny = f & 8;
-                while (r < se) {
-                    const int f2 = flags[(size_t)r * tx * ty + txy], m2 = mats[(size_t)r * tx * ty + txy];
-                    if (subBnd(r) != bnd || taken[(size_t)r * tx * ty + txy]) break;
-                    if (solid ? !(f2 & 1) : (((f2 ^ f) & ~(32 | 128 | 256)) != 0 || ((f & 4) && m2 != m))) break;
-                    pmlAny |= f2 & 8;
-                    r++;
-                }
-                const int kbeg = q * SUB, kend = std::min(r * SUB, s->d.nk);
-                // solid runs: bit0 + bit3 (a sub-tile of the run touches the absorbing layer)
-                int4 run; run.x = txy; run.y = kbeg | (kend << 16); run.z = solid ? (1 | pmlAny) : (f & ~(32 | 128 | 256)); run.w = m;
-                lists[(solid ? 2 : 0) + (bnd ? 0 : 1)].push_back(run);
-                listsAll[bnd ? 0 : 1].push_back(run);
-                for (int u = q; u < r; u++) {
-                    taken[(size_t)u * tx * ty + txy] = 1;
-                    if (solid) T.nSolidSub++;
-                    else { if (f & 2) T.nLossy++; else T.nLossless++; if (f & 4) T.nUni++; if (f & 8) T.nPml++; if (f & 16) T.nLean++; }
-                }
-                q = r;
+        const int sb = c * perChunk, se0 = std::min(sb + perChunk, nsub);
+        int q = sb;
+        while (q < se0) {
+            if (taken[(size_t)q * tx * ty + txy]) { q++; continue; }
+            const int f = flags[(size_t)q * tx * ty + txy], m = mats[(size_t)q * tx * ty + txy];
+            const bool solid = f & 1;
+            const bool bnd = G.subBnd(q);
+            int r = q + 1, pmlAny = f & 8;
+            while (r < se0) {
+                const int f2 = flags[(size_t)r * tx * ty + txy], m2 = mats[(size_t)r * tx * ty + txy];
+                if (G.subBnd(r) != bnd || taken[(size_t)r * tx * ty + txy]) break;
+                if (solid ? !(f2 & 1) : (((f2 ^ f) & ~(32 | 128 | 256)) != 0 || ((f & 4) && m2 != m))) break;
+                pmlAny |= f2 & 8;
+                r++;
             }
+            const int kbeg = q * SUB, kend = std::min(r * SUB, s->d.nk);
+            // solid runs: bit0 + bit3 (a sub-tile of the run touches the absorbing layer)
+            int4 run; run.x = txy; run.y = kbeg | (kend << 16); run.z = solid ? (1 | pmlAny) : (f & ~(32 | 128 | 256)); run.w = m;
+            lists[(solid ? 2 : 0) + (bnd ? 0 : 1)].push_back(run);
+            listsAll[bnd ? 0 : 1].push_back(run);
+            for (int u = q; u < r; u++) {
+                taken[(size_t)u * tx * ty + txy] = 1;
+                if (solid) T.nSolidSub++;
+                else { if (f & 2) T.nLossy++; else T.nLossless++; if (f & 4) T.nUni++; if (f & 8) T.nPml++; if (f & 16) T.nLean++; }
+            }
+            q = r;
         }
-    // solid runs that touch the absorbing layer go to the two ends of the solid list: [boundary: PML | plain][interior: plain | PML]
-    {
-        auto isPml = [](const int4 &r) { return (r.z & 8) != 0; };
-        auto mid = std::stable_partition(lists[2].begin(), lists[2].end(), isPml);
-        T.nSolidBP = (int)(mid - lists[2].begin());
-        auto mid2 = std::stable_partition(lists[3].begin(), lists[3].end(), [&](const int4 &r) { return !isPml(r); });
-        T.nSolidIP = (int)(lists[3].end() - mid2);
     }
+    // solid runs that touch the absorbing layer go to the two ends of the solid list: [boundary: PML | plain][interior: plain | PML]
+    auto isPml = [](const int4 &r) { return (r.z & 8) != 0; };
+    auto mid = std::stable_partition(lists[2].begin(), lists[2].end(), isPml);
+    T.nSolidBP = (int)(mid - lists[2].begin());
+    auto mid2 = std::stable_partition(lists[3].begin(), lists[3].end(), [&](const int4 &r) { return !isPml(r); });
+    T.nSolidIP = (int)(lists[3].end() - mid2);
+}
+
+// Cost-balanced block -> run maps (experiment, BFD_XCD_BALANCE=1; default off). A launch's blocks go to the 8 XCDs round-robin and every
+// XCD works through its own blocks at its own pace (-DBFD_EXP_XCD_CLOCK build: block b always runs on XCD (x0 + b) mod 8). With equal
+// COUNTS per XCD (remap_block) the XCD that holds the short boundary runs is idle for the last fifth of every fluid launch and the bands
+// with more tissue finish last. Here the contiguous parts of the list are cut by estimated cost instead (planes + prologue, weighted by
+// the bytes per cell of the run's class), the launch gets 8 x (longest part) blocks and a block beyond its part returns at once.
+// Measured: the ends of the XCDs move together (spread 19 % -> 13 % of a launch) and the step time does not -- C3 +1.2 %, shear medium
+// -0.4 %, other weightings +-2 % either way: an XCD that runs dry leaves its share of the memory system to the others.
+// profiles/r4/xcd_balance.txt.
+static int build_balance_maps(bfd_sim *s, const std::vector<int4> &all)
+{
+    bfd_tiles &T = s->tiles;
+    bool on = false;
+    if (const char *ev = getenv("BFD_XCD_BALANCE")) on = atoi(ev) != 0 && s->cfg.kernelVariant != 2 && s->cfg.kernelVariant != 1;
+    memset(s->tiles.xmapH, 0, sizeof s->tiles.xmapH);
+    if (on) {
+        const double wPml = 0.25, wLossy = 8, wMulti = 2, wRun = 2.0;
+        // cost of run r for kernel class c: 0 fluid stress, 1 fluid velocity, 2 solid stress, 3 solid velocity
+        auto cost = [&](const int4 &r, int c) {
+            const double planes = (double)((r.y >> 16) - (r.y & 0xFFFF)) + wRun;
+            const int f = r.z;
+            double w;
+            if (c == 0) w = 20 + ((f & 2) ? wLossy : 0) + ((f & 4) ? 0 : wMulti);
+            else if (c == 1) w = 36 + ((f & 4) ? 0 : wMulti);
+            else w = 40;
+            if (f & 8) w *= 1.0 + wPml;
+            return planes * w;
+        };
+        auto make = [&](int m, size_t a0, size_t a1, int c) {
+            int *seg = s->tiles.xmapH[m];
+            const size_t n = a1 > a0 ? a1 - a0 : 0;
+            std::vector<double> cum(n + 1, 0.0);
+            for (size_t i = 0; i < n; i++) cum[i + 1] = cum[i] + cost(all[a0 + i], c);
+            int maxcnt = 0;
+            seg[0] = 0;
+            for (int x = 1; x <= 8; x++) {
+                const double target = cum[n] * x / 8.0;
+                size_t j = std::lower_bound(cum.begin(), cum.end(), target) - cum.begin();
+                if (j > n || x == 8) j = n;
+                if ((int)j < seg[x - 1]) j = seg[x - 1];
+                seg[x] = (int)j;
+                maxcnt = std::max(maxcnt, seg[x] - seg[x - 1]);
+            }
+            seg[9] = std::max(maxcnt, 1);
+        };
+        const size_t F = T.nFluid, FB = T.nFluidB, S0 = F, SB = T.nSolidB, SN = T.nSolid;
+        for (int c = 0; c < 2; c++) {            // fluid stress (c = 0), fluid velocity (c = 1): parts 0, 1, 2
+            const int m = c == 0 ? BFD_XM_SF : BFD_XM_VF;
+            make(m + 0, 0, F, c); make(m + 1, 0, FB, c); make(m + 2, FB, F, c);
+        }
+        make(BFD_XM_SS + 0, S0, S0 + SN, 2); make(BFD_XM_SS + 1, S0, S0 + SB, 2); make(BFD_XM_SS + 2, S0 + SB, S0 + SN, 2);
+        const size_t bp = T.nSolidBP, ip = T.nSolidIP;          // solid list = [boundary: PML | plain][interior: plain | PML]
+        make(BFD_XM_VS + 0, S0 + bp, S0 + SN - ip, 3); make(BFD_XM_VS + 1, S0 + bp, S0 + SB, 3); make(BFD_XM_VS + 2, S0 + SB, S0 + SN - ip, 3);
+        make(BFD_XM_VSP_LO, S0, S0 + bp, 3); make(BFD_XM_VSP_HI, S0 + SN - ip, S0 + SN, 3);
+        make(BFD_XM_FUSED, S0 + SN, S0 + SN + T.nFused, 0);
+        const int rc = dev_alloc(s, &s->tiles.xmap, (size_t)BFD_XMAP_COUNT * 10, false);
+        if (rc) return rc;
+        BFD_HIP(hipMemcpy(s->tiles.xmap, s->tiles.xmapH, sizeof s->tiles.xmapH, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// sparse shear list: cells with a solid centre, ascending index (hostCells), in list order on the device, + their edge coefficients;
+// decides whether the solid state is compact
+static int build_shear_list(bfd_sim *s, const TileGrid &G, int *countOut, bool *compactOut, std::vector<unsigned> &hostCells)
+{
+    unsigned char *flag = nullptr; unsigned *sel = nullptr; int *dcount = nullptr; void *work = nullptr;
+    hipError_t e = hipMalloc((void **)&flag, s->nloc);
+    if (e == hipSuccess) e = hipMalloc((void **)&sel, s->nloc * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMalloc((void **)&dcount, sizeof(int));
+    int count = 0, rc = 0;
+    if (e == hipSuccess) {
+        bfd_launch_mark_solid(s->d, s->stream, flag, (long)s->nloc);
+        size_t wbytes = 0;
+        hipcub::CountingInputIterator<unsigned> ids(0);
+        e = hipcub::DeviceSelect::Flagged(nullptr, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
+        if (e == hipSuccess) e = hipMalloc(&work, std::max<size_t>(wbytes, 1));
+        if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged(work, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    }
+    hostCells.resize((size_t)count);
+    if (e == hipSuccess && count) e = hipMemcpy(hostCells.data(), sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost);
+    // list order (bfd_kernels_v2.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
+    // touched one band-plane earlier instead of one whole plane of the shell
+    if (e == hipSuccess && count > 0) {
+        unsigned long long *k0 = nullptr, *k1 = nullptr; unsigned *v1 = nullptr; void *w2 = nullptr; size_t w2b = 0;
+        e = hipMalloc((void **)&k0, (size_t)count * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&k1, (size_t)count * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&v1, (size_t)count * 4);
+        if (e == hipSuccess) {
+            bfd_launch_shear_order_keys(s->d, s->stream, sel, k0, count, G.lowPlanes, G.hiStart);
+            e = hipcub::DeviceRadixSort::SortPairs(nullptr, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
+        }
+        if (e == hipSuccess) e = hipMalloc(&w2, std::max<size_t>(w2b, 1));
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(w2, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(sel, v1, (size_t)count * 4, hipMemcpyDeviceToDevice, s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        if (k0) hipFree(k0); if (k1) hipFree(k1); if (v1) hipFree(v1); if (w2) hipFree(w2);
+    }
+    // Compact solid state (bfd_dev::cssRow): Sxx, Syy, the shear stresses and the five memory variables Rxx, Ryy, Rxy, Rxz, Ryz of the listed cells in
+    // list order. Needs the row-contiguous list order. In a Z-slab the ghost planes of Sxz / Syz stay in the
+    // full-volume arrays (the sparse kernel keeps full-volume copies of the planes a neighbour reads, the velocity kernel takes ghost planes from
+    // there): the halo exchange is unchanged. BFD_COMPACT_SOLID=0 keeps the full-volume arrays.
+    bool compact = count > 0 && s->d.N1 <= 4095;
+    if (const char *ev = getenv("BFD_COMPACT_SOLID")) compact = compact && atoi(ev) != 0;
+    if (e == hipSuccess) {
+        rc = dev_alloc(s, &s->tiles.shearCells, (size_t)std::max(count, 1), false);
+        if (!rc) rc = dev_alloc(s, &s->tiles.shearCoef, 6 * (size_t)std::max(count, 1), false);
+        if (!rc && !compact) rc = dev_alloc(s, &s->tiles.shearR, 3 * (size_t)std::max(count, 1), true);      // lists are built at step 0: the memory variables start at zero (compact form: they are among the compact arrays)
+        if (!rc && count) e = hipMemcpyAsync(s->tiles.shearCells, sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s->stream);
+        if (!rc) rc = dev_alloc(s, &s->tiles.shearCodes, (size_t)std::max(count, 1), false);
+        if (!rc) rc = dev_alloc(s, &s->tiles.shearTab, 8 * (size_t)s->cfg.nMat, false);
+        if (!rc && e == hipSuccess) bfd_launch_shear_coefficients(s->d, s->stream, s->tiles.shearCells, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.shearTab, s->cfg.nMat, count);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    }
+    if (flag) hipFree(flag); if (sel) hipFree(sel); if (dcount) hipFree(dcount); if (work) hipFree(work);
+    if (e != hipSuccess) BFD_FAIL(-10, std::string("shear list: ") + hipGetErrorString(e));
+    if (rc) return rc;
+    s->tiles.nShear = count;
+    if (s->step > 0 && s->tiles.shearR) { bfd_launch_gather_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
+    *countOut = count; *compactOut = compact;
+    return 0;
+}
+
+// compact solid state: the row table, the ten arrays (hosted in the full-volume buffers or in a block of their own) and the combined run list
+static int setup_compact_state(bfd_sim *s, const TileGrid &G, int count, const std::vector<int4> *listsAll)
+{
+    const int stride = G.tx + 1;
+    int rc = dev_alloc(s, &s->tiles.cssRow, (size_t)(s->d.nk + 4) * s->d.N2 * stride, false);
+    // the compact arrays live inside the full-volume buffers of their fields when the listed cells fit between the planes a Z-neighbour
+    // exchanges (local planes 0, 1 and nk-2, nk-1 of Sxz / Syz travel: allocation planes 4 .. nk-1 are free); BFD_COMPACT_HOSTED=0 or
+    // too many solid cells: one block of their own
+    bool hosted = (size_t)count <= (size_t)std::max(s->d.nk - 4, 0) * s->d.plane;
+    if (const char *ev = getenv("BFD_COMPACT_HOSTED")) hosted = hosted && atoi(ev) != 0;
+    if (!rc && !hosted) rc = dev_alloc(s, &s->tiles.css, 10 * (size_t)count, true);
+    if (rc) return rc;
+    s->tiles.cssCap = count; s->tiles.cssHosted = hosted;
+    bfd_launch_css_row_table(s->d, s->stream, s->tiles.shearCells, count, s->tiles.cssRow, stride, G.lowPlanes, G.hiStart);
+    s->d.cssRow = s->tiles.cssRow; s->d.cssStride = stride;
+    bind_compact_views(s);
+    BFD_HIP(hipStreamSynchronize(s->stream));
+    std::vector<int4> ra(listsAll[0]);
+    ra.insert(ra.end(), listsAll[1].begin(), listsAll[1].end());
+    rc = dev_alloc(s, &s->tiles.runsAll, ra.size(), false);
+    if (rc) return rc;
+    BFD_HIP(hipMemcpy(s->tiles.runsAll, ra.data(), ra.size() * sizeof(int4), hipMemcpyHostToDevice));
+    s->tiles.nAllB = (int)listsAll[0].size(); s->tiles.nAll = (int)ra.size();
+    return 0;
+}
+
+// a compact state set aside before a rebuild in the middle of a run: the values of the old list into the new one (or, should the new state not be compact, into the full-volume arrays)
+static int carry_compact_in(bfd_sim *s, int count, const unsigned *oldCells, long oldN, const float *oldComp)
+{
+    float *tmp = nullptr;
+    const size_t g = 2 * (size_t)s->d.plane;
+    float *newComp[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
+    float *full[10] = {s->d.Sxx, s->d.Syy, s->d.Sxy, s->d.Sxz, s->d.Syz, s->d.Rxx, s->d.Ryy, s->d.Rxy, s->d.Rxz, s->d.Ryz};
+    hipError_t e2 = s->d.cssRow ? malloc_or_release_cache((void **)&tmp, s->nalloc * sizeof(float)) : hipSuccess;
+    // the new state is not compact (no solid cell left, or the form was switched off): the full-volume arrays take over, and the owned planes
+    // of buffers that hosted compact arrays hold list-ordered values, not fields: cleared before the old values are scattered into them
+    for (int a = 0; a < 10 && e2 == hipSuccess && !s->d.cssRow; a++) e2 = hipMemsetAsync(full[a], 0, s->nloc * sizeof(float), s->stream);
+    for (int a = 0; a < 10 && e2 == hipSuccess; a++) {
+        if (s->d.cssRow) {
+            e2 = hipMemsetAsync(tmp, 0, s->nalloc * sizeof(float), s->stream);
+            bfd_launch_css_scatter(s->stream, oldCells, oldN, oldComp + (size_t)a * oldN, tmp + g);
+            bfd_launch_css_gather(s->stream, s->tiles.shearCells, count, tmp + g, newComp[a]);
+        } else bfd_launch_css_scatter(s->stream, oldCells, oldN, oldComp + (size_t)a * oldN, full[a]);
+    }
+    if (e2 == hipSuccess) e2 = hipStreamSynchronize(s->stream);
+    if (tmp) hipFree(tmp);
+    if (e2 != hipSuccess) BFD_FAIL(-10, std::string("compact solid state, list rebuilt in the middle of a run: ") + hipGetErrorString(e2));
+    if (!s->d.cssRow && s->tiles.shearR) { bfd_launch_gather_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
+    return 0;
+}
+
+// algorithmic bytes per launch and kernel class (DESIGN.md "Kernels": per-cell byte tables of the tile classes):
+// what each kernel has to move once per half-step if every value were fetched exactly once -- float32 fields 4 B,
+// material ids 2 B; absorbing-layer memory variables, tables and halo re-reads excluded
+static int account_algorithmic_bytes(bfd_sim *s, int tx, const std::vector<int4> &all)
+{
+    bfd_tiles &T = s->tiles;
+    double (*B)[BFD_K_COUNT] = s->algBytes;
+    memset(s->algBytes, 0, sizeof s->algBytes);
+    const int N1 = s->d.N1, N2 = s->d.N2, N3 = s->d.N3, ND = s->d.ND, k0g = s->d.k0;
+    // class counts over the cells of the solid runs (fluid / solid centre, with / without memory variables, active edges)
+    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+    if (T.nSolid && s->cfg.kernelVariant != 2) {
+        unsigned long long *dc = nullptr;
+        BFD_HIP(hipMalloc((void **)&dc, sizeof cnt));
+        hipMemsetAsync(dc, 0, sizeof cnt, s->stream);
+        bfd_launch_count_solid_cells(s->d, s->stream, s->tiles.runs + T.nFluid, T.nSolid, dc);
+        hipMemcpyAsync(cnt, dc, sizeof cnt, hipMemcpyDeviceToHost, s->stream);
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        hipFree(dc);
+        if (e != hipSuccess) BFD_FAIL(-10, std::string("solid cell counts: ") + hipGetErrorString(e));
+    }
+    auto overlap = [](int a, int b, int lo, int hi) { return (double)std::max(0, std::min(b, hi) - std::max(a, lo)); };
+    const bool pairAcc = pair_engine(s, quiet_runs_wanted(s), T.nFluid);      // the predicate the launches follow (pairing_step)
+    for (size_t r = 0; r < all.size(); r++) {
+        const int4 &run = all[r];
+        const int bx = run.x % tx, by = run.x / tx, kb = run.y & 0xFFFF, ke = run.y >> 16, f = run.z;
+        const int xa = bx * 64, xb = std::min(xa + 64, N1), ya = by * 8, yb = std::min(ya + 8, N2);
+        const double cells = (double)(xb - xa) * (yb - ya) * (ke - kb);
+        const double inner = overlap(xa, xb, ND, N1 - ND) * overlap(ya, yb, ND, N2 - ND) * overlap(k0g + kb, k0g + ke, ND, N3 - ND);
+        const bool fusedRun = r >= (size_t)(T.nFluid + T.nSolid);
+        if (fusedRun) {          // 64 x 24 cells per plane, all outside the absorbing layer: V, Szz (Rzz) read and written once per step (+ ids)
+            const double fc = 64.0 * bfd_fused_rows() * (ke - kb);
+            const double b = 32.0 + ((f & 2) ? 8.0 : 0.0) + ((f & 4) ? 0.0 : 2.0);
+            B[0][BFD_K_FUSED] += b * fc; B[1][BFD_K_FUSED] += b * fc + 8.0 * fc;
+        } else if (r < (size_t)T.nFluid) {
+            const bool lossy = f & 2, uni = f & 4, single = (f & 16) != 0;
+            double bs = 12.0 + 8.0 + (lossy ? 8.0 : 0.0) + (uni ? 0.0 : 2.0);
+            if (!single) bs += 8.0 + (lossy ? 8.0 : 0.0);
+            const double bv = 4.0 + 24.0 + (uni ? 0.0 : 2.0);
+            for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_FLUID] += bs * cells; B[a][BFD_K_VELOCITY_FLUID] += bv * cells; }
+            // Pressure sum read and written: by velocity_fluid in every accumulating step, or (paired accumulation) by stress_fluid in
+            // every second one: 4 B per launch averaged over a step pair
+            if (pairAcc) B[1][BFD_K_STRESS_FLUID] += 4.0 * inner; else B[1][BFD_K_VELOCITY_FLUID] += 8.0 * inner;
+        } else if (s->cfg.kernelVariant == 2) {     // dense: V + 6 S + 6 R read, 6 S + 6 R written, id; 6 S + V read, V written, id
+            for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_SOLID] += 110.0 * cells; B[a][BFD_K_VELOCITY_SOLID] += 50.0 * cells + (a ? 8.0 * inner : 0.0); }
+        } else {                                    // class-predicated solid kernels: per-cell terms come from the class counts below
+            for (int a = 0; a < 2; a++) B[a][BFD_K_VELOCITY_SOLID] += (a ? 8.0 * inner : 0.0);
+        }
+    }
+    if (T.nSolid && s->cfg.kernelVariant != 2) {
+        // stress: V 12 + id 2 + class 1, + Szz r/w 8 (+ Rzz r/w 8) at a fluid cell, + 3 S r/w 24 + 3 R r/w 24 at a solid one
+        // (a reflector cell: 48 B of zero stores); velocity: V r/w 24 + ids 2 + class 1 + Szz 4, + Sxx, Syy 8 at a solid cell,
+        // + 4 per active shear edge
+        const double nF0 = (double)cnt[0], nF1 = (double)cnt[1], nS = (double)cnt[2] + (double)cnt[3], nE = (double)cnt[4], nR = (double)cnt[5];
+        const double all = nF0 + nF1 + nS + nR;
+        const double bs = 15.0 * all + 8.0 * nF0 + 16.0 * nF1 + 48.0 * nS + 48.0 * nR;
+        const double bv = 31.0 * all + 8.0 * (nS + nR) + 4.0 * nE;
+        // compact solid state: the fluid kernel takes Szz / Rzz of the solid runs too (V 12 + id 2, + Szz r/w 8 (+ Rzz r/w 8); no class byte), the
+        // sparse kernel Sxx, Syy, Rxx, Ryy of its cells (+ 32 + id 2 per listed cell, below)
+        const double bsf = 14.0 * all + 8.0 * nF0 + 16.0 * nF1 + 16.0 * nS + 8.0 * nR;
+        for (int a = 0; a < 2; a++) { if (s->d.cssRow) B[a][BFD_K_STRESS_FLUID] += bsf; else B[a][BFD_K_STRESS_SOLID] += bs; B[a][BFD_K_VELOCITY_SOLID] += bv; }
+    }
+    if (s->tiles.nShear) {       // sparse shear: cell index + 6 coefficients + V of the cell + read-modify-write of S and R per active edge
+        unsigned long long *dc = nullptr, hc[2] = {0, 0};
+        BFD_HIP(hipMalloc((void **)&dc, sizeof hc));
+        hipMemsetAsync(dc, 0, sizeof hc, s->stream);
+        hipLaunchKernelGGL(count_active_edges, dim3(grid_for(s->tiles.nShear)), dim3(256), 0, s->stream, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.nShear, dc);
+        hipMemcpyAsync(hc, dc, sizeof hc, hipMemcpyDeviceToHost, s->stream);
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        hipFree(dc);
+        if (e != hipSuccess) BFD_FAIL(-10, std::string("shear edge count: ") + hipGetErrorString(e));
+        s->tiles.nShearExplicit = (long)hc[1];
+        // per listed cell: index 4 + edge codes 4 + V 12; per edge with explicit coefficients 8; per active edge S and R r/w 16; compact solid
+        // state: + Sxx, Syy, Rxx, Ryy r/w 32 (+ the cell's id 2 when it does not fit the code word's fourth byte)
+        const double perCell = s->d.cssRow ? (s->cfg.nMat <= 255 ? 52.0 : 54.0) : 20.0;
+        for (int a = 0; a < 2; a++) B[a][BFD_K_STRESS_SHEAR] = perCell * (double)s->tiles.nShear + 8.0 * (double)hc[1] + 16.0 * (double)hc[0];
+    }
+    return 0;
+}
+
+// Build the run lists of the tiled kernels (bfd_kernels_v2.hip). Sub-tiles of 64 x 8 x 8 cells are
+// classified on the device; consecutive sub-tiles of one (bx,by) column with identical class merge into
+// runs that never cross a 32-plane chunk boundary. Variant 2: every sub-tile counts as solid (dense kernels).
+static int build_tile_lists(bfd_sim *s)
+{
+    // a list rebuilt in the middle of a run (inputs set again at step > 0): the shear memory variables travel through the
+    // full-volume arrays
+    const bool carryShearMemory = s->step > 0 && s->tilesReady == false && s->tiles.shearR && s->tiles.nShear > 0;
+    if (carryShearMemory) { bfd_launch_scatter_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
+    // the same for a compact solid state: its ten arrays are set aside with their list (the full-volume buffers may host the compact arrays
+    // themselves) and re-entered into the new list through one full-volume temporary, array by array, once that list exists
+    const bool carryCompact = s->step > 0 && s->d.cssRow && s->tiles.nShear > 0;
+    unsigned *oldCells = nullptr; float *oldComp = nullptr; const long oldN = s->tiles.nShear;
+    struct FreeOnExit { float **p; ~FreeOnExit() { if (*p) hipFree(*p); } } freeOldComp{&oldComp};       // also on the error returns below
+    if (carryCompact) {
+        float *src[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
+        BFD_HIP(hipMalloc((void **)&oldComp, 10 * (size_t)oldN * sizeof(float)));
+        for (int a = 0; a < 10; a++) BFD_HIP(hipMemcpyAsync(oldComp + (size_t)a * oldN, src[a], (size_t)oldN * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+        BFD_HIP(hipStreamSynchronize(s->stream));
+        oldCells = s->tiles.shearCells; s->tiles.shearCells = nullptr;       // released below, after the new list has taken the values over
+    }
+    s->sensEntValid = false;
+    s->d.cssRow = nullptr; s->d.cSxx = s->d.cSyy = s->d.cSxy = s->d.cSxz = s->d.cSyz = s->d.cRxx = s->d.cRyy = s->d.cRxy = s->d.cRxz = s->d.cRyz = nullptr;
+    dev_release(s, &s->tiles.cssRow); dev_release(s, &s->tiles.css); s->tiles.cssCap = 0; s->tiles.cssHosted = false;
+    dev_release(s, &s->tiles.runsAll); s->tiles.nAll = s->tiles.nAllB = 0;
+    dev_release(s, &s->tiles.runs); dev_release(s, &s->tiles.xmap); dev_release(s, &s->tiles.shearCells); dev_release(s, &s->tiles.shearCoef); dev_release(s, &s->tiles.shearR);    // lists of an earlier build
+    dev_release(s, &s->tiles.shearCodes); dev_release(s, &s->tiles.shearTab);
+    const TileGrid G = choose_tile_grid(s);
+    std::vector<int> flags(G.n, 1), mats(G.n, 0);
+    if (s->cfg.kernelVariant != 2) { const int rc = fetch_tile_classes(s, G.n, flags, mats); if (rc) return rc; }
+    bfd_tiles &T = s->tiles;
+    T.nMat = s->cfg.nMat;
+    T.nFluid = T.nFluidB = T.nSolid = T.nSolidB = T.nSolidBP = T.nSolidIP = T.nFused = T.nLossless = T.nLossy = T.nSolidSub = T.nUni = T.nPml = T.nLean = T.nFusedSub = 0;
+    s->d.tilesX = G.tx; s->d.tilesY = G.ty;
+    // Every fluid sub-tile is LEAN (bit4): fluid cells keep a single copy of their identical normal stresses, whatever
+    // tile they sit in and whatever reads them (bfd_dev::cls)
+    if (s->cfg.kernelVariant != 2) for (int id = 0; id < G.n; id++) if (!(flags[id] & 1)) flags[id] |= 16;
+    std::vector<int4> lists[5];      // fluid boundary, fluid interior, solid boundary, solid interior, fused fluid
+    std::vector<int4> listsAll[2];   // every run of the two-kernel path in list order: boundary, interior (bfd_tiles::runsAll)
+    std::vector<char> taken((size_t)G.n, 0);
+    form_fused_runs(s, G, flags, mats, taken, lists[4]);
+    form_two_kernel_runs(s, G, flags, mats, taken, lists, listsAll);
     T.nFluidB = (int)lists[0].size(); T.nFluid = T.nFluidB + (int)lists[1].size();
     T.nSolidB = (int)lists[2].size(); T.nSolid = T.nSolidB + (int)lists[3].size();
     T.nFused = (int)lists[4].size();
@@ -1469,254 +1746,27 @@ static int build_tile_lists(bfd_sim *s)
     int rc = dev_alloc(s, &s->tiles.runs, all.size(), false);
     if (rc) return rc;
     BFD_HIP(hipMemcpy(s->tiles.runs, all.data(), all.size() * sizeof(int4), hipMemcpyHostToDevice));
-    // Cost-balanced block -> run maps (experiment, BFD_XCD_BALANCE=1; default off). A launch's blocks go to the 8 XCDs round-robin and every
-    // XCD works through its own blocks at its own pace (-DBFD_EXP_XCD_CLOCK build: block b always runs on XCD (x0 + b) mod 8). With equal
-    // COUNTS per XCD (remap_block) the XCD that holds the short boundary runs is idle for the last fifth of every fluid launch and the bands
-    // with more tissue finish last. Here the contiguous parts of the list are cut by estimated cost instead (planes + prologue, weighted by
-    // the bytes per cell of the run's class), the launch gets 8 x (longest part) blocks and a block beyond its part returns at once.
-    // Measured: the ends of the XCDs move together (spread 19 % -> 13 % of a launch) and the step time does not -- C3 +1.2 %, shear medium
-    // -0.4 %, other weightings +-2 % either way: an XCD that runs dry leaves its share of the memory system to the others.
-    // profiles/r4/xcd_balance.txt.
-    {
-        bool on = false;
-        if (const char *ev = getenv("BFD_XCD_BALANCE")) on = atoi(ev) != 0 && s->cfg.kernelVariant != 2 && s->cfg.kernelVariant != 1;
-        s->tiles.xmap = nullptr;
-        memset(s->tiles.xmapH, 0, sizeof s->tiles.xmapH);
-        if (on) {
-            const double wPml = 0.25, wLossy = 8, wMulti = 2, wRun = 2.0;
-            // cost of run r for kernel class c: 0 fluid stress, 1 fluid velocity, 2 solid stress, 3 solid velocity
-            auto cost = [&](const int4 &r, int c) {
-                const double planes = (double)((r.y >> 16) - (r.y & 0xFFFF)) + wRun;
-                const int f = r.z;
-                double w;
-                if (c == 0) w = 20 + ((f & 2) ? wLossy : 0) + ((f & 4) ? 0 : wMulti);
-                else if (c == 1) w = 36 + ((f & 4) ? 0 : wMulti);
-                else w = 40;
-                if (f & 8) w *= 1.0 + wPml;
-                return planes * w;
-            };
-            auto make = [&](int m, size_t a0, size_t a1, int c) {
-                int *seg = s->tiles.xmapH[m];
-                const size_t n = a1 > a0 ? a1 - a0 : 0;
-                std::vector<double> cum(n + 1, 0.0);
-                for (size_t i = 0; i < n; i++) cum[i + 1] = cum[i] + cost(all[a0 + i], c);
-                int maxcnt = 0;
-                seg[0] = 0;
-                for (int x = 1; x <= 8; x++) {
-                    const double target = cum[n] * x / 8.0;
-                    size_t j = std::lower_bound(cum.begin(), cum.end(), target) - cum.begin();
-                    if (j > n || x == 8) j = n;
-                    if ((int)j < seg[x - 1]) j = seg[x - 1];
-                    seg[x] = (int)j;
-                    maxcnt = std::max(maxcnt, seg[x] - seg[x - 1]);
-                }
-                seg[9] = std::max(maxcnt, 1);
-            };
-            const size_t F = T.nFluid, FB = T.nFluidB, S0 = F, SB = T.nSolidB, SN = T.nSolid;
-            for (int c = 0; c < 2; c++) {            // fluid stress (c = 0), fluid velocity (c = 1): parts 0, 1, 2
-                const int m = c == 0 ? BFD_XM_SF : BFD_XM_VF;
-                make(m + 0, 0, F, c); make(m + 1, 0, FB, c); make(m + 2, FB, F, c);
-            }
-            make(BFD_XM_SS + 0, S0, S0 + SN, 2); make(BFD_XM_SS + 1, S0, S0 + SB, 2); make(BFD_XM_SS + 2, S0 + SB, S0 + SN, 2);
-            const size_t bp = T.nSolidBP, ip = T.nSolidIP;          // solid list = [boundary: PML | plain][interior: plain | PML]
-            make(BFD_XM_VS + 0, S0 + bp, S0 + SN - ip, 3); make(BFD_XM_VS + 1, S0 + bp, S0 + SB, 3); make(BFD_XM_VS + 2, S0 + SB, S0 + SN - ip, 3);
-            make(BFD_XM_VSP_LO, S0, S0 + bp, 3); make(BFD_XM_VSP_HI, S0 + SN - ip, S0 + SN, 3);
-            make(BFD_XM_FUSED, S0 + SN, S0 + SN + T.nFused, 0);
-            rc = dev_alloc(s, &s->tiles.xmap, (size_t)BFD_XMAP_COUNT * 10, false);
-            if (rc) return rc;
-            BFD_HIP(hipMemcpy(s->tiles.xmap, s->tiles.xmapH, sizeof s->tiles.xmapH, hipMemcpyHostToDevice));
-        }
-    }
-    s->tiles.shearCells = nullptr; s->tiles.shearCoef = nullptr; s->tiles.shearR = nullptr; s->tiles.shearCodes = nullptr; s->tiles.shearTab = nullptr;
+    rc = build_balance_maps(s, all);
+    if (rc) return rc;
     s->tiles.nShearExplicit = 0;
     s->tiles.nShear = s->tiles.shearLowEnd = s->tiles.shearHighBeg = 0;
     if (T.nSolid && s->cfg.kernelVariant != 2) {     // variant 2 stays monolithic and fully dense
-        // sparse shear list: cells with a solid centre, ascending index, + their edge coefficients
-        unsigned char *flag = nullptr; unsigned *sel = nullptr; int *dcount = nullptr; void *work = nullptr;
-        hipError_t e = hipMalloc((void **)&flag, s->nloc);
-        if (e == hipSuccess) e = hipMalloc((void **)&sel, s->nloc * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc((void **)&dcount, sizeof(int));
-        int count = 0;
-        if (e == hipSuccess) {
-            bfd_launch_mark_solid(s->d, s->stream, flag, (long)s->nloc, T.merged);
-            size_t wbytes = 0;
-            hipcub::CountingInputIterator<unsigned> ids(0);
-            e = hipcub::DeviceSelect::Flagged(nullptr, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
-            if (e == hipSuccess) e = hipMalloc(&work, std::max<size_t>(wbytes, 1));
-            if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged(work, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        }
-        std::vector<unsigned> hostCells((size_t)count);
-        if (e == hipSuccess && count) e = hipMemcpy(hostCells.data(), sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost);
-        // list order (bfd_kernels_v2.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
-        // touched one band-plane earlier instead of one whole plane of the shell
-        const bool reorder = count > 0;
-        if (e == hipSuccess && reorder) {
-            unsigned long long *k0 = nullptr, *k1 = nullptr; unsigned *v1 = nullptr; void *w2 = nullptr; size_t w2b = 0;
-            e = hipMalloc((void **)&k0, (size_t)count * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&k1, (size_t)count * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&v1, (size_t)count * 4);
-            if (e == hipSuccess) {
-                bfd_launch_shear_order_keys(s->d, s->stream, sel, k0, count, lowPlanes, hiStart);
-                e = hipcub::DeviceRadixSort::SortPairs(nullptr, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
-            }
-            if (e == hipSuccess) e = hipMalloc(&w2, std::max<size_t>(w2b, 1));
-            if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(w2, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(sel, v1, (size_t)count * 4, hipMemcpyDeviceToDevice, s->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-            if (k0) hipFree(k0); if (k1) hipFree(k1); if (v1) hipFree(v1); if (w2) hipFree(w2);
-        }
-        // Compact solid state (bfd_dev::cssRow): Sxx, Syy, the shear stresses and the five memory variables Rxx, Ryy, Rxy, Rxz, Ryz of the listed cells in
-        // list order. Needs the row-contiguous list order and the two-kernel form. In a Z-slab the ghost planes of Sxz / Syz stay in the
-        // full-volume arrays (the sparse kernel keeps full-volume copies of the planes a neighbour reads, the velocity kernel takes ghost planes from
-        // there): the halo exchange is unchanged. BFD_COMPACT_SOLID=0 keeps the full-volume arrays.
-        bool compact = count > 0 && !T.merged && s->d.N1 <= 4095;
-        if (const char *ev = getenv("BFD_COMPACT_SOLID")) compact = compact && atoi(ev) != 0;
-        if (e == hipSuccess) {
-            rc = dev_alloc(s, &s->tiles.shearCells, (size_t)std::max(count, 1), false);
-            if (!rc) rc = dev_alloc(s, &s->tiles.shearCoef, 6 * (size_t)std::max(count, 1), false);
-            if (!rc && !T.merged && !compact) rc = dev_alloc(s, &s->tiles.shearR, 3 * (size_t)std::max(count, 1), true);      // lists are built at step 0: the memory variables start at zero (merged form: they live in the full-volume arrays; compact form: with the other compact arrays)
-            if (!rc && count) e = hipMemcpyAsync(s->tiles.shearCells, sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s->stream);
-            if (!rc) rc = dev_alloc(s, &s->tiles.shearCodes, (size_t)std::max(count, 1), false);
-            if (!rc) rc = dev_alloc(s, &s->tiles.shearTab, 8 * (size_t)s->cfg.nMat, false);
-            if (!rc && e == hipSuccess) bfd_launch_shear_coefficients(s->d, s->stream, s->tiles.shearCells, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.shearTab, s->cfg.nMat, count);
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        }
-        if (flag) hipFree(flag); if (sel) hipFree(sel); if (dcount) hipFree(dcount); if (work) hipFree(work);
-        if (e != hipSuccess) BFD_FAIL(-10, std::string("shear list: ") + hipGetErrorString(e));
+        int count = 0; bool compact = false; std::vector<unsigned> hostCells;
+        rc = build_shear_list(s, G, &count, &compact, hostCells);
+        if (!rc && compact) rc = setup_compact_state(s, G, count, listsAll);
+        if (!rc && carryCompact) rc = carry_compact_in(s, count, oldCells, oldN, oldComp);
         if (rc) return rc;
-        s->tiles.nShear = count;
-        if (s->step > 0 && s->tiles.shearR) { bfd_launch_gather_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
-        if (compact) {
-            const int stride = tx + 1;
-            rc = dev_alloc(s, &s->tiles.cssRow, (size_t)(s->d.nk + 4) * s->d.N2 * stride, false);
-            // the compact arrays live inside the full-volume buffers of their fields when the listed cells fit between the planes a Z-neighbour
-            // exchanges (local planes 0, 1 and nk-2, nk-1 of Sxz / Syz travel: allocation planes 4 .. nk-1 are free); BFD_COMPACT_HOSTED=0 or
-            // too many solid cells: one block of their own
-            bool hosted = (size_t)count <= (size_t)std::max(s->d.nk - 4, 0) * s->d.plane;
-            if (const char *ev = getenv("BFD_COMPACT_HOSTED")) hosted = hosted && atoi(ev) != 0;
-            if (!rc && !hosted) rc = dev_alloc(s, &s->tiles.css, 10 * (size_t)count, true);
-            if (rc) return rc;
-            s->tiles.cssCap = count; s->tiles.cssHosted = hosted;
-            bfd_launch_css_row_table(s->d, s->stream, s->tiles.shearCells, count, s->tiles.cssRow, stride, lowPlanes, hiStart);
-            s->d.cssRow = s->tiles.cssRow; s->d.cssStride = stride;
-            bind_compact_views(s);
-            BFD_HIP(hipStreamSynchronize(s->stream));
-            std::vector<int4> ra(listsAll[0]);
-            ra.insert(ra.end(), listsAll[1].begin(), listsAll[1].end());
-            rc = dev_alloc(s, &s->tiles.runsAll, ra.size(), false);
-            if (rc) return rc;
-            BFD_HIP(hipMemcpy(s->tiles.runsAll, ra.data(), ra.size() * sizeof(int4), hipMemcpyHostToDevice));
-            s->tiles.nAllB = (int)listsAll[0].size(); s->tiles.nAll = (int)ra.size();
-        }
-        if (carryCompact) {       // the values of the old list into the new one (or, should the new state not be compact, into the full-volume arrays)
-            float *tmp = nullptr;
-            const size_t g = 2 * (size_t)s->d.plane;
-            float *newComp[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
-            float *full[10] = {s->d.Sxx, s->d.Syy, s->d.Sxy, s->d.Sxz, s->d.Syz, s->d.Rxx, s->d.Ryy, s->d.Rxy, s->d.Rxz, s->d.Ryz};
-            hipError_t e2 = s->d.cssRow ? malloc_or_release_cache((void **)&tmp, s->nalloc * sizeof(float)) : hipSuccess;
-            // the new state is not compact (no solid cell left, or the form was switched off): the full-volume arrays take over, and the owned planes
-            // of buffers that hosted compact arrays hold list-ordered values, not fields: cleared before the old values are scattered into them
-            for (int a = 0; a < 10 && e2 == hipSuccess && !s->d.cssRow; a++) e2 = hipMemsetAsync(full[a], 0, s->nloc * sizeof(float), s->stream);
-            for (int a = 0; a < 10 && e2 == hipSuccess; a++) {
-                if (s->d.cssRow) {
-                    e2 = hipMemsetAsync(tmp, 0, s->nalloc * sizeof(float), s->stream);
-                    bfd_launch_css_scatter(s->stream, oldCells, oldN, oldComp + (size_t)a * oldN, tmp + g);
-                    bfd_launch_css_gather(s->stream, s->tiles.shearCells, count, tmp + g, newComp[a]);
-                } else bfd_launch_css_scatter(s->stream, oldCells, oldN, oldComp + (size_t)a * oldN, full[a]);
-            }
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(s->stream);
-            if (tmp) hipFree(tmp);
-            if (e2 != hipSuccess) BFD_FAIL(-10, std::string("compact solid state, list rebuilt in the middle of a run: ") + hipGetErrorString(e2));
-            if (!s->d.cssRow && s->tiles.shearR) { bfd_launch_gather_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
-        }
-        s->tiles.shearLowEnd = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)lowPlanes * (unsigned)s->d.plane) - hostCells.begin();
-        s->tiles.shearHighBeg = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)hiStart * (unsigned)s->d.plane) - hostCells.begin();
+        s->tiles.shearLowEnd = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)G.lowPlanes * (unsigned)s->d.plane) - hostCells.begin();
+        s->tiles.shearHighBeg = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)G.hiStart * (unsigned)s->d.plane) - hostCells.begin();
     }
     {   // sources of the first / last z-chunk (bfd_set_sources sorted them by voxel)
         std::vector<uint32_t> lin((size_t)s->nSrcVox);
         if (s->nSrcVox) BFD_HIP(hipMemcpy(lin.data(), s->srcLin, lin.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        s->srcLowEnd = std::lower_bound(lin.begin(), lin.end(), (uint32_t)lowPlanes * (uint32_t)s->d.plane) - lin.begin();
-        s->srcHighBeg = std::lower_bound(lin.begin(), lin.end(), (uint32_t)hiStart * (uint32_t)s->d.plane) - lin.begin();
+        s->srcLowEnd = std::lower_bound(lin.begin(), lin.end(), (uint32_t)G.lowPlanes * (uint32_t)s->d.plane) - lin.begin();
+        s->srcHighBeg = std::lower_bound(lin.begin(), lin.end(), (uint32_t)G.hiStart * (uint32_t)s->d.plane) - lin.begin();
     }
-    {   // algorithmic bytes per launch and kernel class (DESIGN.md "Kernels": per-cell byte tables of the tile classes):
-        // what each kernel has to move once per half-step if every value were fetched exactly once -- float32 fields 4 B,
-        // material ids 2 B; absorbing-layer memory variables, tables and halo re-reads excluded
-        double (*B)[BFD_K_COUNT] = s->algBytes;
-        memset(s->algBytes, 0, sizeof s->algBytes);
-        const int N1 = s->d.N1, N2 = s->d.N2, N3 = s->d.N3, ND = s->d.ND, k0g = s->d.k0;
-        // class counts over the cells of the solid runs (fluid / solid centre, with / without memory variables, active edges)
-        unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-        if (T.nSolid && s->cfg.kernelVariant != 2) {
-            unsigned long long *dc = nullptr;
-            BFD_HIP(hipMalloc((void **)&dc, sizeof cnt));
-            hipMemsetAsync(dc, 0, sizeof cnt, s->stream);
-            bfd_launch_count_solid_cells(s->d, s->stream, s->tiles.runs + T.nFluid, T.nSolid, dc);
-            hipMemcpyAsync(cnt, dc, sizeof cnt, hipMemcpyDeviceToHost, s->stream);
-            const hipError_t e = hipStreamSynchronize(s->stream);
-            hipFree(dc);
-            if (e != hipSuccess) BFD_FAIL(-10, std::string("solid cell counts: ") + hipGetErrorString(e));
-        }
-        auto overlap = [](int a, int b, int lo, int hi) { return (double)std::max(0, std::min(b, hi) - std::max(a, lo)); };
-        const bool pairAcc = pair_engine(s, quiet_runs_wanted(s), T.nFluid);      // the predicate the launches follow (pairing_step)
-        for (size_t r = 0; r < all.size(); r++) {
-            const int4 &run = all[r];
-            const int bx = run.x % tx, by = run.x / tx, kb = run.y & 0xFFFF, ke = run.y >> 16, f = run.z;
-            const int xa = bx * 64, xb = std::min(xa + 64, N1), ya = by * 8, yb = std::min(ya + 8, N2);
-            const double cells = (double)(xb - xa) * (yb - ya) * (ke - kb);
-            const double inner = overlap(xa, xb, ND, N1 - ND) * overlap(ya, yb, ND, N2 - ND) * overlap(k0g + kb, k0g + ke, ND, N3 - ND);
-            const bool fusedRun = r >= (size_t)(T.nFluid + T.nSolid);
-            if (fusedRun) {          // 64 x 24 cells per plane, all outside the absorbing layer: V, Szz (Rzz) read and written once per step (+ ids)
-                const double fc = 64.0 * bfd_fused_rows() * (ke - kb);
-                const double b = 32.0 + ((f & 2) ? 8.0 : 0.0) + ((f & 4) ? 0.0 : 2.0);
-                B[0][BFD_K_FUSED] += b * fc; B[1][BFD_K_FUSED] += b * fc + 8.0 * fc;
-            } else if (r < (size_t)T.nFluid) {
-                const bool lossy = f & 2, uni = f & 4, single = (f & 16) != 0;
-                double bs = 12.0 + 8.0 + (lossy ? 8.0 : 0.0) + (uni ? 0.0 : 2.0);
-                if (!single) bs += 8.0 + (lossy ? 8.0 : 0.0);
-                const double bv = 4.0 + 24.0 + (uni ? 0.0 : 2.0);
-                for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_FLUID] += bs * cells; B[a][BFD_K_VELOCITY_FLUID] += bv * cells; }
-                // Pressure sum read and written: by velocity_fluid in every accumulating step, or (paired accumulation) by stress_fluid in
-                // every second one: 4 B per launch averaged over a step pair
-                if (pairAcc) B[1][BFD_K_STRESS_FLUID] += 4.0 * inner; else B[1][BFD_K_VELOCITY_FLUID] += 8.0 * inner;
-            } else if (s->cfg.kernelVariant == 2) {     // dense: V + 6 S + 6 R read, 6 S + 6 R written, id; 6 S + V read, V written, id
-                for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_SOLID] += 110.0 * cells; B[a][BFD_K_VELOCITY_SOLID] += 50.0 * cells + (a ? 8.0 * inner : 0.0); }
-            } else {                                    // class-predicated solid kernels: per-cell terms come from the class counts below
-                for (int a = 0; a < 2; a++) B[a][BFD_K_VELOCITY_SOLID] += (a ? 8.0 * inner : 0.0);
-            }
-        }
-        if (T.nSolid && s->cfg.kernelVariant != 2) {
-            // stress: V 12 + id 2 + class 1, + Szz r/w 8 (+ Rzz r/w 8) at a fluid cell, + 3 S r/w 24 + 3 R r/w 24 at a solid one
-            // (a reflector cell: 48 B of zero stores); velocity: V r/w 24 + ids 2 + class 1 + Szz 4, + Sxx, Syy 8 at a solid cell,
-            // + 4 per active shear edge
-            const double nF0 = (double)cnt[0], nF1 = (double)cnt[1], nS = (double)cnt[2] + (double)cnt[3], nE = (double)cnt[4], nR = (double)cnt[5];
-            const double all = nF0 + nF1 + nS + nR;
-            const double bs = 15.0 * all + 8.0 * nF0 + 16.0 * nF1 + 48.0 * nS + 48.0 * nR;
-            const double bv = 31.0 * all + 8.0 * (nS + nR) + 4.0 * nE;
-            // compact solid state: the fluid kernel takes Szz / Rzz of the solid runs too (V 12 + id 2, + Szz r/w 8 (+ Rzz r/w 8); no class byte), the
-            // sparse kernel Sxx, Syy, Rxx, Ryy of its cells (+ 32 + id 2 per listed cell, below)
-            const double bsf = 14.0 * all + 8.0 * nF0 + 16.0 * nF1 + 16.0 * nS + 8.0 * nR;
-            for (int a = 0; a < 2; a++) { if (s->d.cssRow) B[a][BFD_K_STRESS_FLUID] += bsf; else B[a][BFD_K_STRESS_SOLID] += bs; B[a][BFD_K_VELOCITY_SOLID] += bv; }
-        }
-        if (s->tiles.nShear) {       // sparse shear: cell index + 6 coefficients + V of the cell + read-modify-write of S and R per active edge
-            unsigned long long *dc = nullptr, hc[2] = {0, 0};
-            BFD_HIP(hipMalloc((void **)&dc, sizeof hc));
-            hipMemsetAsync(dc, 0, sizeof hc, s->stream);
-            hipLaunchKernelGGL(count_active_edges, dim3(grid_for(s->tiles.nShear)), dim3(256), 0, s->stream, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.nShear, dc);
-            hipMemcpyAsync(hc, dc, sizeof hc, hipMemcpyDeviceToHost, s->stream);
-            const hipError_t e = hipStreamSynchronize(s->stream);
-            hipFree(dc);
-            if (e != hipSuccess) BFD_FAIL(-10, std::string("shear edge count: ") + hipGetErrorString(e));
-            s->tiles.nShearExplicit = (long)hc[1];
-            // per listed cell: index 4 + edge codes 4 + V 12; per edge with explicit coefficients 8; per active edge S and R r/w 16; compact solid
-            // state: + Sxx, Syy, Rxx, Ryy r/w 32 (+ the cell's id 2 when it does not fit the code word's fourth byte)
-            const double perCell = s->d.cssRow ? (s->cfg.nMat <= 255 ? 52.0 : 54.0) : 20.0;
-            for (int a = 0; a < 2; a++) B[a][BFD_K_STRESS_SHEAR] = perCell * (double)s->tiles.nShear + 8.0 * (double)hc[1] + 16.0 * (double)hc[0];
-            if (T.merged) for (int a = 0; a < 2; a++) B[a][BFD_K_STRESS_SOLID] -= 16.0 * (double)hc[0];      // those edges are the sparse kernel's
-        }
-        if (T.merged && T.nSolid && s->cfg.kernelVariant != 2) for (int a = 0; a < 2; a++) B[a][BFD_K_STRESS_SOLID] += 16.0 * (double)cnt[4];   // S and R of every active edge, read and written
-    }
+    rc = account_algorithmic_bytes(s, G.tx, all);
+    if (rc) return rc;
     if (oldCells) dev_release(s, &oldCells);
     s->tilesReady = true;
     return 0;

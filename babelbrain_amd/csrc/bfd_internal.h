@@ -16,7 +16,6 @@
 #define BFD_CLS_EXZ 8u
 #define BFD_CLS_EYZ 16u
 #define BFD_CLS_REFL 32u    // reflector voxel
-#define BFD_CLS_MIXED 64u   // an updated shear edge of this cell lies between different materials (coefficients are not the per-material ones)
 
 // CA, CB of the O(4) staggered first derivative (Taylor coefficients) and the matching stability constant
 // 1/(CA+CB) of dt <= BFD_STAB h / (sqrt(3) cmax). Overridable for scheme experiments (tests/rayleigh_study.py):
@@ -119,7 +118,7 @@ void bfd_kmark(bfd_sim *sim, int cls, int end, hipStream_t st);
 // maps of bfd_tiles::xmap: fluid stress / fluid velocity / solid stress / solid velocity (plain runs) by part 0, 1, 2; the two pieces of solid
 // runs in the absorbing layer; the fused runs
 enum { BFD_XM_SF = 0, BFD_XM_VF = 3, BFD_XM_SS = 6, BFD_XM_VS = 9, BFD_XM_VSP_LO = 12, BFD_XM_VSP_HI = 13, BFD_XM_FUSED = 14, BFD_XMAP_COUNT = 15 };
-struct bfd_tiles { bfd_sim *ktimer; int nMat; bool merged /* solid runs: normal and shear stresses in one kernel, the sparse list holds the MIXED cells only */; int4 *runs;
+struct bfd_tiles { bfd_sim *ktimer; int nMat; int4 *runs;
                    unsigned *shearCells; float *shearCoef; long nShear, shearLowEnd, shearHighBeg;   /* sparse shear list */
                    unsigned *shearCodes; float *shearTab; long nShearExplicit;   /* per listed cell a byte per edge: 0 inactive, 1 + m = one material around the edge (coefficients from shearTab[8 m], [8 m + 1]; the cell's own AP, BP, AS2, BS2 at [8 m + 4 ..]), 255 = explicit coefficients in shearCoef; number of explicit edges */
                    int4 *runsAll; int nAll, nAllB;   /* compact solid state: every run, fluid and solid, in list order [boundary | interior] -- the stress half-step's one launch of the fluid kernel */
@@ -128,7 +127,7 @@ struct bfd_tiles { bfd_sim *ktimer; int nMat; bool merged /* solid runs: normal 
                       regions, which the sparse kernel's ten streams need as much as the marching kernels' do: 0.253 against 0.266-0.29 ms), from allocation plane 4 on
                       (the planes a Z-neighbour exchanges stay free); else css = one block [10][cssCap] (solid cells too many for that) */
                    unsigned *cssRow; float *css; long cssCap; bool cssHosted;
-                   float *shearR;   /* memory variables Rxy, Rxz, Ryz of the listed cells, [3][nShear] in list order: only the sparse kernel uses them, so they live beside the list (dense, coalesced) instead of in the full-volume arrays, which are filled from here on demand (bfd_get_field) */
+                   float *shearR;   /* full-volume solid state (BFD_COMPACT_SOLID=0) only: memory variables Rxy, Rxz, Ryz of the listed cells, [3][nShear] in list order, beside the list (dense, coalesced); the full-volume arrays are filled from here on demand (bfd_get_field). Null when the state is compact */
                    int nFluid, nFluidB, nSolid, nSolidB, nSolidBP /* leading boundary runs that touch the absorbing layer */, nSolidIP /* trailing interior ones */, nFused /* runs of the fused kernel, after the solid runs */;
                    int nLossless, nLossy, nSolidSub, nUni, nPml, nLean, nFusedSub;
                    /* cost-balanced block -> run maps (round 4): block b of a launch runs on XCD slot b & 7 and takes run seg[slot] + (b >> 3) of
@@ -229,8 +228,8 @@ int bfd_fused_max_materials(void);
 int bfd_tile_subz(void);
 void bfd_launch_classify(const bfd_dev &d, hipStream_t s, int *flagsDev, int *tileMatDev);
 void bfd_launch_mark_source_subtiles(const bfd_dev &d, hipStream_t s, const uint32_t *lin, long n);
-// flags the cells of the sparse shear list: solid, non-reflector centre; mixedOnly: only those with BFD_CLS_MIXED (merged solid stress kernel)
-void bfd_launch_mark_solid(const bfd_dev &d, hipStream_t s, unsigned char *flag, long n, bool mixedOnly);
+// flags the cells of the sparse shear list: solid, non-reflector centre
+void bfd_launch_mark_solid(const bfd_dev &d, hipStream_t s, unsigned char *flag, long n);
 void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart);
 void bfd_launch_shear_coefficients(const bfd_dev &d, hipStream_t s, const unsigned *cells, float *coef, unsigned *codes, float *tab, int nMat, long n);
 // copies the list-ordered shear memory variables into the full-volume arrays Rxy, Rxz, Ryz (outputs only)
