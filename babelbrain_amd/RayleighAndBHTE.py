@@ -2,6 +2,8 @@
 (imports at TranscranialModeling/BabelIntegrationBASE.py:19 and BabelIntegrationSingle.py:23):
 
     ForwardSimple(cwvnb, center, ds, u0, rf, deviceMetal=None)     Single:295, ANNULAR:383,411, CONCAVE:307,328,425,446
+    ForwardSteered / ForwardElements                                not in the reference: its loops over steerings (CONCAVE:91-107)
+                                                                   and over elements (H246:333-339, ANNULAR:379-384) as one call
     InitCuda / InitOpenCL / InitMetal(deviceName)                  BASE:918-925
     SpeedofSoundWater(T)                                           Single:243
     GenerateFocusTx(f, Foc, Diam, c, PPWSurface)                   Single:241
@@ -105,6 +107,116 @@ def ForwardSimple(cwvnb, center, ds, u0, rf, deviceMetal=None, MacOsPlatform=Non
             raise _engine.EngineError(e)
     last_kernel_ms = max(times)
     return out
+
+
+def _elem_start(elemdims, nSrc):
+    """elemStart (int64, nElem + 1) of the records of each element: elemdims is one count for every element (CONCAVE's
+    self._Tx['elemdims']: nSrc must be a multiple of it) or one count per element, flat or in the reference's
+    elemdims[n][0] shape (H246:333-339, ANNULAR:379-384). The records of an element are contiguous, elements in
+    ascending order (nBase += elemdims)."""
+    if np.ndim(elemdims) == 0:
+        c = int(elemdims)
+        if c != elemdims or c <= 0 or nSrc % c:
+            raise ValueError('a uniform elemdims must be a positive count that divides the %d sub-sources' % nSrc)
+        counts = np.full(nSrc // c, c, np.int64)
+    else:
+        raw = np.asarray(elemdims)
+        if raw.ndim == 2 and raw.shape[1] == 1:
+            raw = raw[:, 0]
+        if raw.ndim != 1 or (raw.size and not np.all(raw == np.floor(raw))):
+            raise ValueError('elemdims must be an int or a sequence of counts (flat or [[c], ...])')
+        counts = raw.astype(np.int64)
+        if np.any(counts < 0):
+            raise ValueError('elemdims holds a negative count')
+        if counts.sum() != nSrc:
+            raise ValueError('elemdims add up to %d, not to the %d sub-sources' % (counts.sum(), nSrc))
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), np.int64)
+
+
+def _forward_elements(cwvnb, center, ds, elemdims, weights, rf, u0):
+    """ForwardSteered (weights (nElem, S)) and ForwardElements (weights None) through bfd_rayleigh_forward_elements; the field
+    points are shared among the devices as in ForwardSimple."""
+    global last_kernel_ms
+    k = complex(np.asarray(cwvnb).reshape(-1)[0])
+    cen = np.ascontiguousarray(center, np.float32).reshape(-1, 3)
+    a = np.ascontiguousarray(ds, np.float32).reshape(-1)
+    u = None if u0 is None else np.ascontiguousarray(np.asarray(u0).reshape(-1), np.complex64)
+    pts = np.ascontiguousarray(rf, np.float32).reshape(-1, 3)
+    if len(a) != len(cen) or (u is not None and len(u) != len(cen)):
+        raise ValueError('center, ds and u0 must describe the same number of sources')
+    es = _elem_start(elemdims, len(cen))
+    nElem = len(es) - 1
+    w = None
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim == 1:
+            w = w[:, None]
+        if w.ndim != 2 or w.shape[0] != nElem:
+            raise ValueError('weights must be (nElem, S) or (nElem,) with nElem = %d' % nElem)
+        if w.shape[1] < 1:
+            raise ValueError('weights must hold at least one steering column')
+        w = np.ascontiguousarray(w, np.complex64)
+    nOut = nElem if w is None else w.shape[1]
+    lib = _engine.load_library()
+    out = np.zeros((nOut, len(pts)), np.complex64)
+    devices = _devices
+    if devices is None and os.environ.get('BABELFDTD_DEVICES'):
+        set_devices(os.environ['BABELFDTD_DEVICES'])
+        devices = _devices
+    if devices is None or len(pts) < 64 * len(devices):
+        devices = [_device]
+    bounds = [len(pts) * r // len(devices) for r in range(len(devices) + 1)]
+    times, errors = [0.0] * len(devices), [None] * len(devices)
+
+    def share(r):          # ctypes releases the GIL for the call: the devices work at the same time
+        n0, n1 = bounds[r], bounds[r + 1]
+        if n1 <= n0:
+            return
+        ms = C.c_double()
+        part = out if len(devices) == 1 else np.empty((nOut, n1 - n0), np.complex64)
+        rc = lib.bfd_rayleigh_forward_elements(devices[r], len(cen), _ptr(cen), _ptr(a), None if u is None else _ptr(u.view(np.float32)),
+                                               nElem, _ptr(es), 0 if w is None else w.shape[1], None if w is None else _ptr(w.view(np.float32)),
+                                               k.real, k.imag, n1 - n0, _ptr(pts[n0:n1]), _ptr(part.view(np.float32)), C.byref(ms))
+        if rc != 0:
+            errors[r] = 'bfd_rayleigh_forward_elements failed on device %d (rc=%d): %s' % (devices[r], rc, lib.bfd_last_error().decode())
+            return
+        if part is not out:
+            out[:, n0:n1] = part
+        times[r] = ms.value
+    if len(devices) == 1:
+        share(0)
+    else:
+        th = [threading.Thread(target=share, args=(r,)) for r in range(len(devices))]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+    for e in errors:
+        if e:
+            raise _engine.EngineError(e)
+    last_kernel_ms = max(times)
+    return out
+
+
+def ForwardSteered(cwvnb, center, ds, elemdims, weights, rf, u0=None, deviceMetal=None):
+    """S steered fields of a phased array over one geometry in one pass (bfd_rayleigh_forward_elements):
+        out[s][n] = sum_e weights[e][s] (i k / 2 pi) sum_{m in element e} u0[m] ds[m] exp(-i k R_nm) / R_nm
+    which is ForwardSimple with u0[m] -> weights[elem(m)][s] u0[m], for every column s, at about the cost of one such call: the
+    reference runs its whole case once per MultiPoint entry (CONCAVE:91-107, ForwardSimple at :328 and :446) although only one
+    complex number per element changes (:308-314). elemdims: records per element, an int (uniform, self._Tx['elemdims']) or a
+    sequence of counts, flat or [[c], ...]; the records of an element are contiguous (nBase += elemdims). weights: (nElem, S) or
+    (nElem,) complex; u0: optional per-sub-source factor (AdjustWeightAmplitudes, BASE:2224-2234), default 1.
+    Returns complex64 (S, N). The field points are shared among several devices as in ForwardSimple."""
+    if weights is None:
+        raise ValueError('ForwardSteered needs weights (ForwardElements returns the element fields themselves)')
+    return _forward_elements(cwvnb, center, ds, elemdims, weights, rf, u0)
+
+
+def ForwardElements(cwvnb, center, ds, elemdims, rf, u0=None, deviceMetal=None):
+    """The field of every element by itself, complex64 (nElem, N): row e is ForwardSimple on the records of element e alone
+    (u0 default 1). One call for the per-element loops of H246:333-339, ANNULAR:379-384 and TxCalibration:323-328, 1021-1026;
+    an empty element gives zeros. Arguments as in ForwardSteered."""
+    return _forward_elements(cwvnb, center, ds, elemdims, None, rf, u0)
 
 
 def SpeedofSoundWater(Temperature):

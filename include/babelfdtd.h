@@ -338,6 +338,30 @@ int64_t bfd_group_device_bytes(bfd_group *g);
 int bfd_rayleigh_forward(int32_t device, int64_t nSrc, const float *center, const float *ds, const float *u0,
                          double kReal, double kImag, int64_t nPts, const float *rf, float *out, double *kernelMs);
 
+/* ---- The same integral resolved by transducer element: many steerings, or every element's own field, in one pass ----
+ * Replaces the repeated ForwardSimple calls of the phased-array drivers over one geometry:
+ *   per steering: BabelIntegrationCONCAVE_PHASEDARRAY.py:91-107 (each MultiPoint entry calls ForwardSimple at :328 and, refocused,
+ *   at :446, and once more for the water-only pass; H317, I12378, ATAC, R15148, R15646, IGT64_500, H301, DomeTx and REMOPD reach
+ *   it through CalculateFieldProcess.py:75-120) -- between those calls only exp(i phi_e) per element changes (:308-314);
+ *   per element: BabelIntegrationH246.py:333-339, BabelIntegrationANNULAR_ARRAY.py:379-384, TxCalibration.py:323-328, 1021-1026
+ *   (one ForwardSimple call per element on that element's sub-sources).
+ * The records of element e are elemStart[e] .. elemStart[e+1]-1 (nBase += elemdims in the reference).
+ *   G[e][n]   = (i k / 2pi) sum_{m in e} sub[m] ds[m] exp(-i k R_nm) / R_nm,  k = kReal + i kImag
+ *   out[s][n] = sum_e weights[e][s] G[e][n]
+ * sub: nSrc x 2 float32 (re,im) per-sub-source factor (AdjustWeightAmplitudes / OptimizedWeights, BabelIntegrationBASE.py:2224-2234),
+ * NULL = 1. elemStart: nElem + 1 values, elemStart[0] = 0, elemStart[nElem] = nSrc, non-decreasing; an empty element contributes
+ * nothing. weights: [nElem][nSteer][2] float32; out: [nSteer][nPts][2]. Any nSteer >= 1: geometry and points go up once, the
+ * columns run 8 to a launch, kernelMs (may be NULL) is the device time of all launches.
+ * Element mode, weights = NULL and nSteer = 0: out is G itself, [nElem][nPts][2] (zeros for an empty element).
+ * A column's value depends only on the records, that column of the weights, k and the point -- not on nSteer, the column's
+ * position, nPts or the point's position.
+ * Device memory held during the call: 24 nSrc + 8 (nElem + 1) + 64 nElem ceil(nSteer / 8) + 12 nPts + 8 nPts nSteer bytes
+ * (element mode: 8 nPts nElem for the result). Returns 0; -1 bad argument, -3 no such device, -10 device error (a failed
+ * allocation included); bfd_last_error() has the text. nPts = 0 returns 0. */
+int bfd_rayleigh_forward_elements(int32_t device, int64_t nSrc, const float *center, const float *ds, const float *sub,
+                                  int32_t nElem, const int64_t *elemStart, int32_t nSteer, const float *weights,
+                                  double kReal, double kImag, int64_t nPts, const float *rf, float *out, double *kernelMs);
+
 /* ---- Pennes bio-heat equation + CEM43 dose: replaces BabelViscoFDTD.tools.RayleighAndBHTE.BHTE ----
  * (call sites ThermalModeling/CalculateTemperatureEffects.py:365-456, 960). Volumes x-fastest float32, mat = uint8
  * ids into cd/cp (per material: dt k/(rho c dx^2) and dt rho_b c_b w/(6e7 c)); q = temperature increment of one ON
