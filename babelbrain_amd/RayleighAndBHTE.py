@@ -303,20 +303,28 @@ def bhte_pass_plan(sched, nFactorMonitoring=1, monitored_plane=True, steps_heati
 
 
 def _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, blood_rho, blood_ct, DutyCycle, MonitoringPointsMap, initT0, initDose):
-    """Host-side checks and the arrays every bfd_bhte_run_* call takes (no device call)."""
+    """Host-side checks and the arrays every bfd_bhte_run_* call takes (no device call). The width of the material ids follows from
+    the LENGTH of MaterialList: up to 256 rows give a uint8 map for bfd_bhte_run_volumes / _protocol, more (a CT-derived list: up
+    to 1030) a uint16 map for the ...16 entries; 'wide' says which."""
     P = np.asarray(fields)
     nF, N1, N2, N3 = P.shape
     mm = np.asarray(MaterialMap)
     nMat = len(MaterialList['Density'])
     if mm.shape != (N1, N2, N3):
         raise ValueError('MaterialMap must have the shape of the pressure field(s)')
-    if mm.max() >= nMat or nMat > 256:
-        raise ValueError('MaterialMap ids must index MaterialList (at most 256 materials)')
+    wide = nMat > 256
+    bad_id = mm.size > 0 and (mm.min() < 0 or mm.max() >= nMat)
+    if wide or bad_id:                  # the limit of the 16-bit path is the library's to say; up to 256 rows need no library here
+        limit = int(_engine.load_library().bfd_bhte_max_materials())
+        if nMat > limit:
+            raise ValueError('MaterialList has %d rows: the bio-heat solver takes at most %d materials' % (nMat, limit))
+        if bad_id:
+            raise ValueError('MaterialMap ids must index MaterialList (%d rows; at most %d materials)' % (nMat, limit))
     cd, cp, qf = bhte_coefficients(MaterialList, dx, dt, DutyCycle, blood_rho, blood_ct)
 
     # The volumes go to the device in the caller's C order (bfd_bhte_run_volumes: last axis fastest, neighbours summed axis 0
     # first like the oracle does): no transposes; the heat source q = (p p) qf[material] is computed on the device and comes back.
-    mat = np.ascontiguousarray(mm, np.uint8)
+    mat = np.ascontiguousarray(mm, np.uint16 if wide else np.uint8)     # every id < nMat (checked above): the cast cannot wrap
     P32 = np.ascontiguousarray(P, np.float32)
     flags = 0
     if initT0 is not None:
@@ -341,7 +349,7 @@ def _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, blood_rho, blood_ct,
         lin = np.flatnonzero(mp)
         order = np.argsort(mp[lin], kind='stable')               # point ids 1..n label the rows
         idx = np.ascontiguousarray(lin[order], np.uint32)
-    return dict(shape=(nF, N1, N2, N3), nMat=nMat, mat=mat, cd=cd, cp=cp, qf=qf, initT=initT, P32=P32, T=T, dose=dose, flags=flags, idx=idx)
+    return dict(shape=(nF, N1, N2, N3), nMat=nMat, wide=wide, mat=mat, cd=cd, cp=cp, qf=qf, initT=initT, P32=P32, T=T, dose=dose, flags=flags, idx=idx)
 
 
 def _ptr(a):
@@ -370,11 +378,12 @@ def _bhte_run(fields, sched, MaterialMap, MaterialList, dx, LocationMonitoring, 
         sched = np.full(1, -1, np.int32)
 
     ptr = _ptr
-    rc = lib.bfd_bhte_run_volumes(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
-                                  ptr(v['P32']), ptr(q), ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
-                                  int(LocationMonitoring) if slice_ok else -1, fm, ptr(mon), 0 if idx is None else len(idx), ptr(idx), ptr(pts), C.byref(ms))
+    entry = 'bfd_bhte_run_volumes16' if v['wide'] else 'bfd_bhte_run_volumes'
+    rc = getattr(lib, entry)(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
+                             ptr(v['P32']), ptr(q), ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
+                             int(LocationMonitoring) if slice_ok else -1, fm, ptr(mon), 0 if idx is None else len(idx), ptr(idx), ptr(pts), C.byref(ms))
     if rc != 0:
-        raise _engine.EngineError('bfd_bhte_run_volumes failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+        raise _engine.EngineError('%s failed (rc=%d): %s' % (entry, rc, lib.bfd_last_error().decode()))
     last_kernel_ms = ms.value
     out = (T, dose, mon if slice_ok else np.zeros((0,), np.float32), q)
     if MonitoringPointsMap is not None:
@@ -529,12 +538,13 @@ def RunBHTECycles(nCurrent, Repetitions, TotalIterations, TotalDurationBetweenGr
     lib = _engine.load_library()
     ms = C.c_double()
     ptr = _ptr
-    rc = lib.bfd_bhte_run_protocol(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
-                                   ptr(v['P32']), None, ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
-                                   -1, max(int(nFactorMonitoring), 1), None, len(idx), ptr(idx), ptr(pts), C.byref(ms),
-                                   len(caps), ptr(caps), ptr(Tmax), ptr(doseCap))
+    entry = 'bfd_bhte_run_protocol16' if v['wide'] else 'bfd_bhte_run_protocol'
+    rc = getattr(lib, entry)(_device, N1, N2, N3, v['nMat'], ptr(v['mat']), ptr(v['cd']), ptr(v['cp']), ptr(v['qf']), ptr(v['initT']), nF,
+                             ptr(v['P32']), None, ptr(T), ptr(dose), v['flags'], float(stableTemp), float(dt), nSteps, ptr(sched),
+                             -1, max(int(nFactorMonitoring), 1), None, len(idx), ptr(idx), ptr(pts), C.byref(ms),
+                             len(caps), ptr(caps), ptr(Tmax), ptr(doseCap))
     if rc != 0:
-        raise _engine.EngineError('bfd_bhte_run_protocol failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+        raise _engine.EngineError('%s failed (rc=%d): %s' % (entry, rc, lib.bfd_last_error().decode()))
     last_kernel_ms = ms.value
     if int(nCurrent) > 0:
         pts = np.hstack((TemperaturePoints, pts))

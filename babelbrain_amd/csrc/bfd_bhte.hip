@@ -9,7 +9,7 @@
 //   T' = T + cd[m] * (((((Txm+Txp)+Tym)+Typ)+Tzm)+Tzp - 6 T) + cp[m] * (Tcore - T) + (n < nStepsOn ? q : 0)
 //   cd = dt k/(rho c dx^2),  cp = dt rho_b c_b w / (6e7 c)  (w in mL/min/kg),  q = dt * duty * a_abs p^2/(rho c_s) / (rho c)
 //   dose += dt/60 * R^(43 - T'),  R = 0.5 for T' >= 43 else 0.25 (evaluated as exp2).   Faces of the volume keep their temperature.
-// Bound: HBM. One step moves T read + write, q read, dose RMW, uint8 ids: ~21 B per voxel; the default path takes FOUR steps per
+// Bound: HBM. One step moves T read + write, q read, dose RMW, uint8 ids (uint16 for lists of more than 256 materials, below): ~21 B per voxel; the default path takes FOUR steps per
 // launch (round 6: bhte_stepNg; stretches it cannot take go to the two-step kernel bhte_step2g and the one-step kernel) and moves those bytes
 // once for all of them. x-fastest layout.
 #include "bfd_internal.h"
@@ -20,7 +20,24 @@
 // steps per pass of the default path (bhte_stepNg): four (bhte_run_core says how that was chosen)
 constexpr int BFD_BHTE_STEPS_HEATING = 4, BFD_BHTE_STEPS_COOLING = 4;
 
+// Material ids. Up to 256 materials take 8-bit ids (bfd_bhte_run*, the kernels and bits of every round so far). A CT-derived list holds up
+// to 2^10 bone bins behind 3 or 6 soft tissues (1030 rows), so bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16 take 16-bit ids: every kernel
+// that reads `mat` is written once over the id type (a *_body template) and instantiated by two __global__ overloads, const unsigned char *mat
+// (the symbols and machine code of before) and const uint16_t *mat. Same expressions in the same order for both.
+// The limit of the wide path is the coefficient table the multi-step kernels keep in LDS (float2 per material). The largest user is the four-step
+// cooling kernel: 4 levels x 2 x 2160 cells x 4 B = 69,120 B of plane buffers, 512 threads, TWO workgroups per CU, so 81,920 B of the 160 KiB
+// each; 1,536 entries make 81,408 B, which the compiler still reports at 4 waves/SIMD (two workgroups; profiles/r12). 1,030 are needed.
+#define BFD_BHTE_MAX_MATERIALS 1536
+constexpr int BFD_LDS_PER_CU = 160 * 1024;    // gfx950; a target with less (64 KiB before it) cannot hold the four-step planes at all
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "bfd_bhte.hip sizes its LDS (plane buffers + coefficient table) for the 160 KiB per CU of gfx950"
+#endif
+
 namespace {
+
+template <typename ID> struct IdTab;
+template <> struct IdTab<unsigned char> { static constexpr int N = 256, BITS = 8; typedef unsigned Queue; };                       // four planes' ids in one register
+template <> struct IdTab<uint16_t> { static constexpr int N = BFD_BHTE_MAX_MATERIALS, BITS = 16; typedef unsigned long long Queue; };  // ... in two
 
 // uni() / F4(): (wave-uniform plane base) + (32-bit byte offset in a VGPR), from bfd_device.h
 
@@ -47,8 +64,8 @@ __device__ __forceinline__ float bhte_dose_rate(float Tn, float dtMin)
     // cell); such a term (T' < -20 degC) is 1e-38 of a minute and flushes to zero here
     return __fmul_rn(dtMin, __builtin_amdgcn_exp2f(Tn >= 43.0f ? -e : -2.0f * e));
 }
-template <bool REV>
-__device__ __forceinline__ float bhte_cell(const float *__restrict__ Tin, const float *__restrict__ q, const unsigned char *__restrict__ mat,
+template <bool REV, typename ID>
+__device__ __forceinline__ float bhte_cell(const float *__restrict__ Tin, const float *__restrict__ q, const ID *__restrict__ mat,
                                            const float *__restrict__ cd, const float *__restrict__ cp, int i, int j, int k, int N1, int N2, int N3,
                                            float Tcore)
 {
@@ -60,11 +77,11 @@ __device__ __forceinline__ float bhte_cell(const float *__restrict__ Tin, const 
 }
 
 // One step, one thread per voxel (odd step counts, BFD_BHTE_FUSE=0). q == nullptr: no heating in this step.
-template <bool REV>
-__global__ __launch_bounds__(256) void bhte_step(const float *__restrict__ Tin, float *__restrict__ Tout, float *__restrict__ dose,
-                                                 const float *__restrict__ q, const unsigned char *__restrict__ mat,
-                                                 const float *__restrict__ cd, const float *__restrict__ cp,
-                                                 int N1, int N2, int N3, float Tcore, float dtMin)
+#define B1_ARGS(ID) const float *__restrict__ Tin, float *__restrict__ Tout, float *__restrict__ dose, const float *__restrict__ q, const ID *__restrict__ mat, \
+                    const float *__restrict__ cd, const float *__restrict__ cp, int N1, int N2, int N3, float Tcore, float dtMin
+#define B1_PASS Tin, Tout, dose, q, mat, cd, cp, N1, N2, N3, Tcore, dtMin
+template <bool REV, typename ID>
+__device__ __forceinline__ void bhte_step_body(B1_ARGS(ID))
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i >= N1 || j >= N2) return;
@@ -76,6 +93,8 @@ __global__ __launch_bounds__(256) void bhte_step(const float *__restrict__ Tin, 
     // memory-side cache), the dose array in another memory region than T
     dose[c] = __fadd_rn(dose[c], bhte_dose_rate(Tn, dtMin));
 }
+template <bool REV> __global__ __launch_bounds__(256) void bhte_step(B1_ARGS(unsigned char)) { bhte_step_body<REV>(B1_PASS); }
+template <bool REV> __global__ __launch_bounds__(256) void bhte_step(B1_ARGS(uint16_t)) { bhte_step_body<REV>(B1_PASS); }
 
 // Two steps per launch, round-3 form (BFD_BHTE_KERNEL=1; the default is bhte_step2g below). One step moves 21 B per voxel (T in, T out, dose in and out, heat source, material id) for ~12
 // flops; two steps in one pass move the same 21 B: T(n) in, T(n+2) out, the dose read once and written once with both
@@ -89,14 +108,15 @@ constexpr int B2_W = 68, B2_H = 30, B2_TY = B2_H - 4, B2_T = 512, B2_NC = 4, B2_
 // all of them at the top, or one plane ahead (before or after the barrier, +6 VGPRs: 6 waves/SIMD instead of 7) was measured
 // slower: 312-319 / 338-347 against 374-392 Gvoxel-steps/s at 384^3 (profiles/r3/bhte_two_steps_per_launch.txt).
 // Addressing: plane bases are wave-uniform (scalar registers), every cell keeps one unsigned 32-bit offset inside the plane.
-#define B2_ARGS const float *__restrict__ Tin, float *__restrict__ Tout, float *__restrict__ dose, const float *__restrict__ qa, const float *__restrict__ qb, \
-                const unsigned char *__restrict__ mat, const float *__restrict__ cd, const float *__restrict__ cp, int nMat, int N1, int N2, int N3, float Tcore, \
+#define B2_ARGS(ID) const float *__restrict__ Tin, float *__restrict__ Tout, float *__restrict__ dose, const float *__restrict__ qa, const float *__restrict__ qb, \
+                const ID *__restrict__ mat, const float *__restrict__ cd, const float *__restrict__ cp, int nMat, int N1, int N2, int N3, float Tcore, \
                 float dtMin, int zrun, int tilesX, int tilesY, int nBlocks, int xcdOrder
-template <bool REV>
-__device__ __forceinline__ void bhte_step2_body(int b, B2_ARGS)
+#define B2_PASS Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder
+template <bool REV, typename ID>
+__device__ __forceinline__ void bhte_step2_body(int b, B2_ARGS(ID))
 {
     __shared__ float A[2][B2_NC * B2_T], B[2][B2_NC * B2_T];
-    __shared__ float sCd[256], sCp[256];
+    __shared__ float sCd[IdTab<ID>::N], sCp[IdTab<ID>::N];
     const int tid = threadIdx.x;
     for (int m = tid; m < nMat; m += B2_T) { sCd[m] = cd[m]; sCp[m] = cp[m]; }
     const int bx = b % tilesX, by = (b / tilesX) % tilesY, bz = b / (tilesX * tilesY);
@@ -104,7 +124,7 @@ __device__ __forceinline__ void bhte_step2_body(int b, B2_ARGS)
     const long pl = (long)N1 * N2;
 
     // flags: bit 0 inside the volume, 1 T(n+1) computed here (off the x / y faces), 2 output cell, 3 on an x / y face;
-    // bits 8-15: material id of the cell one plane down
+    // bits 8 and up: material id of the cell one plane down
     unsigned off[B2_NC], flags[B2_NC];
     float t0m[B2_NC], t0c[B2_NC], t1m[B2_NC], t1c[B2_NC], qprev[B2_NC];
     #pragma unroll
@@ -129,7 +149,7 @@ __device__ __forceinline__ void bhte_step2_body(int b, B2_ARGS)
         const long cp0 = (long)__builtin_amdgcn_readfirstlane(p) * pl;                              // wave-uniform plane bases
         const float *TinUp = Tin + cp0 + pl, *qaP = qa ? qa + cp0 : nullptr, *qbO = qb ? qb + cp0 - pl : nullptr;
         float *doseO = dose + cp0 - pl, *ToutO = Tout + cp0 - pl;
-        const unsigned char *matP = mat + cp0;
+        const ID *matP = mat + cp0;
         #pragma unroll
         for (int n = 0; n < B2_NC; n++) {
             t0p[n] = (p + 1 < N3 && (flags[n] & 1u)) ? F4(TinUp, off[n]) : 0.0f;
@@ -173,12 +193,8 @@ __device__ __forceinline__ int xcd_block(int nBlocks, int xcdOrder)
     return b;
 }
 
-template <bool REV>
-__global__ __launch_bounds__(B2_T) void bhte_step2(B2_ARGS)
-{
-    const int b = xcd_block(nBlocks, xcdOrder);
-    bhte_step2_body<REV>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
-}
+template <bool REV> __global__ __launch_bounds__(B2_T) void bhte_step2(B2_ARGS(unsigned char)) { bhte_step2_body<REV>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
+template <bool REV> __global__ __launch_bounds__(B2_T) void bhte_step2(B2_ARGS(uint16_t)) { bhte_step2_body<REV>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
 
 // ---- round 4: the same two steps with loads that stay in flight (bhte_step2g, the default; BFD_BHTE_KERNEL=1 selects bhte_step2) ----
 // What the ISA of bhte_step2 shows: its loads are FLAT instructions -- they count on lgkmcnt as well, so every wait for an LDS read
@@ -205,16 +221,19 @@ template <typename T> __device__ __forceinline__ BFD_GA const T *gbase(const T *
 __device__ __forceinline__ unsigned gpin(unsigned v) { asm("" : "+v"(v)); return v; }
 __device__ __forceinline__ float gl4(const float *b, unsigned ofs) { return *(BFD_GA const float *)((BFD_GA const char *)gbase(b) + ofs); }
 __device__ __forceinline__ unsigned gl1(const unsigned char *b, unsigned ofs) { return *(BFD_GA const unsigned char *)((BFD_GA const unsigned char *)gbase(b) + ofs); }
+// the id of the cell whose float lies at byte offset ofs4 of its plane
+__device__ __forceinline__ unsigned glid(const unsigned char *b, unsigned ofs4) { return gl1(b, ofs4 >> 2); }
+__device__ __forceinline__ unsigned glid(const uint16_t *b, unsigned ofs4) { return *(BFD_GA const uint16_t *)((BFD_GA const char *)gbase(b) + (ofs4 >> 1)); }
 __device__ __forceinline__ void gs4(float *b, unsigned ofs, float v) { *(BFD_GA float *)((BFD_GA char *)gbase((const float *)b) + ofs) = v; }
 template <int K> struct Ph3 { static constexpr int v = K; };
 
 // QM: 0 no heating in either step, 1 the same heat source in both, 2 anything else (qa / qb independent, either may be null)
-template <bool REV, int QM>
-__device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
+template <bool REV, int QM, typename ID>
+__device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS(ID))
 {
     // one row of margin before and behind each tile: the ring cells read "neighbours" there (never used)
     __shared__ float A[2][G2_CELLS + 2 * G2_W], B[2][G2_CELLS + 2 * G2_W];
-    __shared__ float2 sC[256];
+    __shared__ float2 sC[IdTab<ID>::N];
     for (int m = threadIdx.x; m < nMat; m += G2_T) sC[m] = make_float2(cd[m], cp[m]);
     // 476 threads own the 4 x 476 region cells; the last 36 repeat the work of threads 0..35 without storing (same LDS values)
     const bool mirror = threadIdx.x >= G2_ACT;
@@ -257,7 +276,7 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
         t0[n][2] = gl4(Tin + clampz(p0 - 1), gp);
         t0[n][0] = gl4(Tin + clampz(p0), gp);
         t0[n][1] = gl4(Tin + clampz(p0 + 1), gp);
-        mi[n][0] = gl1(mat + clampz(p0), gp >> 2);
+        mi[n][0] = glid(mat + clampz(p0), gp);
         qv[n][0] = QM ? gl4(qaE + clampz(p0), gp) : 0.0f;
         t1[n][0] = t1[n][1] = t1[n][2] = 0.0f; mi[n][1] = mi[n][2] = 0u; qv[n][1] = qv[n][2] = 0.0f;
     }
@@ -296,7 +315,7 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
         const long kN = clampz(p + 1), kNN = clampz(p + 2);
         #pragma unroll
         for (int n = 0; n < G2_NC; n++) {
-            mi[n][p1] = gl1(mat + kN, g[n] >> 2);
+            mi[n][p1] = glid(mat + kN, g[n]);
             if (QM) qv[n][p1] = gl4(qaE + kN, g[n]);
             t0[n][m1] = gl4(Tin + kNN, g[n]);
         }
@@ -324,12 +343,11 @@ __device__ __forceinline__ void bhte_step2g_body(int b, B2_ARGS)
 }
 
 constexpr int G2_WAVES = 6;  // waves per SIMD the register budget is held to (6: 80 VGPRs, three workgroups per CU)
-template <bool REV, int QM>
-__global__ __launch_bounds__(G2_T, G2_WAVES) void bhte_step2g(B2_ARGS)
-{
-    const int b = xcd_block(nBlocks, xcdOrder);
-    bhte_step2g_body<REV, QM>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
-}
+template <bool REV, int QM> __global__ __launch_bounds__(G2_T, G2_WAVES) void bhte_step2g(B2_ARGS(unsigned char)) { bhte_step2g_body<REV, QM>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
+// 16-bit ids: held to 4 waves per SIMD (128 registers, two workgroups per CU) instead of 6 -- at 80 registers the heating flavours spill 2 / 4 registers to
+// scratch (as their 8-bit twins do), and the kernel runs at the memory system's rate with one to three workgroups per CU alike (bhte_run_core)
+constexpr int G2_WAVES_WIDE = 4;
+template <bool REV, int QM> __global__ __launch_bounds__(G2_T, G2_WAVES_WIDE) void bhte_step2g(B2_ARGS(uint16_t)) { bhte_step2g_body<REV, QM>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
 // ---- round 6: S = 3 or 4 steps per pass (bhte_stepNg) ----
 // Two steps per pass move T in / out, the dose in / out, the heat source and the ids once for two steps (10.5 B per voxel-step while heating); S steps
 // move them once for S. Same machinery as bhte_step2g, one more level of it per step: a workgroup marches a z-run over a region of (64 + 2 S) x 28
@@ -347,13 +365,14 @@ __global__ __launch_bounds__(G2_T, G2_WAVES) void bhte_step2g(B2_ARGS)
 // flavours that fit anyway are faster with four (cooling, S = 4: 728 / 805 against 651 / 734) -- so the heating flavour of S = 4 takes two, the rest four.
 template <int QM, int S> struct GNCells { static constexpr int v = (QM == 1 && S == 4) ? 2 : 4; };
 template <int S, int NCELLS> struct GN { static constexpr int W = 64 + 2 * S, H = 28, TY = H - 2 * S, NC = NCELLS, T = 2048 / NC, ROWS = H / NC, ACT = ROWS * W, CELLS = W * H; };
-template <bool REV, int QM, int S>
-__device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
+template <bool REV, int QM, int S, typename ID>
+__device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS(ID))
 {
     using G = GN<S, GNCells<QM, S>::v>;
     static_assert(G::ACT <= G::T && S >= 3 && S <= 4, "region / thread mapping");
     __shared__ float L[S][2][G::CELLS + 2 * G::W];
-    __shared__ float2 sC[256];
+    __shared__ float2 sC[IdTab<ID>::N];
+    static_assert((sizeof(L) + sizeof(sC)) * (G::T == 512 ? 2 : 1) <= BFD_LDS_PER_CU, "plane buffers + coefficient table: two workgroups of 512 threads (one of 1024) per CU");
     for (int m = threadIdx.x; m < nMat; m += G::T) sC[m] = make_float2(cd[m], cp[m]);
     const bool mirror = threadIdx.x >= G::ACT;
     const int tid = mirror ? threadIdx.x - G::ACT : threadIdx.x;
@@ -382,7 +401,8 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
 
     float t[S][G::NC][3];                 // level k (T(n + k)), planes by slot (plane - p0) mod 3
     float q[G::NC][S], qn[G::NC];         // heat source of planes p, p - 1, ..., p - S + 1; of plane p + 1 on its way
-    unsigned mi[G::NC], mn[G::NC];        // ids of planes p .. p - 3 as bytes; of plane p + 1 on its way
+    typename IdTab<ID>::Queue mi[G::NC];  // ids of planes p .. p - 3, IdTab<ID>::BITS each (8-bit ids: one register, 16-bit: two)
+    unsigned mn[G::NC];                   // id of plane p + 1 on its way
     const int p0 = z0 - (S - 1);
     #pragma unroll
     for (int n = 0; n < G::NC; n++) {
@@ -391,7 +411,7 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
         t[0][n][2] = gl4(Tin + clampz(p0 - 1), gp);
         t[0][n][0] = gl4(Tin + clampz(p0), gp);
         t[0][n][1] = gl4(Tin + clampz(p0 + 1), gp);
-        mi[n] = gl1(mat + clampz(p0), gp >> 2);
+        mi[n] = glid(mat + clampz(p0), gp);
         q[n][0] = QM ? gl4(qE + clampz(p0), gp) : 0.0f;
         #pragma unroll
         for (int k = 1; k < S; k++) { t[k][n][0] = t[k][n][1] = t[k][n][2] = 0.0f; q[n][k] = 0.0f; }
@@ -427,7 +447,7 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
                 const int e = e0 + n * G::ACT;
                 const int sc = ((c - k + 1) % 3 + 3) % 3, sm = ((c - k) % 3 + 3) % 3, sp = ((c - k + 2) % 3 + 3) % 3;
                 const float tc = t[k - 1][n][sc];
-                const float2 cc = sC[(mi[n] >> (8 * (k - 1))) & 255u];
+                const float2 cc = sC[(unsigned)(mi[n] >> (IdTab<ID>::BITS * (k - 1))) & ((1u << IdTab<ID>::BITS) - 1u)];
                 float U = bhte_update<REV>(tc, Lp[e - 1], Lp[e + 1], Lp[e - G::W], Lp[e + G::W], t[k - 1][n][sm], t[k - 1][n][sp], cc.x, cc.y, Tcore, heat, q[n][k - 1]);
                 asm volatile("" : "+v"(U));                                         // computed by every lane, selected below
                 const float val = (innerz && fIn[n] && dist[n] >= k) ? U : tc;
@@ -452,7 +472,7 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
                 const long kN = clampz(p + 1), kNN = clampz(p + 2);
                 #pragma unroll
                 for (int n = 0; n < G::NC; n++) {
-                    mn[n] = gl1(mat + kN, g[n] >> 2);
+                    mn[n] = glid(mat + kN, g[n]);
                     if (QM) qn[n] = gl4(qE + kN, g[n]);
                     t[0][n][(c + 2) % 3] = gl4(Tin + kNN, g[n]);
                 }
@@ -460,7 +480,7 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
         }
         #pragma unroll
         for (int n = 0; n < G::NC; n++) {
-            mi[n] = (mi[n] << 8) | mn[n];
+            mi[n] = (mi[n] << IdTab<ID>::BITS) | mn[n];
             #pragma unroll
             for (int k = S - 1; k >= 1; k--) q[n][k] = q[n][k - 1];
             q[n][0] = qn[n];
@@ -474,119 +494,33 @@ __device__ __forceinline__ void bhte_stepNg_body(int b, B2_ARGS)
 }
 
 constexpr int GN_WAVES = 4;  // 128 registers: two workgroups of 8 waves per CU, or one of 16
-template <bool REV, int QM, int S>
-__global__ __launch_bounds__((GN<S, GNCells<QM, S>::v>::T), GN_WAVES) void bhte_stepNg(B2_ARGS)
-{
-    const int b = xcd_block(nBlocks, xcdOrder);
-    bhte_stepNg_body<REV, QM, S>(b, Tin, Tout, dose, qa, qb, mat, cd, cp, nMat, N1, N2, N3, Tcore, dtMin, zrun, tilesX, tilesY, nBlocks, xcdOrder);
-}
+template <bool REV, int QM, int S> __global__ __launch_bounds__((GN<S, GNCells<QM, S>::v>::T), GN_WAVES) void bhte_stepNg(B2_ARGS(unsigned char)) { bhte_stepNg_body<REV, QM, S>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
+template <bool REV, int QM, int S> __global__ __launch_bounds__((GN<S, GNCells<QM, S>::v>::T), GN_WAVES) void bhte_stepNg(B2_ARGS(uint16_t)) { bhte_stepNg_body<REV, QM, S>(xcd_block(nBlocks, xcdOrder), B2_PASS); }
 
-// Monitor points of the intermediate steps of an S-step pass: T(n + depth) at the listed voxels from T(n), depth 1 .. 3 -- the cube of side
-// 2 depth + 1 around the voxel advanced level by level in LDS (one workgroup per point; the caller monitors 1 - 4 points,
-// CalculateTemperatureEffects.py:1003-1023). The same cell update as everywhere: equal to the value a one-step run would hold.
-template <bool REV>
-__global__ __launch_bounds__(64) void cone_points(const float *__restrict__ Tin, const float *__restrict__ q, const unsigned char *__restrict__ mat,
-                                                  const float *__restrict__ cd, const float *__restrict__ cp, int N1, int N2, int N3, float Tcore,
-                                                  const unsigned *__restrict__ idx, float *__restrict__ out, long stride, long col, int depth)
-{
-    __shared__ float A[2][343];
-    const int side = 2 * depth + 1, ncell = side * side * side;
-    const unsigned c0 = idx[blockIdx.x];
-    const int ci = (int)(c0 % (unsigned)N1), cj = (int)((c0 / (unsigned)N1) % (unsigned)N2), ck = (int)(c0 / ((unsigned)N1 * (unsigned)N2));
-    const long pl = (long)N1 * N2;
-    for (int v = threadIdx.x; v < ncell; v += 64) {
-        const int li = v % side, lj = (v / side) % side, lk = v / (side * side);
-        const int i = min(max(ci - depth + li, 0), N1 - 1), j = min(max(cj - depth + lj, 0), N2 - 1), k = min(max(ck - depth + lk, 0), N3 - 1);
-        A[0][v] = Tin[(long)k * pl + (long)j * N1 + i];
-    }
-    __syncthreads();
-    for (int lev = 1; lev <= depth; lev++) {
-        const float *src = A[(lev - 1) & 1]; float *dst = A[lev & 1];
-        for (int v = threadIdx.x; v < ncell; v += 64) {
-            const int li = v % side, lj = (v / side) % side, lk = v / (side * side);
-            float val = src[v];
-            if (li >= lev && li < side - lev && lj >= lev && lj < side - lev && lk >= lev && lk < side - lev) {
-                const int i = ci - depth + li, j = cj - depth + lj, k = ck - depth + lk;
-                if (i > 0 && i < N1 - 1 && j > 0 && j < N2 - 1 && k > 0 && k < N3 - 1) {       // inside the volume and off its faces: all six neighbours exist
-                    const long c = (long)k * pl + (long)j * N1 + i;
-                    const int m = mat[c];
-                    val = bhte_update<REV>(src[v], src[v - 1], src[v + 1], src[v - side], src[v + side], src[v - side * side], src[v + side * side], cd[m], cp[m], Tcore,
-                                           q != nullptr, q ? q[c] : 0.0f);
-                }
-            }
-            dst[v] = val;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[(long)blockIdx.x * stride + col] = A[depth & 1][(depth * side + depth) * side + depth];
-}
-
-// The monitored plane at a step INSIDE a pass: T(n + depth) on the row j = jsel for a patch of 16 x 16 cells in (i, k), from T(n) -- the slab of
-// (16 + 2 depth) x (2 depth + 1) x (16 + 2 depth) cells around the patch advanced level by level in LDS, like cone_points does for a cube. One sample of
-// a 320 x 320 plane at depth 3 costs 400 workgroups x 3388 cells: a few per cent of one volume step, once per nFactorMonitoring steps.
-template <bool REV>
-__global__ __launch_bounds__(256) void cone_slice(const float *__restrict__ Tin, const float *__restrict__ q, const unsigned char *__restrict__ mat,
-                                                  const float *__restrict__ cd, const float *__restrict__ cp, int N1, int N2, int N3, float Tcore,
-                                                  float *__restrict__ out, int jsel, long sample, long nSamples, int depth)
-{
-    __shared__ float A[2][22 * 7 * 22];
-    const int sx = 16 + 2 * depth, sy = 2 * depth + 1, sz = 16 + 2 * depth, ncell = sx * sy * sz;
-    const int i0 = blockIdx.x * 16 - depth, j0 = jsel - depth, k0 = blockIdx.y * 16 - depth;
-    const long pl = (long)N1 * N2;
-    for (int v = threadIdx.x; v < ncell; v += 256) {
-        const int li = v % sx, lj = (v / sx) % sy, lk = v / (sx * sy);
-        const int i = min(max(i0 + li, 0), N1 - 1), j = min(max(j0 + lj, 0), N2 - 1), k = min(max(k0 + lk, 0), N3 - 1);
-        A[0][v] = Tin[(long)k * pl + (long)j * N1 + i];
-    }
-    __syncthreads();
-    for (int lev = 1; lev <= depth; lev++) {
-        const float *src = A[(lev - 1) & 1]; float *dst = A[lev & 1];
-        for (int v = threadIdx.x; v < ncell; v += 256) {
-            const int li = v % sx, lj = (v / sx) % sy, lk = v / (sx * sy);
-            float val = src[v];
-            if (li >= lev && li < sx - lev && lj >= lev && lj < sy - lev && lk >= lev && lk < sz - lev) {
-                const int i = i0 + li, j = j0 + lj, k = k0 + lk;
-                if (i > 0 && i < N1 - 1 && j > 0 && j < N2 - 1 && k > 0 && k < N3 - 1) {
-                    const long c = (long)k * pl + (long)j * N1 + i;
-                    const int m = mat[c];
-                    val = bhte_update<REV>(src[v], src[v - 1], src[v + 1], src[v - sx], src[v + sx], src[v - sx * sy], src[v + sx * sy], cd[m], cp[m], Tcore,
-                                           q != nullptr, q ? q[c] : 0.0f);
-                }
-            }
-            dst[v] = val;
-        }
-        __syncthreads();
-    }
-    const float *res = A[depth & 1];
-    const int li = depth + (int)(threadIdx.x & 15), lk = depth + (int)(threadIdx.x >> 4);
-    const int i = i0 + li, k = k0 + lk;
-    if (i < N1 && k < N3) out[(REV ? (long)k * N1 + i : (long)i * N3 + k) * nSamples + sample] = res[(lk * sy + depth) * sx + li];
-}
+// what every monitor kernel starts with
+#define BM_ARGS(ID) const float *__restrict__ Tin, const float *__restrict__ q, const ID *__restrict__ mat, const float *__restrict__ cd, const float *__restrict__ cp, \
+                    int N1, int N2, int N3, float Tcore
+#define BM_PASS Tin, q, mat, cd, cp, N1, N2, N3, Tcore
+// cone_points, cone_slice (monitors of the steps inside an S-step pass) and step_slice, for 8-bit and for 16-bit ids
+#define BHTE_ID unsigned char
+#include "bfd_bhte_monitors.inc"
+#undef BHTE_ID
+#define BHTE_ID uint16_t
+#include "bfd_bhte_monitors.inc"
+#undef BHTE_ID
 
 // Monitors of the first of two fused steps: T(n+1) at the listed voxels / on the monitored plane, computed from T(n)
-template <bool REV>
-__global__ void step_points(const float *__restrict__ Tin, const float *__restrict__ q, const unsigned char *__restrict__ mat,
-                            const float *__restrict__ cd, const float *__restrict__ cp, int N1, int N2, int N3, float Tcore,
-                            const unsigned *__restrict__ idx, float *__restrict__ out, long n, long stride, long col)
+template <bool REV, typename ID>
+__device__ __forceinline__ void step_points_body(BM_ARGS(ID), const unsigned *__restrict__ idx, float *__restrict__ out, long n, long stride, long col, long t)      // t: the kernel's global thread index
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const unsigned c = idx[t];
     const int i = (int)(c % (unsigned)N1), j = (int)((c / (unsigned)N1) % (unsigned)N2), k = (int)(c / ((unsigned)N1 * (unsigned)N2));
     out[t * stride + col] = bhte_cell<REV>(Tin, q, mat, cd, cp, i, j, k, N1, N2, N3, Tcore);
 }
-template <bool REV>
-__global__ void step_slice(const float *__restrict__ Tin, const float *__restrict__ q, const unsigned char *__restrict__ mat,
-                           const float *__restrict__ cd, const float *__restrict__ cp, int N1, int N2, int N3, float Tcore,
-                           float *__restrict__ out, int jsel, long sample, long nSamples)
-{
-    const long n = (long)N1 * N3;
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x) {
-        const int i = (int)(v % N1), k = (int)(v / N1);
-        out[(REV ? (long)k * N1 + i : (long)i * N3 + k) * nSamples + sample] = bhte_cell<REV>(Tin, q, mat, cd, cp, i, jsel, k, N1, N2, N3, Tcore);
-    }
-}
-
+#define SP_TAIL const unsigned *__restrict__ idx, float *__restrict__ out, long n, long stride, long col
+template <bool REV> __global__ void step_points(BM_ARGS(unsigned char), SP_TAIL) { step_points_body<REV>(BM_PASS, idx, out, n, stride, col, (long)blockIdx.x * blockDim.x + threadIdx.x); }
+template <bool REV> __global__ void step_points(BM_ARGS(uint16_t), SP_TAIL) { step_points_body<REV>(BM_PASS, idx, out, n, stride, col, (long)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void gather_points(const float *__restrict__ T, const unsigned *__restrict__ idx, float *__restrict__ out, long n, long stride, long col)
 {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -602,18 +536,24 @@ __global__ void gather_slice(const float *__restrict__ T, float *__restrict__ ou
     }
 }
 
-__global__ void table_lookup(const unsigned char *__restrict__ mat, const float *__restrict__ tab, float *__restrict__ out, size_t n)
+template <typename ID>
+__device__ __forceinline__ void table_lookup_body(const ID *mat, const float *tab, float *out, size_t n, size_t first, size_t stride)
 {
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) out[v] = tab[mat[v]];
+    for (size_t v = first; v < n; v += stride) out[v] = tab[mat[v]];
 }
+__global__ void table_lookup(const unsigned char *__restrict__ mat, const float *__restrict__ tab, float *__restrict__ out, size_t n) { table_lookup_body(mat, tab, out, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x); }
+__global__ void table_lookup(const uint16_t *__restrict__ mat, const float *__restrict__ tab, float *__restrict__ out, size_t n) { table_lookup_body(mat, tab, out, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x); }
 // heat increment of one ON step from the pressure amplitude: q = (p p) qf[m], float32 with the oracle's roundings
-__global__ void heat_source(const float *p, const unsigned char *__restrict__ mat, const float *__restrict__ qf, float *q, size_t n)      // q may be p
+template <typename ID>
+__device__ __forceinline__ void heat_source_body(const float *p, const ID *mat, const float *qf, float *q, size_t n, size_t first, size_t stride)      // q may be p
 {
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    for (size_t v = first; v < n; v += stride) {
         const float a = p[v];
         q[v] = __fmul_rn(__fmul_rn(a, a), qf[mat[v]]);
     }
 }
+__global__ void heat_source(const float *p, const unsigned char *__restrict__ mat, const float *__restrict__ qf, float *q, size_t n) { heat_source_body(p, mat, qf, q, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x); }
+__global__ void heat_source(const float *p, const uint16_t *__restrict__ mat, const float *__restrict__ qf, float *q, size_t n) { heat_source_body(p, mat, qf, q, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x); }
 
 // np.maximum of one element: a NaN on either side wins
 __device__ __forceinline__ float nan_max(float m, float t) { return (t > m || t != t) ? t : m; }
@@ -642,14 +582,20 @@ __global__ __launch_bounds__(256) void bhte_capture(const float4 *__restrict__ T
 // initT (per material) replaces the upload of T when flags bit 0 is clear; the dose starts from zero when bit 1 is clear.
 // Captures (bfd_bhte_run_protocol; the other entry points pass none): at step boundary captureStep[c] (after step captureStep[c] - 1)
 // Tmax = max(Tmax, T) (the first copies T) and doseCap = dose; no pass crosses a capture boundary.
-template <bool REV>
-static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_t nMat, const unsigned char *mat, const float *cd, const float *cp,
+// ID: the width of the material ids (unsigned char: nMat <= 256; uint16_t: nMat <= BFD_BHTE_MAX_MATERIALS); it selects the kernels' overloads.
+template <bool REV, typename ID>
+static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_t nMat, const ID *mat, const float *cd, const float *cp,
                          const float *qf, const float *initT, int32_t nFields, const float *q, const float *pressure, float *qOut, float *T, float *dose,
                          int32_t flags, float Tcore, double dt, int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
                          float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
                          int32_t nCaptures = 0, const int32_t *captureStep = nullptr, float *Tmax = nullptr, float *doseCap = nullptr)
 {
-    if (F < 3 || M < 3 || S < 3 || nMat < 1 || nMat > 256 || nFields < 1 || !mat || !cd || !cp || (!q && !(pressure && qf)) || !T || !dose || nSteps < 0 ||
+    if (nMat > IdTab<ID>::N) {
+        bfd_set_error("bfd_bhte_run: " + std::to_string(nMat) + " materials, at most " + std::to_string(IdTab<ID>::N) + " with " + std::to_string(IdTab<ID>::BITS) + "-bit ids" +
+                      (sizeof(ID) == 1 ? " (bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16 take up to " + std::to_string(BFD_BHTE_MAX_MATERIALS) + ")" : std::string()));
+        return -1;
+    }
+    if (F < 3 || M < 3 || S < 3 || nMat < 1 || nFields < 1 || !mat || !cd || !cp || (!q && !(pressure && qf)) || !T || !dose || nSteps < 0 ||
         (nSteps > 0 && !fieldOfStep) || (!(flags & 1) && !initT) || nCaptures < 0 || (nCaptures > 0 && !(captureStep && Tmax && doseCap))) {
         bfd_set_error("bfd_bhte_run: bad argument"); return -1;
     }
@@ -672,7 +618,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     const long nSamples = (monitorSlice && sliceJ >= 0) ? (nSteps + fm - 1) / fm : 0;
     float *dT[2] = {nullptr, nullptr}, *dDose = nullptr, *dq = nullptr, *dcd = nullptr, *dcp = nullptr, *dqf = nullptr, *dSlice = nullptr, *dPts = nullptr;
     float *dTmax = nullptr, *dDoseCap = nullptr;
-    unsigned char *dmat = nullptr; unsigned *dIdx = nullptr;
+    ID *dmat = nullptr; unsigned *dIdx = nullptr;
     std::vector<void *> allocs;
     auto A = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) allocs.push_back(*p); return e; };
     // the volumes carry pads (elements): bhte_step2g addresses every cell of its 68 x 28 regions, also those that hang over the faces
@@ -686,7 +632,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     if (e == hipSuccess) e = AP((void **)&dT[1], n, 4);
     if (e == hipSuccess) e = AP((void **)&dDose, n, 4);
     if (e == hipSuccess) e = AP((void **)&dq, n * (size_t)nFields, 4);
-    if (e == hipSuccess) e = AP((void **)&dmat, n, 1);
+    if (e == hipSuccess) e = AP((void **)&dmat, n, sizeof(ID));
     if (e == hipSuccess && nCaptures) e = AP((void **)&dTmax, n, 4);
     if (e == hipSuccess && nCaptures) e = AP((void **)&dDoseCap, n, 4);
     if (e == hipSuccess) e = A((void **)&dcd, nMat * 4);
@@ -694,7 +640,9 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
     if (e == hipSuccess) e = A((void **)&dqf, nMat * 4);
     if (e == hipSuccess && nSamples) e = A((void **)&dSlice, (size_t)N1 * N3 * nSamples * 4);
     if (e == hipSuccess && nPoints && points) { e = A((void **)&dIdx, nPoints * 4); if (e == hipSuccess) e = A((void **)&dPts, (size_t)nPoints * nSteps * 4); }
-    if (e == hipSuccess) e = hipMemcpy(dmat, mat, n, hipMemcpyHostToDevice);
+    // 16-bit ids index the LDS table of the multi-step kernels: the ring cells that lie in the pads must read an id inside it too (any byte is inside the 8-bit table)
+    if (e == hipSuccess && sizeof(ID) > 1) e = hipMemset(dmat - padF, 0, (padF + n + padB) * sizeof(ID));
+    if (e == hipSuccess) e = hipMemcpy(dmat, mat, n * sizeof(ID), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dcd, cd, nMat * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dcp, cp, nMat * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -863,7 +811,7 @@ extern "C" int bfd_bhte_run_fields(int32_t device, int32_t N1, int32_t N2, int32
                                    float *points, double *kernelMs)
 {
     if (!q) { bfd_set_error("bfd_bhte_run: bad argument"); return -1; }
-    return bhte_run_core<false>(device, N1, N2, N3, nMat, mat, cd, cp, nullptr, nullptr, nFields, q, nullptr, nullptr, T, dose, 3, Tcore, dt, nSteps, fieldOfStep,
+    return bhte_run_core<false, unsigned char>(device, N1, N2, N3, nMat, mat, cd, cp, nullptr, nullptr, nFields, q, nullptr, nullptr, T, dose, 3, Tcore, dt, nSteps, fieldOfStep,
                                 sliceJ, nFactorMonitoring, monitorSlice, nPoints, pointIndex, points, kernelMs);
 }
 
@@ -881,7 +829,7 @@ extern "C" int bfd_bhte_run_volumes(int32_t device, int32_t N1, int32_t N2, int3
                                     float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs)
 {
     if (!pressure || !qf) { bfd_set_error("bfd_bhte_run_volumes: bad argument"); return -1; }
-    return bhte_run_core<true>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
+    return bhte_run_core<true, unsigned char>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
                                sliceJ, nFactorMonitoring, monitorSlice, nPoints, pointIndex, points, kernelMs);
 }
 
@@ -897,8 +845,33 @@ extern "C" int bfd_bhte_run_protocol(int32_t device, int32_t N1, int32_t N2, int
                                      int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture)
 {
     if (!pressure || !qf || sliceJ != -1 || nCaptures < 1) { bfd_set_error("bfd_bhte_run_protocol: bad argument"); return -1; }
-    return bhte_run_core<true>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
+    return bhte_run_core<true, unsigned char>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
                                -1, nFactorMonitoring, nullptr, nPoints, pointIndex, points, kernelMs, nCaptures, captureStep, Tmax, doseAtCapture);
+}
+
+// The two calls above for material lists of more than 256 rows (a CT-derived list: up to 1030): 16-bit ids, nMat <= bfd_bhte_max_materials().
+// Same arithmetic in the same order; a list that fits 8 bits gives the same bits through either entry.
+extern "C" int bfd_bhte_max_materials(void) { return BFD_BHTE_MAX_MATERIALS; }
+extern "C" int bfd_bhte_run_volumes16(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const uint16_t *mat,
+                                      const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                                      const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                                      int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                                      float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs)
+{
+    if (!pressure || !qf) { bfd_set_error("bfd_bhte_run_volumes16: bad argument"); return -1; }
+    return bhte_run_core<true, uint16_t>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
+                                         sliceJ, nFactorMonitoring, monitorSlice, nPoints, pointIndex, points, kernelMs);
+}
+extern "C" int bfd_bhte_run_protocol16(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const uint16_t *mat,
+                                       const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                                       const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                                       int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                                       float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                                       int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture)
+{
+    if (!pressure || !qf || sliceJ != -1 || nCaptures < 1) { bfd_set_error("bfd_bhte_run_protocol16: bad argument"); return -1; }
+    return bhte_run_core<true, uint16_t>(device, N3, N2, N1, nMat, mat, cd, cp, qf, initT, nFields, nullptr, pressure, qOut, T, dose, flags, Tcore, dt, nSteps, fieldOfStep,
+                                         -1, nFactorMonitoring, nullptr, nPoints, pointIndex, points, kernelMs, nCaptures, captureStep, Tmax, doseAtCapture);
 }
 
 // One pressure field heating during the first nStepsOn steps (the reference's BHTE call).

@@ -410,6 +410,26 @@ int bfd_bhte_run_protocol(int32_t device, int32_t N1, int32_t N2, int32_t N3, in
                           float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
                           int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture);
 
+/* Material lists of more than 256 rows. A CT-derived plan quantises bone HU to 2^10 bins behind 3 or 6 soft tissues
+ * (BabelDatasetPreps.py:1019-1037, BabelIntegrationBASE.py:1242-1244): MaterialMapCT indexes up to 1030 rows, one thermal row per
+ * bin (CalculateTemperatureEffects.py:804-841). bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16 are bfd_bhte_run_volumes /
+ * bfd_bhte_run_protocol with 16-bit ids: mat = uint16 ids into cd / cp / qf / initT, 1 <= nMat <= bfd_bhte_max_materials()
+ * (1536, the coefficient table the multi-step kernels keep in LDS; more gives -1 and an error text that names the limit);
+ * every other argument, the return codes and the arithmetic are those of the 8-bit twin, which stays the entry for nMat <= 256.
+ * The same problem gives the same bits through either. (The x-fastest entries bfd_bhte_run / bfd_bhte_run_fields are 8-bit only.) */
+int bfd_bhte_max_materials(void);
+int bfd_bhte_run_volumes16(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const uint16_t *mat,
+                           const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                           const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                           int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                           float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs);
+int bfd_bhte_run_protocol16(int32_t device, int32_t N1, int32_t N2, int32_t N3, int32_t nMat, const uint16_t *mat,
+                            const float *cd, const float *cp, const float *qf, const float *initT, int32_t nFields,
+                            const float *pressure, float *qOut, float *T, float *dose, int32_t flags, float Tcore, double dt,
+                            int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                            float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                            int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture);
+
 #ifdef __cplusplus
 }
 #endif

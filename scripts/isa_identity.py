@@ -30,21 +30,29 @@ def kernels(obj, tmp):
         m = re.match(r'^[0-9a-f]+ <(.+)>:$', line)
         if m:
             cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != '...':      # '...': objdump's mark for the zero padding behind a kernel
             cur.append(re.sub(r'\s*//.*$', '', line).strip())
     return out
+
+
+def owner(f):
+    """the source a remark belongs to: an include file of kernels counts for the source it is named after (bfd_bhte_monitors.inc -> bfd_bhte.hip)"""
+    f = os.path.basename(f)
+    if f.endswith('.inc'):
+        f = max((s for s in SRC if f.startswith(s)), key=len) + '.hip'
+    return f
 
 
 def resources(log):
     """remarks of a (possibly parallel) build: per source file in order, Function Name opens a record"""
     res, cur = {}, {}
     for line in open(log, errors='replace'):
-        m = re.match(r'^(\S+?\.hip):\d+:\d+: remark: (.*?) \[-Rpass-analysis=kernel-resource-usage\]', line)
+        m = re.match(r'^(\S+?\.(?:hip|inc)):\d+:\d+: remark: (.*?) \[-Rpass-analysis=kernel-resource-usage\]', line)
         if not m:
             continue
         f, body = m.group(1), m.group(2).strip()
         if body.startswith('Function Name:'):
-            cur[f] = res.setdefault((os.path.basename(f), body.split(':', 1)[1].strip()), [])
+            cur[f] = res.setdefault((owner(f), body.split(':', 1)[1].strip()), [])
         elif f in cur:
             cur[f].append(body)
     return res
