@@ -19,7 +19,6 @@
 #include <thread>
 #include <hipcub/hipcub.hpp>
 
-extern "C" int64_t bfd_placement_cache_release(void);
 static thread_local std::string g_err;
 // pinned 16 MB pieces of copy_out_large, kept from one readback of a call to the next (allocating and releasing eight of them costs 22 ms, as much as
 // moving a 512^3 map); given back to the system with the placement cache (bfd_placement_cache_release: the drop-in call does that at its end)
@@ -52,7 +51,6 @@ static void pin_release_all()
     g_pinFree.clear();
 }
 void bfd_set_error(const std::string &s) { g_err = s; }
-#define BFD_FAIL(code, msg) do { bfd_set_error(msg); return (code); } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // coefficient preparation (float64, rounded once to float32). DESIGN.md "Material model".
@@ -567,7 +565,7 @@ static void drop_step_graph(bfd_sim *s)
     s->stepDevValid = false;
 }
 
-// hipMalloc that gives idle buffers of the placement cache (placement_cache_*) back to the device before it reports that memory ran out
+// hipMalloc that gives idle buffers of the placement cache (bfd_placement.hip) back to the device before it reports that memory ran out
 static hipError_t malloc_or_release_cache(void **q, size_t bytes)
 {
     hipError_t e = hipMalloc(q, bytes);
@@ -611,14 +609,6 @@ int sel_list(uint32_t mask, int *sel)
     int n = 0;
     for (int b = 0; b < BFD_MAP_COUNT; b++) if (mask & (1u << b)) sel[n++] = b;
     return n;
-}
-
-hipEvent_t get_event(bfd_sim *s)
-{
-    hipEvent_t e;
-    if (!s->evPool.empty()) { e = s->evPool.back(); s->evPool.pop_back(); return e; }
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;      // callers skip the timing pair
-    return e;
 }
 
 // number of non-zero edge coefficients A (active shear updates) in the sparse shear list
@@ -735,9 +725,28 @@ void pulse_row_read(bfd_sim *s, int step, hipStream_t st)
 
 static int dft_bin(int n, double d, double freq);
 
+hipEvent_t bfd_get_event(bfd_sim *s)
+{
+    hipEvent_t e;
+    if (!s->evPool.empty()) { e = s->evPool.back(); s->evPool.pop_back(); return e; }
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;      // callers skip the timing pair
+    return e;
+}
+
+void bfd_bind_state_views(bfd_sim *s)
+{
+    bfd_dev &d = s->d;
+    const size_t g = 2 * (size_t)d.plane;
+    float **fp[15] = {&d.Vx, &d.Vy, &d.Vz, &d.Sxx, &d.Syy, &d.Szz, &d.Sxy, &d.Sxz, &d.Syz, &d.Rxx, &d.Ryy, &d.Rzz, &d.Rxy, &d.Rxz, &d.Ryz};
+    for (int a = 0; a < 15; a++) *fp[a] = s->stateBase[a] + g;
+    d.mat = s->matBase + g; d.cls = s->clsBase + g;
+    d.VxW = d.Vx; d.VyW = d.Vy; d.VzW = d.Vz; d.SzzW = d.Szz; d.RzzW = d.Rzz;      // in-place variants: no second copies
+    if (s->pingpong) { d.VxW = s->ppBase[0] + g; d.VyW = s->ppBase[1] + g; d.VzW = s->ppBase[2] + g; d.SzzW = s->ppBase[3] + g; d.RzzW = s->ppBase[4] + g; }
+}
+
 void bfd_kmark(bfd_sim *s, int cls, int end, hipStream_t st)
 {
-    hipEvent_t e = get_event(s);
+    hipEvent_t e = bfd_get_event(s);
     if (!e) return;
     if (!end && (s->evK[cls].size() & 1)) { s->evPool.push_back(e); return; }    // unmatched begin: keep pairs intact
     if (end && !(s->evK[cls].size() & 1)) { s->evPool.push_back(e); return; }
@@ -787,8 +796,6 @@ int bfd_material_tables(int32_t nMat, const double *matlist, const double *qcorr
     return 0;
 }
 
-static bool placement_cache_put(int device, size_t bytes, void *p);
-static void placement_cache_evict_other_sizes(int device, size_t bytes);
 int bfd_create(const bfd_config *cfg, bfd_sim **out)
 {
     if (!cfg || !out) BFD_FAIL(-1, "bfd_create: null argument");
@@ -840,7 +847,7 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     d.ND = cfg->NDelta; d.P = P; d.plane = cfg->N1 * cfg->N2;
     s->nloc = (size_t)d.plane * d.nk;
     s->nalloc = (size_t)d.plane * (d.nk + 4);
-    placement_cache_evict_other_sizes(cfg->device, s->nalloc * sizeof(float));
+    bfd_placement_cache_evict_other_sizes(cfg->device, s->nalloc * sizeof(float));
 
     int rc = 0;
     float **fp[15] = {&d.Vx, &d.Vy, &d.Vz, &d.Sxx, &d.Syy, &d.Szz, &d.Sxy, &d.Sxz, &d.Syz,
@@ -902,7 +909,7 @@ void bfd_destroy(bfd_sim *s)
     for (int b = 0; b < 2; b++) { if (s->evTile[b]) hipEventDestroy(s->evTile[b]); for (int q = 0; q < 2; q++) if (s->evRead[b][q]) hipEventDestroy(s->evRead[b][q]); }
     for (void *p : s->allocs) {
         const bool searched = std::find(s->searched.begin(), s->searched.end(), p) != s->searched.end();
-        if (searched && placement_cache_put(s->cfg.device, s->nalloc * sizeof(float), p)) continue;
+        if (searched && bfd_placement_cache_put(s->cfg.device, s->nalloc * sizeof(float), p)) continue;
         hipFree(p);
     }
     for (hipEvent_t e : s->evPool) hipEventDestroy(e);
@@ -1232,7 +1239,7 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
 }
 
 // where the ten compact arrays live (bfd_tiles::cssHosted); called when the list is built and again whenever the state buffers change hands
-// (choose_placement exchanges them at step 0, when everything is still zero)
+// (bfd_choose_placement exchanges them at step 0, when everything is still zero)
 static void bind_compact_views(bfd_sim *s)
 {
     bfd_dev &d = s->d;
@@ -1772,381 +1779,6 @@ static int build_tile_lists(bfd_sim *s)
     return 0;
 }
 
-// ---- placement of the per-voxel arrays ----------------------------------------------------------------------------------
-// The tiled kernels stream 6 to 20 arrays at the same cell offset. Round 2 found that the same kernels on the same data run
-// 1.50 or 1.70 ms per step at C3 depending on nothing but where hipMalloc put those arrays, and chose among whole sets of
-// allocations by timing the kernels (a lottery). Round 3 found the cause (scripts/ubench_layout.hip, ubench_pairmap.hip;
-// profiles/r3/placement_*): the 288 GB of HBM fall into three contiguous physical regions of about 90 GiB (the ranks of the
-// 12-high stacks, as far as can be told from outside), and streams that advance together are slow when they all lie in ONE
-// region and fast as soon as they are spread over two: every array in one region 0.98 + 0.76 ms for the two fluid proxies,
-// arrays alternating between two regions 0.86 + 0.68 ms, on every draw. A fresh process gets all its allocations from one
-// region, a fragmented device gives a mix -- the lottery's "fast sets".
-// What counts are the arrays a kernel WRITES (mixing experiment of the same benchmark: the stress proxy turns fast when Szz and
-// Rzz lie apart, whatever V does; the velocity proxy when Vx, Vy, Vz and the accumulator are split two and two).
-// So the arrays are placed, not drawn: a pair probe (two arrays updated in place at the same cell offset along the engine's
-// own runs; zeros stay zeros, so it runs on the initial state) tells whether an array lies in the region of the reference
-// array Vx (about 7 % slower) or in another one. The arrays of the stream order Vx Vy Vz Szz Rzz [Sxx ... Ryz] then alternate
-// between "region of Vx" and "another region": first by exchanging buffers among the 15 state arrays (all the same size, all
-// zero), then, if one kind is short, with freshly allocated candidates (misses are held until the search ends, so that the
-// allocator moves on; bounded by the free memory). The Pressure accumulators are re-allocated likewise when they fall on
-// the wrong side. A few dozen probes of well under a millisecond; results do not depend on it.
-// BFD_PLACEMENT=0 (or BFD_PLACEMENT_TRIALS=0, the round-2 name) switches it off; BFD_PLACEMENT_VERBOSE=1 prints what it does.
-// Buffers that a search found in another memory region are kept when their engine is destroyed and offered to the next engine of this
-// process that wants arrays of the same size on the same device (re-probed there: region classes are relative): the two or three solver calls
-// of one RunCases (BASE:2338, 2374, 2401) pay the search once. Bounded (BABELFDTD_PLACEMENT_CACHE_GIB, default 48, 0 = off);
-// bfd_placement_cache_release() frees it.
-struct CachedBuf { int device; size_t bytes; void *p; };
-static std::mutex g_cacheMutex;
-static std::vector<CachedBuf> g_cache;
-// at most BABELFDTD_PLACEMENT_CACHE_GIB (default 48) and never more than an eighth of the device's memory
-static size_t placement_cache_cap()
-{
-    double gib = 48.0;
-    if (const char *ev = getenv("BABELFDTD_PLACEMENT_CACHE_GIB")) gib = atof(ev);
-    size_t cap = gib > 0 ? (size_t)(gib * 1073741824.0) : 0;
-    size_t freeB = 0, totalB = 0;
-    if (cap && hipMemGetInfo(&freeB, &totalB) == hipSuccess && totalB) cap = std::min(cap, totalB / 8);
-    else (void)hipGetLastError();
-    return cap;
-}
-// a new engine on `device` whose state arrays have `bytes` each: cached buffers of any other size are of no use to it and go back to the device
-// before it allocates (they used to wait for the next bfd_destroy)
-static void placement_cache_evict_other_sizes(int device, size_t bytes)
-{
-    std::lock_guard<std::mutex> lk(g_cacheMutex);
-    for (size_t q = 0; q < g_cache.size();) {
-        if (g_cache[q].device == device && g_cache[q].bytes != bytes) { hipFree(g_cache[q].p); g_cache.erase(g_cache.begin() + q); }
-        else q++;
-    }
-    (void)hipGetLastError();
-}
-static size_t placement_cache_bytes(int device)
-{
-    std::lock_guard<std::mutex> lk(g_cacheMutex);
-    size_t held = 0;
-    for (const CachedBuf &c : g_cache) if (c.device == device) held += c.bytes;
-    return held;
-}
-static std::vector<void *> placement_cache_take(int device, size_t bytes)
-{
-    std::lock_guard<std::mutex> lk(g_cacheMutex);
-    std::vector<void *> out;
-    for (size_t q = 0; q < g_cache.size();) {
-        if (g_cache[q].device == device && g_cache[q].bytes == bytes) { out.push_back(g_cache[q].p); g_cache.erase(g_cache.begin() + q); }
-        else q++;
-    }
-    return out;
-}
-// true if the cache took the buffer (the caller must not free it)
-static bool placement_cache_put(int device, size_t bytes, void *p)
-{
-    std::lock_guard<std::mutex> lk(g_cacheMutex);
-    hipSetDevice(device);
-    const size_t cap = placement_cache_cap();
-    // buffers of another size on this device are of no use to the caller that is coming: they make room first
-    for (size_t q = 0; q < g_cache.size();) {
-        if (g_cache[q].device == device && g_cache[q].bytes != bytes) { hipSetDevice(device); hipFree(g_cache[q].p); g_cache.erase(g_cache.begin() + q); }
-        else q++;
-    }
-    size_t held = 0;
-    for (const CachedBuf &c : g_cache) held += c.bytes;
-    if (held + bytes > cap) return false;
-    g_cache.push_back({device, bytes, p});
-    return true;
-}
-
-static void bind_state_views(bfd_sim *s)
-{
-    bfd_dev &d = s->d;
-    const size_t g = 2 * (size_t)d.plane;
-    float **fp[15] = {&d.Vx, &d.Vy, &d.Vz, &d.Sxx, &d.Syy, &d.Szz, &d.Sxy, &d.Sxz, &d.Syz, &d.Rxx, &d.Ryy, &d.Rzz, &d.Rxy, &d.Rxz, &d.Ryz};
-    for (int a = 0; a < 15; a++) *fp[a] = s->stateBase[a] + g;
-    d.mat = s->matBase + g; d.cls = s->clsBase + g;
-    d.VxW = d.Vx; d.VyW = d.Vy; d.VzW = d.Vz; d.SzzW = d.Szz; d.RzzW = d.Rzz;      // in-place variants: no second copies
-    if (s->pingpong) { d.VxW = s->ppBase[0] + g; d.VyW = s->ppBase[1] + g; d.VzW = s->ppBase[2] + g; d.SzzW = s->ppBase[3] + g; d.RzzW = s->ppBase[4] + g; }
-}
-
-// device time of `reps` pair probes of the arrays at a and b (pointers to local plane 0), planes [0, kmax); < 0 on error
-static float time_pair(bfd_sim *s, float *a, float *b, int kmax, int reps)
-{
-    (void)hipGetLastError();                    // a stale error of some earlier call is not this probe's
-    hipEvent_t e0 = get_event(s), e1 = get_event(s);
-    if (!e0 || !e1) { if (e0) s->evPool.push_back(e0); if (e1) s->evPool.push_back(e1); return -1.f; }
-    for (int r = -1; r < reps; r++) {           // r = -1: untimed
-        if (r == 0) hipEventRecord(e0, s->stream);
-        bfd_launch_probe_pair(s->d, s->stream, &s->tiles, a, b, kmax);
-    }
-    hipEventRecord(e1, s->stream);
-    float ms = -1.f;
-    if (hipEventSynchronize(e1) == hipSuccess && hipGetLastError() == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ms /= reps;
-    else ms = -1.f;
-    s->evPool.push_back(e0); s->evPool.push_back(e1);
-    return ms;
-}
-
-static int choose_placement(bfd_sim *s)
-{
-    s->placementNote = "off";
-    bool on = s->placementMode != 0;
-    if (const char *ev = getenv("BFD_PLACEMENT")) on = atoi(ev) != 0;
-    // below ~32 M voxels the arrays a kernel streams (5 x 4 B per voxel and up) fit the 256 MB memory-side cache, where they lie
-    // in DRAM stops mattering, and the probe (0.02 ms at 256^3) cannot tell the regions apart any more
-    size_t minVoxels = (size_t)32 << 20;
-    if (const char *ev = getenv("BFD_PLACEMENT_MIN_VOXELS")) minVoxels = (size_t)atol(ev);      // tests: exercise it on small grids too
-    if (!on) return 0;
-    if (s->step != 0 || s->haloHandedOut || s->cfg.kernelVariant == 1 || s->nloc < minVoxels || s->d.nk < 8 ||
-        s->tiles.nFluid + s->tiles.nSolid == 0) { s->placementNote = "skipped (small grid or arrays already handed out)"; return 0; }
-    // buffers 0-14: the state arrays; 15-19 (variant 4 on a whole domain): the second copies of Vx Vy Vz Szz Rzz, written in
-    // the steps in which the first copies are read
-    const int nBuf = s->pingpong ? 20 : 15;
-    auto bufBase = [&](int a) -> float *& { return a < 15 ? s->stateBase[a] : s->ppBase[a - 15]; };
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    const auto tStart = std::chrono::steady_clock::now();
-    const bool verbose = getenv("BFD_PLACEMENT_VERBOSE") != nullptr;
-    const size_t g = 2 * (size_t)s->d.plane;
-    const int kmax = s->d.nk / 2;
-    const size_t half = (size_t)(s->d.nk - kmax) * s->d.plane;
-    const size_t bytes = s->nalloc * sizeof(float);
-    const int reps = 3;
-    int nProbes = 0;
-    auto pair = [&](float *a, float *b) { nProbes++; return time_pair(s, a, b, kmax, reps); };
-    // Two levels of pair times: "same region" (an array against itself half a slab further on is always one of these) and,
-    // 7-15 % below, "different regions". Their absolute values move with the run lists of the medium, so the threshold is
-    // read off the samples: the five self-pairs and Vx against every other array, sorted; the widest gap below the fastest
-    // self-pair separates the levels if it is wider than 3.5 % (measured gaps: 7-10 %, scatter inside a level up to 5 %
-    // top to bottom but dense); without such a gap every array lies in the region of Vx.
-    float tSame = 0;
-    std::vector<float> samples;
-    for (int a : {0, 1, 2, 5, 11}) {
-        const float t = pair(s->stateBase[a] + g, s->stateBase[a] + g + half);
-        if (t <= 0) BFD_FAIL(-10, "placement: the pair probe failed on the zero state");
-        if (tSame == 0 || t < tSame) tSame = t;
-    }
-    samples.push_back(tSame);
-    std::vector<float> t0(nBuf, 0.f);
-    std::string times;
-    for (int a = 1; a < nBuf; a++) {
-        t0[a] = pair(s->stateBase[0] + g, bufBase(a) + g);
-        if (t0[a] <= 0) BFD_FAIL(-10, "placement: the pair probe failed");
-        if (t0[a] <= tSame) samples.push_back(t0[a]);
-        if (verbose) { char q[48]; snprintf(q, sizeof q, " %d:%.3f", a, t0[a]); times += q; }
-    }
-    std::sort(samples.begin(), samples.end());
-    float thr = 0.95f * samples.front(), widest = 0.f;
-    for (size_t q = 0; q + 1 < samples.size(); q++) {
-        const float gap = samples[q + 1] / samples[q] - 1.0f;
-        if (gap > widest) { widest = gap; if (gap >= 0.035f) thr = 0.5f * (samples[q] + samples[q + 1]); }
-    }
-    // region classes of the 15 state-sized buffers, by comparison with one representative per class
-    struct Buf { float *base; int cls; bool fresh; };
-    std::vector<Buf> pool;
-    std::vector<float *> repOf;                                              // class -> representative (pointer to local plane 0)
-    for (int a = 0; a < nBuf; a++) {
-        Buf b = {bufBase(a), -1, false};
-        for (size_t c = 0; c < repOf.size() && b.cls < 0; c++) {
-            const float t = (c == 0 && a > 0) ? t0[a] : pair(repOf[c], b.base + g);
-            if (t <= 0) BFD_FAIL(-10, "placement: the pair probe failed");
-            if (verbose && c > 0) { char q[48]; snprintf(q, sizeof q, " %d/%zu:%.3f", a, c, t); times += q; }
-            if (t >= thr) b.cls = (int)c;
-        }
-        if (b.cls < 0) { b.cls = (int)repOf.size(); repOf.push_back(b.base + g); }
-        pool.push_back(b);
-    }
-    const bool solids = s->tiles.nSolid > 0 || s->cfg.kernelVariant == 2;
-    // stream order: arrays that a kernel WRITES together are neighbours in this list, and the list alternates between the
-    // most populated region M and "anywhere else":
-    //   velocity kernels write Vx Vy Vz (+ accumulator); stress_fluid Szz Rzz; stress_solid Sxx Syy Szz Rxx Ryy Rzz;
-    //   the sparse shear kernel Sxy Sxz Syz Rxy Rxz Ryz
-    std::vector<int> order = {0, 1, 2, 5, 11};                               // Vx Vy Vz Szz Rzz
-    std::vector<int> side = {0, 1, 0, 1, 0};                                 // 0: region M, 1: elsewhere
-    if (s->pingpong) for (int a = 15; a < 20; a++) { order.push_back(a); side.push_back((a - 15) & 1); }   // the second copies like the first (the sums lie apart from Vz and from its copy)
-    if (solids) { int q = 1; for (int a : {3, 9, 4, 10, 6, 12, 7, 13, 8, 14}) { order.push_back(a); side.push_back(q); q ^= 1; } }   // Sxx Rxx Syy Ryy Sxy Rxy Sxz Rxz Syz Ryz
-    std::string before;
-    for (int a : order) before += (char)('0' + std::min(pool[a].cls, 9));
-    int M = 0;
-    {
-        std::vector<int> cnt(repOf.size(), 0);
-        for (const Buf &b : pool) cnt[b.cls]++;
-        for (size_t c = 0; c < cnt.size(); c++) if (cnt[c] > cnt[M]) M = (int)c;
-    }
-    auto sideOf = [&](const Buf &b) { return b.cls == M ? 0 : 1; };            // 0: region M, 1: elsewhere
-    int need[2] = {0, 0};
-    for (int sd : side) need[sd]++;
-    for (const Buf &b : pool) need[sideOf(b)]--;                              // spare arrays count: their buffers can be exchanged in
-    std::vector<void *> held;                                                // candidates on the side that is not short, spacers: freed at the end
-    size_t heldBytes = 0;
-    bool gaveUp = false;
-    int nFresh = 0;
-    bool probeTells = tSame >= 0.05f;                                          // ms; shorter probes are launch overhead, not memory time
-    // How much throw-away memory the search for another region may hold at a time (candidates that missed + spacers, all freed
-    // before this function returns). A region is up to ~96 GiB wide and a fresh process may start at the beginning of one (boxes
-    // needed 92-160 GiB of candidates), but a solver call must not take the device away from whoever shares it: NOTHING is searched
-    // when other allocations than this engine's are present on the device (another process, the other slabs of a group, a GUI's
-    // bio-heat volumes): the buffers are then only exchanged among themselves. On a device the engine has to itself the search may
-    // hold up to 192 GiB while always leaving 48 GiB of what was free on entry untouched (round 4 had capped it at 64 GiB, which
-    // gives up on some boxes -- C3 85 instead of 91 Gvoxel-steps/s there; since round 5 a successful search is paid once per
-    // process: its buffers are kept for the next engine, placement_cache_*). bfd_set_placement(sim, mode, limitBytes) /
-    // BFD_PLACEMENT_SEARCH_MB set the limit explicitly (then the shared-device rule is off: the caller has decided);
-    // BABELFDTD_PLACEMENT_SEARCH_GIB replaces the 192 GiB.
-    size_t free0 = 0, total0 = 0;
-    if (hipMemGetInfo(&free0, &total0) != hipSuccess) { free0 = total0 = 0; (void)hipGetLastError(); }
-    // what this process keeps from an earlier engine's search (placement_cache_*) is the engine's to take, not somebody else's memory
-    const size_t mine = (size_t)s->devBytes + placement_cache_bytes(s->cfg.device);
-    const size_t others = total0 > free0 + mine ? total0 - free0 - mine : 0;
-    // default bound: 192 GiB, never more than two thirds of what was free on entry (an empty 288 GB device keeps 90 GiB for whoever comes), always
-    // leaving 48 GiB; while it walks the search watches the device's free memory: allocations that are neither this engine's nor the search's
-    // own (another process that started at the same moment) end it at once and everything held goes back
-    size_t heldCap = free0 > ((size_t)48 << 30) ? std::min(std::min((size_t)192 << 30, free0 / 3 * 2), free0 - ((size_t)48 << 30)) : 0;
-    bool defaultRule = true;
-    double searchSeconds = 2.0;                                                // BABELFDTD_PLACEMENT_SEARCH_SECONDS
-    if (const char *ev = getenv("BABELFDTD_PLACEMENT_SEARCH_SECONDS")) searchSeconds = atof(ev);
-    std::string capNote;
-    if (others > ((size_t)6 << 30)) { heldCap = 0; char q[96]; snprintf(q, sizeof q, "; device shared (%.0f GiB of other allocations): no search beyond the own buffers", others / 1073741824.0); capNote = q; }
-    if (const char *ev = getenv("BABELFDTD_PLACEMENT_SEARCH_GIB")) {           // the owner of the device raises (or lowers) the default bound without code
-        const double gib = atof(ev);
-        if (gib >= 0 && others <= ((size_t)6 << 30)) heldCap = std::min((size_t)(gib * 1073741824.0), free0 > ((size_t)48 << 30) ? free0 - ((size_t)48 << 30) : 0);
-    }
-    if (s->placementLimit >= 0) { heldCap = (size_t)s->placementLimit; capNote.clear(); defaultRule = false; }
-    if (const char *ev = getenv("BFD_PLACEMENT_SEARCH_MB")) { probeTells = true; heldCap = (size_t)atol(ev) << 20; capNote.clear(); defaultRule = false; }   // tests: walk a little on any grid
-    if (heldCap == 0) probeTells = false;
-    int nCached = 0;
-    // whatever leaves this function early gives back what the search holds: the misses, the spacers and the fresh buffers no array has taken
-    struct GiveBack {
-        std::vector<void *> *held; std::vector<Buf> *pool; bool armed;
-        ~GiveBack() { if (!armed) return; for (void *h : *held) hipFree(h); for (const Buf &b : *pool) if (b.fresh) hipFree(b.base); (void)hipGetLastError(); }
-    } giveBack{&held, &pool, true};
-    size_t ownFreshBytes = 0;                                                  // fresh buffers drawn below (the cached ones are part of `mine`)
-    if ((need[0] > 0 || need[1] > 0) && tSame >= 0.05f) {                      // first what an earlier engine of this process found
-        for (void *cp : placement_cache_take(s->cfg.device, bytes)) {
-            float *c = (float *)cp;
-            int sd = -1;
-            if (hipMemsetAsync(c, 0, bytes, s->stream) == hipSuccess) { const float t = pair(repOf[M], c + g); if (t > 0) sd = t >= thr ? 0 : 1; }
-            if (sd >= 0 && need[sd] > 0) { pool.push_back({c, sd == 0 ? M : 100 + nFresh, true}); need[sd]--; nFresh++; nCached++; }
-            else { hipStreamSynchronize(s->stream); hipFree(c); }
-        }
-    }
-    while ((need[0] > 0 || need[1] > 0) && !gaveUp && probeTells) {            // draw candidates until both sides have enough
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < 2 * bytes + totalB / 8 || heldBytes + bytes > heldCap) { gaveUp = true; break; }
-        if (defaultRule) {
-            // ... and a clock: what the placement is worth to ONE solver call is a few per cent of its run time, so a search that has walked for longer than
-            // that (seen once: ~6 s in a process that had built and destroyed many engines before) stops and keeps what exchanging gives
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count() > searchSeconds) {
-                gaveUp = true; capNote += "; search ended by its time bound"; break;
-            }
-            const size_t known = mine + heldBytes + ownFreshBytes + others;
-            if (totalB > freeB + known && totalB - freeB - known > ((size_t)6 << 30)) { gaveUp = true; capNote += "; somebody else began to allocate on the device: search ended"; break; }
-        }
-        float *c = nullptr;
-        if (hipMalloc((void **)&c, bytes) != hipSuccess) { (void)hipGetLastError(); gaveUp = true; break; }
-        if (hipMemsetAsync(c, 0, bytes, s->stream) != hipSuccess) { hipFree(c); gaveUp = true; break; }
-        const float t = pair(repOf[M], c + g);
-        if (t <= 0) { hipFree(c); gaveUp = true; break; }
-        const int side = t >= thr ? 0 : 1;
-        if (need[side] > 0) { pool.push_back({c, side == 0 ? M : 100 + nFresh, true}); need[side]--; nFresh++; ownFreshBytes += bytes; continue; }
-        held.push_back(c); heldBytes += bytes;
-        // a region is ~90 GiB wide: walk on in growing strides (an unprobed throw-away block as large as everything held so
-        // far, 4 GiB at most: hipMalloc of 4 GiB takes 0.3 ms, of 16 GiB 650 ms -- scripts/r3/malloc_cost.hip) instead of one
-        // array at a time
-        const size_t stride = std::min(heldBytes, (size_t)4 << 30);
-        void *sp = nullptr;
-        if (heldBytes + stride <= heldCap && hipMemGetInfo(&freeB, &totalB) == hipSuccess && freeB > stride + 2 * bytes + totalB / 8 && hipMalloc(&sp, stride) == hipSuccess) { held.push_back(sp); heldBytes += stride; }
-        else (void)hipGetLastError();
-    }
-    std::vector<char> taken(pool.size(), 0);
-    std::vector<int> slotBuf(nBuf, -1);
-    auto pick = [&](int side, int prefer) -> int {
-        if (!taken[prefer] && sideOf(pool[prefer]) == side) return prefer;
-        for (int pass = 0; pass < 2; pass++)                                   // original buffers first, fresh ones after
-            for (size_t q = 0; q < pool.size(); q++) if (!taken[q] && sideOf(pool[q]) == side && pool[q].fresh == (pass == 1)) return (int)q;
-        return -1;
-    };
-    for (size_t q = 0; q < order.size(); q++) {
-        const int a = order[q];
-        int p = pick(side[q], a);
-        if (p < 0) p = pick(1 - side[q], a);                                   // nothing on the wanted side
-        taken[p] = 1; slotBuf[a] = p;
-    }
-    // the arrays outside the list take what is left of the original buffers; unused fresh ones and the held misses are released
-    for (int a = 0; a < nBuf; a++) {
-        if (slotBuf[a] >= 0) continue;
-        int p = -1;
-        for (size_t q = 0; q < pool.size() && p < 0; q++) if (!taken[q] && !pool[q].fresh) p = (int)q;
-        for (size_t q = 0; q < pool.size() && p < 0; q++) if (!taken[q]) p = (int)q;
-        taken[p] = 1; slotBuf[a] = p;
-    }
-    BFD_HIP(hipStreamSynchronize(s->stream));
-    giveBack.armed = false;                                                   // from here on every buffer has an owner again
-    struct FreeHeld { std::vector<void *> *held; ~FreeHeld() { for (void *h : *held) hipFree(h); held->clear(); } } freeHeld{&held};
-    for (size_t q = 0; q < pool.size(); q++) {
-        if (taken[q]) { if (pool[q].fresh) { s->allocs.push_back(pool[q].base); s->searched.push_back(pool[q].base); } continue; }
-        if (!pool[q].fresh) {                                                 // an original buffer displaced by a fresh one
-            auto it = std::find(s->allocs.begin(), s->allocs.end(), (void *)pool[q].base);
-            if (it != s->allocs.end()) s->allocs.erase(it);
-        }
-        hipFree(pool[q].base);
-    }
-    for (int a = 0; a < nBuf; a++) bufBase(a) = pool[slotBuf[a]].base;
-    bind_state_views(s);
-    // Pressure accumulators: written beside Vx Vy Vz by the velocity kernels: the RMS sums go to another region than Vz, a
-    // peak map beside them to another region than the sums
-    std::string accNote;
-    float *prevRep = s->stateBase[2] + g;
-    for (int which = 0; which < 2; which++) {
-        float **pp = which == 0 ? &s->acc : &s->pk;
-        if (!*pp) continue;
-        int qP = -1;
-        for (int q = 0; q < s->nSelR; q++) if (s->selR[q] == BFD_MAP_PRESSURE) qP = q;
-        if (qP < 0) continue;
-        const size_t accBytes = (size_t)s->nSelR * s->nloc * sizeof(float);
-        float *cur = *pp;
-        float t = pair(prevRep, cur + (size_t)qP * s->nloc);
-        std::vector<void *> miss;
-        size_t missBytes = 0;
-        while (t >= thr && miss.size() < 80 && probeTells) {                  // same region as its neighbour: look for another buffer
-            size_t freeB = 0, totalB = 0;
-            if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < 2 * accBytes + totalB / 8 || missBytes + accBytes > heldCap) break;
-            float *c = nullptr;
-            if (hipMalloc((void **)&c, accBytes) != hipSuccess) { (void)hipGetLastError(); break; }
-            if (hipMemsetAsync(c, 0, accBytes, s->stream) != hipSuccess) { hipFree(c); break; }
-            const float tc = pair(prevRep, c + (size_t)qP * s->nloc);
-            if (tc > 0 && tc < thr) {
-                auto it = std::find(s->allocs.begin(), s->allocs.end(), (void *)cur);
-                if (it != s->allocs.end()) s->allocs.erase(it);
-                hipStreamSynchronize(s->stream);
-                hipFree(cur);
-                cur = c; s->allocs.push_back(c); t = tc;
-            } else {
-                miss.push_back(c); missBytes += accBytes;
-                if (tc <= 0) break;
-                void *sp = nullptr;                                            // walk on, as above
-                const size_t stride = std::min(missBytes, (size_t)4 << 30);
-                if (missBytes + stride <= heldCap && hipMemGetInfo(&freeB, &totalB) == hipSuccess && freeB > stride + 2 * accBytes + totalB / 8 && hipMalloc(&sp, stride) == hipSuccess) { miss.push_back(sp); missBytes += stride; }
-                else (void)hipGetLastError();
-            }
-        }
-        hipStreamSynchronize(s->stream);
-        for (void *m : miss) hipFree(m);
-        *pp = cur;
-        accNote += std::string(which == 0 ? " sums " : " peaks ") + (t > 0 && t < thr ? "apart from" : "WITH") + (which == 0 ? " Vz," : " the sums,");
-        prevRep = cur + (size_t)qP * s->nloc;
-    }
-    BFD_HIP(hipStreamSynchronize(s->stream));
-    const size_t nHeld = held.size();
-    for (void *h : held) hipFree(h);
-    held.clear();
-    std::string after;
-    for (int a : order) { const Buf &b = pool[slotBuf[a]]; after += b.fresh ? (b.cls == M ? 'm' : 'n') : (char)('0' + std::min(b.cls, 9)); }
-    char buf[1024];
-    snprintf(buf, sizeof buf, "arrays placed by memory region (pair probe on the zero state: %d probes, within-region %.3f ms, threshold %.3f ms, gap between the levels %.0f %%; %zu regions seen): "
-             "regions of %s %s -> %s (m / n = fresh allocation in / outside the most populated region),%s %d fresh, %zu candidates / spacers (%.1f GiB) released%s; %.2f s", nProbes, tSame, thr, 100.0 * widest, repOf.size(),
-             (std::string("Vx Vy Vz Szz Rzz") + (s->pingpong ? " + their second copies" : "") + (solids ? " Sxx Rxx Syy Ryy Sxy Rxy Sxz Rxz Syz Ryz" : "")).c_str(), before.c_str(), after.c_str(), accNote.c_str(), nFresh, nHeld, heldBytes / 1073741824.0,
-             (std::string(gaveUp ? "; search for another region given up (limit / memory)" : "") + capNote + (nCached ? "; " + std::to_string(nCached) + " of the fresh buffers came from an earlier search of this process" : "")).c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count());
-    s->placementNote = buf;
-    if (verbose) fprintf(stderr, "placement: %s\nplacement: probe times, array:ms against Vx, array/class:ms against the other representatives:%s\n", buf, times.c_str());
-    return 0;
-}
-
 // Quiet runs (bfd_dev::act; bfd_kernels_v2.hip): a production call lets the runs ahead of the wave front return at entry. On when the
 // engine (a whole domain or a Z-slab of at least three sub-tiles: its boundary runs always work) accumulates its maps over the caller's own window (rmsFirstStep = 0: bench.py's timed windows, which accumulate from
 // step 1, never see it), runs the class-specialised kernels (variants 0 / 3, in-place update) and keeps solid-only values compact; BFD_SKIP_ZERO=0
@@ -2217,7 +1849,7 @@ static int check_ready(bfd_sim *s)
     }
     if (!s->placementDone) {
         s->placementDone = true;
-        const int rc = choose_placement(s);
+        const int rc = bfd_choose_placement(s);
         if (rc) return rc;
         bind_compact_views(s);        // the state buffers may have changed hands
     }
@@ -2320,7 +1952,7 @@ static int stress_part(bfd_sim *s, int part, hipStream_t st)
     BFD_HIP(hipSetDevice(s->cfg.device));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (s->timing && s->perKernel) {
-        e0 = get_event(s); e1 = get_event(s);
+        e0 = bfd_get_event(s); e1 = bfd_get_event(s);
         if (!e0 || !e1) { if (e0) s->evPool.push_back(e0); if (e1) s->evPool.push_back(e1); e0 = e1 = nullptr; }
         else hipEventRecord(e0, st);
     }
@@ -2353,7 +1985,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
     const bfd_dev &d = s->d;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (s->timing && s->perKernel) {
-        e0 = get_event(s); e1 = get_event(s);
+        e0 = bfd_get_event(s); e1 = bfd_get_event(s);
         if (!e0 || !e1) { if (e0) s->evPool.push_back(e0); if (e1) s->evPool.push_back(e1); e0 = e1 = nullptr; }
         else hipEventRecord(e0, st);
     }
@@ -2540,31 +2172,10 @@ int bfd_halo_region(bfd_sim *s, int32_t group, int32_t f, int32_t side, int32_t 
 
 int64_t bfd_placement_cache_release(void)
 {
-    std::lock_guard<std::mutex> lk(g_cacheMutex);
-    int64_t freed = 0;
-    int cur = 0;
-    const bool haveCur = hipGetDevice(&cur) == hipSuccess;
-    for (const CachedBuf &c : g_cache) { hipSetDevice(c.device); hipFree(c.p); freed += (int64_t)c.bytes; }
-    g_cache.clear();
+    const int64_t freed = bfd_placement_cache_drop_all();
     pin_release_all();          // host memory: not part of the count
-    if (haveCur) hipSetDevice(cur);
     (void)hipGetLastError();
     return freed;
-}
-
-int bfd_set_placement(bfd_sim *s, int32_t mode, int64_t searchLimitBytes)
-{
-    if (!s) BFD_FAIL(-1, "null sim");
-    if (s->placementDone) BFD_FAIL(-6, "bfd_set_placement: the arrays are placed already (call it before the first step / bfd_prepare)");
-    s->placementMode = mode != 0; s->placementLimit = searchLimitBytes;
-    return 0;
-}
-
-const char *bfd_placement_note(bfd_sim *s)
-{
-    if (!s) return "";
-    if (!s->placementDone) return "not prepared yet";
-    return s->placementNote.c_str();
 }
 
 int bfd_halo_fields(bfd_sim *s, int32_t group, uint32_t *mask)

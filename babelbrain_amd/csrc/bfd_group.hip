@@ -100,7 +100,7 @@ int group_prepare(bfd_group *g)
     if (g->prepared) return 0;
     // Slabs that share a device prepare one after the other (the placement holds transient memory, and a slab that sees its siblings' arrays on
     // the device does not search at all). One slab per device -- the real multi-GPU case -- is every device's only tenant: each slab runs the same
-    // bounded search a single-device call runs (choose_placement prices `others` per device), and the slabs prepare SIDE BY SIDE on their host
+    // bounded search a single-device call runs (bfd_choose_placement prices `others` per device), and the slabs prepare SIDE BY SIDE on their host
     // threads, so that eight searches cost the time of one (round 6; BFD_GROUP_PARALLEL_PREPARE=0 / 1 forces either order).
     bool distinct = true;
     for (int r = 0; r < g->n; r++) for (int q = 0; q < r; q++) if (g->dev[r] == g->dev[q]) distinct = false;

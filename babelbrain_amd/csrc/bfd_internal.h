@@ -146,7 +146,7 @@ struct bfd_sim {
     uint16_t *matBase;
     uint8_t *clsBase; bool classesReady;
     bool placementDone, haloHandedOut;   // bfd_prepare: the per-voxel arrays may be moved until a halo pointer has been given out
-    std::string placementNote;           // what choose_placement found and did (bfd_placement_note)
+    std::string placementNote;           // what bfd_choose_placement found and did (bfd_placement_note; bfd_placement.hip)
     std::vector<void *> searched;        // state buffers that a search found in another memory region: kept for the next engine of this process when this one is destroyed
     int placementMode; int64_t placementLimit;   // bfd_set_placement: 0 = off; bytes the search may hold at a time (-1 = default rule)
     float *tables;                  // 7*nMat
@@ -212,7 +212,19 @@ void bfd_set_error(const std::string &s);
             return -10;                                                                            \
         }                                                                                          \
     } while (0)
+#define BFD_FAIL(code, msg) do { bfd_set_error(msg); return (code); } while (0)
 
+// an event from the engine's pool or a new one; null when none can be made (bfd_api.hip)
+hipEvent_t bfd_get_event(bfd_sim *s);
+// the kernels' views of the state arrays (bfd_dev) from the allocation bases stateBase / ppBase (bfd_api.hip)
+void bfd_bind_state_views(bfd_sim *s);
+// placement of the per-voxel arrays by memory region and the cache of the buffers a search found (bfd_placement.hip): the chooser of bfd_prepare;
+// a buffer of a destroyed engine offered to the cache (true: taken, the caller must not free it); cached buffers of another size freed; all freed,
+// returns their bytes
+int bfd_choose_placement(bfd_sim *s);
+bool bfd_placement_cache_put(int device, size_t bytes, void *p);
+void bfd_placement_cache_evict_other_sizes(int device, size_t bytes);
+int64_t bfd_placement_cache_drop_all(void);
 // madvise(MADV_HUGEPAGE) on a result buffer of the caller before a large device-to-host copy (bfd_api.hip)
 void bfd_advise_result_buffer(void *p, size_t bytes);
 // bfd_get_sensors with a row pitch: the series of selected map q at out + q * rowElems (bfd_group.hip: a slab writes into its columns)

@@ -1354,7 +1354,7 @@ __global__ __launch_bounds__(NTHREADS, PML ? 4 : SOLID_VELOCITY_WAVES_PER_SIMD) 
     velocity_solid_body_g<ACC, PML, CSS, WHOLE, QUIET>(d, run, tilesX, sS, accP, pkP);
 }
 
-// placement probe (bfd_api.hip, choose_placement): two float32 arrays updated in place at the same cell offset along the
+// placement probe (bfd_placement.hip, bfd_choose_placement): two float32 arrays updated in place at the same cell offset along the
 // engine's own runs, planes below kmax only. a' = a + b, b' = b + a: the all-zero state of step 0 stays all zero.
 __global__ __launch_bounds__(NTHREADS, 8) void probe_pair(float *__restrict__ a, float *__restrict__ b, long pl, int N1, int N2, int tilesX,
                                                           int nblocks, const int4 *__restrict__ runs, int kmax)

@@ -1,7 +1,8 @@
 """Does the ±8 % process-to-process spread of velocity_fluid come from where the arrays land in memory? One process builds
 the C3 engine several times, with a throw-away allocation of varying size in between, and times the kernels each time.
-BFD_PLACEMENT_TRIALS=0 shows the raw placements (0.89 or 1.0 ms for the same kernel on the same data); the default lets
-every engine choose among 1 + 3 sets of arrays (BFD_PLACEMENT_VERBOSE=1 prints the candidates)."""
+BFD_PLACEMENT=0 shows the raw placements (0.89 or 1.0 ms for the same kernel on the same data); the default lets every engine
+place its arrays by memory region (BFD_PLACEMENT_VERBOSE=1 prints what it found). Round 2 ran it with BFD_PLACEMENT_TRIALS=0, a
+switch of the lottery of that round which no source reads any more (profiles/r2/placement_choice.txt)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

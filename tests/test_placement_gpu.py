@@ -2,6 +2,7 @@
 device: its search for a buffer in another region holds throw-away allocations, so it is switched off on a device that carries
 other allocations, bounded on a device of its own (192 GiB, at most two thirds of the free memory, 48 GiB always left; any explicit limit), and it
 gives up quietly -- bfd_prepare succeeds wherever it would with the placement off, and the results do not depend on it."""
+import re
 import subprocess
 import sys
 import threading
@@ -155,6 +156,51 @@ def test_placement_buffers_kept_between_engines_and_released(monkeypatch):
     freed = _engine.placement_cache_release()
     assert 0 <= freed <= 1 << 30
     assert _engine.placement_cache_release() == 0
+
+
+def test_note_regions_and_hand_over_for_every_buffer_count(monkeypatch):
+    """The stream order, the assignment and the hand-over of the buffers at commit and at destroy, for the three sets of buffers the placement
+    handles: 15 (variant 0), 15 with the ten solid arrays in the list (variant 2), 20 (variant 4 on a whole domain: the second copies). The note
+    names the arrays and gives their regions before and after, one character per array; a short forced search on a small grid.
+    60 steps, as in the test above: one period of the source at this grid. The harness gives a run shorter than that an empty source table
+    (pulse_sources cuts the table to whole periods), so after 20 or 40 steps every map is exactly zero -- in the CPU oracle too (RMS maximum
+    0.0 at both counts) -- and the comparison of the maps would hold whatever the placement did."""
+    monkeypatch.setenv('BFD_PLACEMENT_MIN_VOXELS', '0')
+    monkeypatch.setenv('BFD_PLACEMENT_SEARCH_MB', '64')
+    monkeypatch.setenv('BABELFDTD_PLACEMENT_CACHE_GIB', '1')
+    _engine.placement_cache_release()
+    a, k, info = H.make_problem('C2', N=(96, 80, 72), steps=60, stable_dt_fn=_hip_dt, full_sensors=False)
+    for variant in (0, 2, 4):
+        ref = _engine_for(a, k, info, kernelVariant=variant)
+        ref.set_placement(0)
+        ref.run(60)
+        want = ref.get_map(_engine.KIND_RMS, 'Pressure')
+        assert ref.placement_note() == 'off'
+        ref.close()
+        eng = _engine_for(a, k, info, kernelVariant=variant)
+        eng.prepare()
+        note = eng.placement_note()
+        print('variant', variant, ':', note)
+        m = re.search(r'regions of (.*?) (\S+) -> (\S+) \(m / n = ', note)
+        assert m, note
+        names, before, after = m.groups()
+        copies, solids = 'their second copies' in names, 'Sxx' in names
+        assert len(before) == len(after) == 5 + 5 * copies + 10 * solids
+        if variant == 4:
+            assert copies
+        if variant == 2:
+            assert solids
+        assert before.isdigit()
+        fresh = int(re.search(r' (\d+) fresh,', note).group(1))
+        assert after.count('m') + after.count('n') <= fresh
+        with pytest.raises(_engine.EngineError):
+            eng.set_placement(0)                        # too late: the arrays are placed
+        eng.run(60)
+        got = eng.get_map(_engine.KIND_RMS, 'Pressure')
+        eng.close()
+        assert np.array_equal(got, want) and want.max() > 0
+        assert 0 <= _engine.placement_cache_release() <= 1 << 30
+        assert _engine.placement_cache_release() == 0
 
 
 def test_drop_in_call_leaves_no_idle_buffers_by_default(monkeypatch):
