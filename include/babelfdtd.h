@@ -430,6 +430,25 @@ int bfd_bhte_run_protocol16(int32_t device, int32_t N1, int32_t N2, int32_t N3, 
                             float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
                             int32_t nCaptures, const int32_t *captureStep, float *Tmax, float *doseAtCapture);
 
+/* ---- 3-D median filter: replaces scipy.ndimage.median_filter / GPUFunctions.GPUMedianFilter.MedianFilter around the solver calls ----
+ * (ThermalModeling/CalculateTemperatureEffects.py:908-918: float32 pressure amplitude, size 3; BabelBrain/BabelDatasetPreps.py:870-876,
+ * 1050-1053, 1069-1072: uint8 masks, sizes 7 and 3, through the callback CalculateMaskProcess.py:42-70 installs).
+ *   out[i][j][k] = the element of rank n/2 (0-based, ascending) of the s1 x s2 x s3 window centred on (i,j,k), n = s1 s2 s3
+ * in and out: HOST pointers to [N1][N2][N3] volumes in numpy C order (k fastest), dtype 0 = uint8, 1 = float32; in is never written and out
+ * may not overlap it. Each s is 1, 3, 5 or 7 (the reference's limit is 7 per axis). mode 0 = scipy's 'reflect' (the default there; the
+ * reference kernel's -1-ix / 2 dim-1-ix), 1 = 'constant' with cval (for uint8 an integer in 0..255; for float32 rounded to float32).
+ * Every dimension must be at least s/2 on its axis (one reflection suffices), and the volume must have fewer than 2^31 voxels: otherwise -1,
+ * nothing is truncated. The output is one of the window's input values with its bits unchanged: nothing is flushed or rounded, float32
+ * denormals included; where a window holds both -0.0 and +0.0 either may come out. Behaviour on NaN is undefined.
+ * regionMask (may be NULL): uint8 [N1][N2][N3]; out = regionMask != 0 ? median : in, bit for bit (4 x 4 x 64 tiles without a masked voxel
+ * are copied). kernelMs (may be NULL): device time of the kernel alone, HIP events. Device memory during the call: two volumes and the mask.
+ * Returns 0; -1 bad argument (reported before a device is looked for), -3 no such device, -10 device error; text in bfd_last_error.
+ * There is no CPU fallback. */
+int bfd_median_filter3d(int device, int dtype /*0 u8, 1 f32*/, const void *in, void *out,
+                        const uint8_t *regionMask /*may be NULL*/,
+                        int64_t N1, int64_t N2, int64_t N3, int s1, int s2, int s3,
+                        int mode /*0 reflect, 1 constant*/, double cval, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
