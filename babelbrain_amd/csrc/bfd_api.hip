@@ -1,11 +1,8 @@
-// C ABI of libbabelfdtd_hip.so (include/babelfdtd.h): host logic, coefficient preparation,
-// layout conversion, sources, sensors, accumulation. gfx950 only.
+// C ABI of libbabelfdtd_hip.so (include/babelfdtd.h): host logic, coefficient preparation, layout conversion,
+// sources, tile lists, time stepping. gfx950 only. Sensors, maps and the result getters: bfd_outputs.hip.
 //
 // Mirrors what BabelIntegrationBASE.py:2338-2365 hands to the reference's solver
 // (package BabelViscoFDTD==1.2.4, absent from /root/reference).
-#include <functional>
-#include <cstring>
-#include <sys/mman.h>
 #include "bfd_internal.h"
 
 #include <math.h>
@@ -14,42 +11,10 @@
 
 #include <algorithm>
 #include <array>
-#include <chrono>
-#include <mutex>
 #include <thread>
 #include <hipcub/hipcub.hpp>
 
 static thread_local std::string g_err;
-// pinned 16 MB pieces of copy_out_large, kept from one readback of a call to the next (allocating and releasing eight of them costs 22 ms, as much as
-// moving a 512^3 map); given back to the system with the placement cache (bfd_placement_cache_release: the drop-in call does that at its end)
-static std::mutex g_pinMutex;
-static std::vector<char *> g_pinFree;
-static const size_t kPinPiece = (size_t)16 << 20;
-static char *pin_take(size_t bytes)
-{
-    if (bytes == kPinPiece) {
-        std::lock_guard<std::mutex> lk(g_pinMutex);
-        if (!g_pinFree.empty()) { char *p = g_pinFree.back(); g_pinFree.pop_back(); return p; }
-    }
-    char *p = nullptr;
-    if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return p;
-}
-static void pin_give(char *p, size_t bytes)
-{
-    if (!p) return;
-    if (bytes == kPinPiece) {
-        std::lock_guard<std::mutex> lk(g_pinMutex);
-        if (g_pinFree.size() < 32) { g_pinFree.push_back(p); return; }
-    }
-    hipHostFree(p);
-}
-static void pin_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_pinMutex);
-    for (char *p : g_pinFree) hipHostFree(p);
-    g_pinFree.clear();
-}
 void bfd_set_error(const std::string &s) { g_err = s; }
 
 // ------------------------------------------------------------------------------------------------
@@ -182,16 +147,6 @@ __global__ void or_reflector(const uint32_t *__restrict__ in, long s1, long s2, 
         mat[v] = m;
     }
 }
-// x-fastest device layout -> strided caller layout (through a dense device staging buffer)
-__global__ void scatter_from_xfast(const float *__restrict__ in, float *__restrict__ out, long s1, long s2, long s3,
-                                   int N1, int N2, int nk)
-{
-    const long n = (long)N1 * N2 * nk;
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x) {
-        const int i = (int)(v % N1), j = (int)((v / N1) % N2), k = (int)(v / ((long)N1 * N2));
-        out[i * s1 + j * s2 + k * s3] = in[v];
-    }
-}
 __global__ void transpose_pulse(const double *__restrict__ in, float *__restrict__ out, int nSrc, int L)
 {   // in [nSrc][L] f64 -> out [L][nSrc] f32
     const long n = (long)nSrc * L;
@@ -199,243 +154,6 @@ __global__ void transpose_pulse(const double *__restrict__ in, float *__restrict
         const int s = (int)(v % nSrc);
         const long t = v / nSrc;
         out[v] = (float)in[(long)s * L + t];
-    }
-}
-
-// does cell c (local linear index) hold only the Szz/Rzz copy of its normal stresses? (every fluid cell: bfd_dev::cls)
-__device__ __forceinline__ bool normal_collapsed(const bfd_dev &d, long c)
-{
-    return (d.cls[c] & BFD_CLS_FLUID) != 0;
-}
-
-// a value that exists only at solid cells: from the compact arrays when the solid state is compact (0 where the cell is not listed:
-// a reflector, or a fluid cell asked for a shear stress), else from the full-volume array. KNOWN: the caller has the cell's list entry
-// already (e, -1 = not listed) -- the sensor kernels take it from a per-sensor table, accumulate_maps from the row table and a ballot --
-// otherwise css_index walks the class bytes of the row
-template <bool KNOWN>
-__device__ __forceinline__ float solid_value(const bfd_dev &d, const float *full, const float *comp, long c, long e)
-{
-    if (!d.cssRow) return full[c];
-    if (!KNOWN) e = css_index(d, c);
-    return e >= 0 ? comp[e] : 0.0f;
-}
-template <bool KNOWN>
-__device__ __forceinline__ float map_value_t(const bfd_dev &d, int sel, long c, long e)
-{
-    switch (sel) {
-    case BFD_MAP_VX: return d.Vx[c];
-    case BFD_MAP_VY: return d.Vy[c];
-    case BFD_MAP_VZ: return d.Vz[c];
-    case BFD_MAP_SIGMAXX: return normal_collapsed(d, c) ? d.Szz[c] : solid_value<KNOWN>(d, d.Sxx, d.cSxx, c, e);     // a fluid cell keeps one copy of its normal stresses
-    case BFD_MAP_SIGMAYY: return normal_collapsed(d, c) ? d.Szz[c] : solid_value<KNOWN>(d, d.Syy, d.cSyy, c, e);
-    case BFD_MAP_SIGMAZZ: return d.Szz[c];
-    case BFD_MAP_SIGMAXY: return solid_value<KNOWN>(d, d.Sxy, d.cSxy, c, e);
-    case BFD_MAP_SIGMAXZ: return solid_value<KNOWN>(d, d.Sxz, d.cSxz, c, e);
-    case BFD_MAP_SIGMAYZ: return solid_value<KNOWN>(d, d.Syz, d.cSyz, c, e);
-    case BFD_MAP_PRESSURE: {
-        const float zz = d.Szz[c];
-        if (normal_collapsed(d, c)) return -((zz + zz) + zz) * (1.0f / 3.0f);
-        float xx, yy;
-        if (d.cssRow) { if (!KNOWN) e = css_index(d, c); xx = e >= 0 ? d.cSxx[e] : 0.0f; yy = e >= 0 ? d.cSyy[e] : 0.0f; }
-        else { xx = d.Sxx[c]; yy = d.Syy[c]; }
-        const float s = (xx + yy) + zz;
-        return -s * (1.0f / 3.0f);
-    }
-    default: return 0.0f;
-    }
-}
-__device__ __forceinline__ float map_value(const bfd_dev &d, int sel, long c) { return map_value_t<false>(d, sel, c, -1); }
-// value of map `sel` as the outputs define it (ALLV = |V|) with the cell's list entry known
-__device__ __forceinline__ float output_value(const bfd_dev &d, int sel, long c, long e)
-{
-    if (sel == BFD_MAP_ALLV) { const float x = d.Vx[c], y = d.Vy[c], z = d.Vz[c]; return sqrtf((x * x + y * y) + z * z); }
-    return map_value_t<true>(d, sel, c, e);
-}
-__device__ __forceinline__ bool map_needs_entry(int sel)
-{
-    return sel == BFD_MAP_SIGMAXX || sel == BFD_MAP_SIGMAYY || sel == BFD_MAP_SIGMAXY || sel == BFD_MAP_SIGMAXZ || sel == BFD_MAP_SIGMAYZ || sel == BFD_MAP_PRESSURE;
-}
-// list entries of the sensor voxels (compact solid state), resolved once per list: a capture is a plain gather again
-__global__ void sensor_entries(bfd_dev d, const uint32_t *__restrict__ lin, long nSens, int *__restrict__ out)
-{
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nSens; s += (long)gridDim.x * blockDim.x)
-        out[s] = (int)css_index(d, (long)lin[s]);
-}
-// fluid cells keep only Szz/Rzz of their identical normal stresses: restore the other copies
-__global__ void expand_normal(bfd_dev d, long n)
-{
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x) {
-        if (!normal_collapsed(d, v)) continue;
-        const float s = d.Szz[v], r = d.Rzz[v];
-        d.Sxx[v] = s; d.Syy[v] = s; d.Rxx[v] = r; d.Ryy[v] = r;
-    }
-}
-// output assembly (bfd_get_field, compact solid state): out = src at the cells that keep one copy of their normal stresses
-__global__ void copy_at_fluid_cells(bfd_dev d, const float *__restrict__ src, float *__restrict__ out, long n)
-{
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x)
-        if (normal_collapsed(d, v)) out[v] = src[v];
-}
-__device__ __forceinline__ float map_sq(const bfd_dev &d, int sel, long c)
-{
-    if (sel == BFD_MAP_ALLV) {
-        const float x = d.Vx[c], y = d.Vy[c], z = d.Vz[c];
-        return (x * x + y * y) + z * z;
-    }
-    const float v = map_value(d, sel, c);
-    return v * v;
-}
-
-struct SelList { int n; int sel[BFD_MAP_COUNT]; int skip[BFD_MAP_COUNT]; };
-
-// RMS / peak accumulation outside the absorbing layer (generic path, any map selection). A wave = 64 consecutive x cells of one row: with a
-// compact solid state the cell's list entry is the row-table base of this x tile + the listed lanes below (one ballot), once for all selections
-__global__ __launch_bounds__(256) void accumulate_maps(bfd_dev d, SelList L, float *__restrict__ acc, float *__restrict__ pk, long nloc)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const int j = blockIdx.y * 4 + threadIdx.y;
-    const int kl = blockIdx.z;
-    const int k = d.k0 + kl;
-    const bool inDomain = i < d.N1 && j < d.N2;
-    const long c = (long)kl * d.plane + (long)j * d.N1 + i;
-    long e = -1;
-    if (d.cssRow) {
-        bool need = false;
-        for (int q = 0; q < L.n; q++) need = need || (!L.skip[q] && map_needs_entry(L.sel[q]));
-        if (need) {                                                      // block-uniform
-            const bool listed = inDomain && css_listed(d.cls[c]);
-            const unsigned rank = css_rank(listed);
-            const unsigned rb = j < d.N2 ? d.cssRow[((long)(kl + 2) * d.N2 + j) * d.cssStride + blockIdx.x] : BFD_CSS_NONE;
-            if (listed && rb != BFD_CSS_NONE) e = (long)rb + rank;
-        }
-    }
-    if (i < d.ND || i >= d.N1 - d.ND || j < d.ND || j >= d.N2 - d.ND || k < d.ND || k >= d.N3 - d.ND) return;
-    for (int q = 0; q < L.n; q++) {
-        if (L.skip[q]) continue;    // accumulated inside the velocity kernel
-        const float v = output_value(d, L.sel[q], c, e);
-        if (acc) acc[q * nloc + c] = acc[q * nloc + c] + (L.sel[q] == BFD_MAP_ALLV ? map_sq(d, BFD_MAP_ALLV, c) : v * v);
-        if (pk) {
-            const float a = fabsf(v);
-            if (a > pk[q * nloc + c]) pk[q * nloc + c] = a;
-        }
-    }
-}
-__global__ void finalize_rms(const float *__restrict__ acc, float *__restrict__ out, long n, float cnt)
-{
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x)
-        out[v] = sqrtf(acc[v] / cnt);
-}
-__global__ void last_map(bfd_dev d, int sel, float *__restrict__ out, long n)
-{
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x)
-        out[v] = (sel == BFD_MAP_ALLV) ? sqrtf(map_sq(d, BFD_MAP_ALLV, v)) : map_value(d, sel, v);
-}
-
-// Sensor sets that are a dense box of voxels (what the caller's CreateSensorMap makes: everything inside the absorbing layer past the source plane,
-// BASE:2279-2290) need no index list: sensor s of the box is voxel (i0 + s % bx, j0 + (s / bx) % by, k0 + s / (bx by)) -- the order of the ascending
-// x-fastest linear index the list is in. lin == null selects that form (4 of the 13 bytes a captured sample moved were the index).
-struct SensorBox { unsigned bx, bxy, i0, j0, k0; };
-__device__ __forceinline__ long sensor_cell(const bfd_dev &d, const uint32_t *__restrict__ lin, const SensorBox &B, long s)
-{
-    if (lin) return (long)lin[s];
-    const unsigned u = (unsigned)s, kk = u / B.bxy, r = u - kk * B.bxy, jj = r / B.bx, ii = r - jj * B.bx;
-    return (long)(B.k0 + kk) * d.plane + (long)(B.j0 + jj) * d.N1 + (B.i0 + ii);
-}
-// bounding box of a sensor list (min / max of i, j, k): six atomics per workgroup
-__global__ __launch_bounds__(256) void sensor_bounds(bfd_dev d, const uint32_t *__restrict__ lin, long n, unsigned *__restrict__ mm)
-{
-    unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (long)gridDim.x * blockDim.x) {
-        const unsigned c = lin[s], kl = c / (unsigned)d.plane, r = c - kl * (unsigned)d.plane, j = r / (unsigned)d.N1, i = r - j * (unsigned)d.N1;
-        lo[0] = min(lo[0], i); hi[0] = max(hi[0], i); lo[1] = min(lo[1], j); hi[1] = max(hi[1], j); lo[2] = min(lo[2], kl); hi[2] = max(hi[2], kl);
-    }
-    for (int a = 0; a < 3; a++) {
-        for (int o = 32; o > 0; o >>= 1) { lo[a] = min(lo[a], (unsigned)__shfl_down((int)lo[a], o)); hi[a] = max(hi[a], (unsigned)__shfl_down((int)hi[a], o)); }
-        if ((threadIdx.x & 63) == 0) { atomicMin(mm + a, lo[a]); atomicMax(mm + 3 + a, hi[a]); }
-    }
-}
-// sensors: out[q][col][s]; ent = the sensors' list entries (compact solid state) or null
-__global__ void record_sensors(bfd_dev d, SelList L, const uint32_t *__restrict__ lin, SensorBox B, const int *__restrict__ ent, long nSens,
-                               float *__restrict__ out, int col, int nTs)
-{
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nSens; s += (long)gridDim.x * blockDim.x) {
-        const long c = sensor_cell(d, lin, B, s);
-        const long e = (ent && !normal_collapsed(d, c)) ? (long)ent[s] : -1;
-        for (int q = 0; q < L.n; q++)
-            out[((long)q * nTs + col) * nSens + s] = output_value(d, L.sel[q], c, e);
-    }
-}
-// sensorMode 1: the sample of this step goes straight into the running single-bin DFT sums and peaks of its sensor
-// (same arithmetic, sample by sample, as dft_series applies to a stored series)
-__global__ void accumulate_sensor_dft(bfd_dev d, SelList L, const uint32_t *__restrict__ lin, SensorBox B, const int *__restrict__ ent, long nSens,
-                                      double *__restrict__ acc, float *__restrict__ pk, int col, int nTs, int bin)
-{
-    const int r = (int)(((long)bin * col) % nTs);                 // exact phase index
-    double sn, cs;
-    sincospi(2.0 * (double)r / (double)nTs, &sn, &cs);
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nSens; s += (long)gridDim.x * blockDim.x) {
-        const long c = sensor_cell(d, lin, B, s);
-        const long e = (ent && !normal_collapsed(d, c)) ? (long)ent[s] : -1;
-        for (int q = 0; q < L.n; q++) {
-            const float x = output_value(d, L.sel[q], c, e);
-            double *a = acc + 2 * ((long)q * nSens + s);
-            a[0] += (double)x * cs; a[1] -= (double)x * sn;
-            float *p = pk + (long)q * nSens + s;
-            *p = fmaxf(*p, x);
-        }
-    }
-}
-__global__ void fill_float(float *__restrict__ p, long n, float v)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
-}
-__global__ void finalize_sensor_dft(const double *__restrict__ acc, float *__restrict__ out, long n2, double sc)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) out[i] = (float)(acc[i] * sc);
-}
-
-// [q][nTs][nSens] -> [q][nSens][nTs]
-__global__ void transpose_sensors(const float *__restrict__ in, float *__restrict__ out, long nSens, int nTs, int nq)
-{
-    const long n = nSens * nTs * nq;
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (long)gridDim.x * blockDim.x) {
-        const int t = (int)(v % nTs);
-        const long s = (v / nTs) % nSens;
-        const long q = v / ((long)nTs * nSens);
-        out[v] = in[(q * nTs + t) * nSens + s];
-    }
-}
-
-// the same for elements [v0, v0 + cnt) of the transposed block only (out = a piece buffer): the sensor series leave the device piece by piece
-__global__ void transpose_sensors_range(const float *__restrict__ in, float *__restrict__ out, long nSens, int nTs, long v0, long cnt)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (long)gridDim.x * blockDim.x) {
-        const long v = v0 + i;
-        const int t = (int)(v % nTs);
-        const long s = (v / nTs) % nSens;
-        const long q = v / ((long)nTs * nSens);
-        out[i] = in[(q * nTs + t) * nSens + s];
-    }
-}
-
-// single-bin DFT + peak of sensor series. x(s,n) = in[s*sS + n*sN]; out[s] = (2/nTs) sum_n x exp(-2 pi i bin n/nTs)
-__global__ void dft_series(const float *__restrict__ in, long sS, long sN, long nSens, int nTs, int bin,
-                           float *__restrict__ outReIm, float *__restrict__ outPeak)
-{
-    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nSens; s += (long)gridDim.x * blockDim.x) {
-        double re = 0.0, im = 0.0;
-        float pk = -INFINITY;
-        for (int n = 0; n < nTs; n++) {
-            const float x = in[s * sS + n * sN];
-            const int r = (int)(((long)bin * n) % nTs);                 // exact phase index
-            double sn, cs;
-            sincospi(2.0 * (double)r / (double)nTs, &sn, &cs);
-            re += (double)x * cs; im -= (double)x * sn;
-            pk = fmaxf(pk, x);
-        }
-        const double sc = 2.0 / (double)nTs;
-        outReIm[2 * s] = (float)(re * sc); outReIm[2 * s + 1] = (float)(im * sc);
-        if (outPeak) outPeak[s] = pk;
     }
 }
 
@@ -530,7 +248,6 @@ __global__ void inject_sources_sep_at(bfd_dev d, int typeSource, const uint32_t 
 __global__ void set_step(int *stepDev, int v) { *stepDev = v; }
 __global__ void advance_step(int *stepDev) { *stepDev = *stepDev + 1; }
 
-inline int grid_for(long n, int block = 256) { return (int)std::min<long>((n + block - 1) / block, 256L * 32); }
 
 // separable injection with K terms: at host step `step`, or (stepDev != null, graph replay) at the device's step counter
 template <int K>
@@ -565,52 +282,6 @@ static void drop_step_graph(bfd_sim *s)
     s->stepDevValid = false;
 }
 
-// hipMalloc that gives idle buffers of the placement cache (bfd_placement.hip) back to the device before it reports that memory ran out
-static hipError_t malloc_or_release_cache(void **q, size_t bytes)
-{
-    hipError_t e = hipMalloc(q, bytes);
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-        (void)hipGetLastError();
-        if (bfd_placement_cache_release() > 0) e = hipMalloc(q, bytes);
-    }
-    return e;
-}
-
-template <typename T>
-int dev_alloc(bfd_sim *s, T **p, size_t count, bool zero = true)
-{
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    BFD_HIP(malloc_or_release_cache(&q, bytes));
-    if (zero) BFD_HIP(hipMemsetAsync(q, 0, bytes, s->stream));
-    s->allocs.push_back(q);
-    s->devBytes += (int64_t)bytes;
-    *p = (T *)q;
-    return 0;
-}
-
-// frees an array obtained from dev_alloc before the sim is destroyed (inputs that are set again)
-template <typename T>
-void dev_release(bfd_sim *s, T **p)
-{
-    if (!*p) return;
-    auto it = std::find(s->allocs.begin(), s->allocs.end(), (void *)*p);
-    if (it != s->allocs.end()) { hipFree(*it); s->allocs.erase(it); }
-    *p = nullptr;
-}
-
-inline size_t span_elems(int N1, int N2, int nk, int64_t s1, int64_t s2, int64_t s3)
-{
-    return (size_t)((N1 - 1) * s1 + (N2 - 1) * s2 + (nk - 1) * s3 + 1);
-}
-
-int sel_list(uint32_t mask, int *sel)
-{
-    int n = 0;
-    for (int b = 0; b < BFD_MAP_COUNT; b++) if (mask & (1u << b)) sel[n++] = b;
-    return n;
-}
-
 // number of non-zero edge coefficients A (active shear updates) in the sparse shear list
 __global__ void count_active_edges(const float *__restrict__ coef, const unsigned *__restrict__ codes, long n, unsigned long long *__restrict__ out)
 {
@@ -623,7 +294,6 @@ __global__ void count_active_edges(const float *__restrict__ coef, const unsigne
     if (c) atomicAdd(out, (unsigned long long)c);
     if (x) atomicAdd(out + 1, (unsigned long long)x);
 }
-
 
 // ---- streamed source table -------------------------------------------------------------------------------------------
 // tile t = steps [t*TS, min((t+1)*TS, L)) of the caller's [nSources][L] float64 table -> pinned [steps][nSources] float32
@@ -723,7 +393,52 @@ void pulse_row_read(bfd_sim *s, int step, hipStream_t st)
 
 }  // namespace
 
-static int dft_bin(int n, double d, double freq);
+int sel_list(uint32_t mask, int *sel)
+{
+    int n = 0;
+    for (int b = 0; b < BFD_MAP_COUNT; b++) if (mask & (1u << b)) sel[n++] = b;
+    return n;
+}
+
+void bfd_launch_gather_flags(const bfd_sim *s, const uint32_t *in, long s1, long s2, long s3, uint8_t *flags)
+{
+    const bfd_dev &d = s->d;
+    hipLaunchKernelGGL((gather_to_xfast<1, uint8_t>), dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream,
+                       in, s1, s2, s3, flags, d.N1, d.N2, d.nk, 0, 0, d.nk - 1, 0u, (int *)nullptr);
+}
+
+hipError_t select_flagged(uint8_t *flags, uint32_t *sel, int *dcount, int n, hipStream_t st, DevTemp<char> &work)
+{
+    size_t wbytes = 0;
+    hipcub::CountingInputIterator<uint32_t> ids(0);
+    hipError_t e = hipcub::DeviceSelect::Flagged(nullptr, wbytes, ids, flags, sel, dcount, n, st);
+    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
+    if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged((void *)work.p, wbytes, ids, flags, sel, dcount, n, st);
+    return e;
+}
+
+// inputs changed: the run lists, the activity map and a recorded step graph are out of date, and (classes: materials, map, reflector) the cell classes
+static void invalidate_lists(bfd_sim *s, bool classes = true) { s->tilesReady = false; if (classes) s->classesReady = false; s->actReady = false; drop_step_graph(s); }
+
+static int pressure_slot(const bfd_sim *s)
+{
+    int qP = -1;
+    for (int q = 0; q < s->nSelR; q++) if (s->selR[q] == BFD_MAP_PRESSURE) qP = q;
+    return qP;
+}
+// paired accumulation (see "paired accumulation" below): the slot of the Pressure map, and the flush of the outstanding step.
+// st: the stream the following launches go to (default: the engine's); bfd_outputs.hip calls it too
+int flush_pending(bfd_sim *s, hipStream_t st)
+{
+    if (!s->pendingAcc) return 0;        // also between the half-steps of the second step of a pair: its stress half-step has added both (pairDone)
+    s->pendingAcc = false;
+    const int qP = pressure_slot(s);
+    if (qP < 0 || !s->tilesReady) return 0;
+    BFD_HIP(hipSetDevice(s->cfg.device));
+    bfd_launch_flush_paired(s->d, st, s->acc ? s->acc + (size_t)qP * s->nloc : nullptr, s->pk ? s->pk + (size_t)qP * s->nloc : nullptr, &s->tiles);
+    BFD_HIP(hipGetLastError());
+    return 0;
+}
 
 hipEvent_t bfd_get_event(bfd_sim *s)
 {
@@ -942,9 +657,6 @@ int bfd_use_private_stream(bfd_sim *s)
     return 0;
 }
 
-static int flush_pending(bfd_sim *s, hipStream_t st);
-static int flush_pending(bfd_sim *s) { return flush_pending(s, s->stream); }
-
 int bfd_set_materials(bfd_sim *s, const double *matlist, const double *qcorr)
 {
     if (!s || !matlist) BFD_FAIL(-1, "bfd_set_materials: null argument");
@@ -980,7 +692,7 @@ int bfd_set_materials(bfd_sim *s, const double *matlist, const double *qcorr)
     d.axI = bx; d.bxI = bx + d.N1; d.axH = bx + 2 * d.N1; d.bxH = bx + 3 * d.N1;
     d.ayI = by; d.byI = by + d.N2; d.ayH = by + 2 * d.N2; d.byH = by + 3 * d.N2;
     d.azI = bz; d.bzI = bz + d.N3; d.azH = bz + 2 * d.N3; d.bzH = bz + 3 * d.N3;
-    s->haveMaterials = true; s->tilesReady = false; s->classesReady = false; s->actReady = false; drop_step_graph(s);
+    s->haveMaterials = true; invalidate_lists(s);
     return 0;
 }
 
@@ -997,25 +709,23 @@ int bfd_set_material_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2
     const int nkSpan = d.nk + ghostLow + ghostHigh;
     if (s1 < 0 || s2 < 0 || s3 < 0) BFD_FAIL(-2, "negative strides are not supported");
     const size_t span = span_elems(d.N1, d.N2, nkSpan, s1, s2, s3);
-    uint32_t *tmp = nullptr;
-    BFD_HIP(hipMalloc((void **)&tmp, span * sizeof(uint32_t)));
+    DevTemp<uint32_t> tmp; DevTemp<int> flag; int hflag = 0;
+    BFD_HIP(tmp.alloc(span));
     hipError_t e = hipMemcpyAsync(tmp, base, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream);
-    int *flag = nullptr; int hflag = 0;
-    if (e == hipSuccess) e = hipMalloc((void **)&flag, sizeof(int));
+    if (e == hipSuccess) e = flag.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s->stream);
     if (e == hipSuccess) {
         // destination covers local planes -2..nk+1; source plane index = local k + ghostLow, clamped to the span
         hipLaunchKernelGGL((gather_to_xfast<0, uint16_t>), dim3(grid_for((long)s->nalloc)), dim3(256), 0, s->stream,
-                           tmp, (long)s1, (long)s2, (long)s3, s->matBase, d.N1, d.N2, d.nk + 4, ghostLow - 2, 0, nkSpan - 1,
-                           (uint32_t)s->cfg.nMat, flag);
+                           tmp.p, (long)s1, (long)s2, (long)s3, s->matBase, d.N1, d.N2, d.nk + 4, ghostLow - 2, 0, nkSpan - 1,
+                           (uint32_t)s->cfg.nMat, flag.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(tmp); if (flag) hipFree(flag);
     if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_set_material_map: ") + hipGetErrorString(e));
     if (hflag) BFD_FAIL(-5, "bfd_set_material_map: MaterialMap holds an id >= number of MaterialList rows");
-    s->haveMap = true; s->tilesReady = false; s->classesReady = false; s->actReady = false; drop_step_graph(s);
+    s->haveMap = true; invalidate_lists(s);
     return 0;
 }
 
@@ -1026,17 +736,16 @@ int bfd_set_reflector(bfd_sim *s, const uint32_t *mask, int64_t s1, int64_t s2, 
     BFD_HIP(hipSetDevice(s->cfg.device));
     { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
-    uint32_t *tmp = nullptr;
+    DevTemp<uint32_t> tmp;
     if (mask) {
         const size_t span = span_elems(d.N1, d.N2, d.nk, s1, s2, s3);
-        BFD_HIP(hipMalloc((void **)&tmp, span * sizeof(uint32_t)));
+        BFD_HIP(tmp.alloc(span));
         BFD_HIP(hipMemcpyAsync(tmp, mask, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     }
-    hipLaunchKernelGGL(or_reflector, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, tmp, (long)s1, (long)s2, (long)s3,
+    hipLaunchKernelGGL(or_reflector, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, tmp.p, (long)s1, (long)s2, (long)s3,
                        s->matBase + 2 * (size_t)d.plane, d.N1, d.N2, d.nk, mask ? 0 : 1);
     BFD_HIP(hipStreamSynchronize(s->stream));
-    if (tmp) hipFree(tmp);
-    s->tilesReady = false; s->classesReady = false; s->actReady = false; drop_step_graph(s);      // reflector cells end the UNI class of their tiles
+    invalidate_lists(s);      // reflector cells end the UNI class of their tiles
     return 0;
 }
 
@@ -1057,7 +766,7 @@ static int set_source_voxels(bfd_sim *s, const char *who, int64_t nVox, const ui
     dev_release(s, &s->srcWeights); dev_release(s, &s->srcSignals); s->srcK = 0;
     for (int a = 0; a < 3; a++) dev_release(s, &s->srcW[a]);
     s->nSrcVox = nVox; s->nSources = nSources; s->lengthSource = lengthSource;
-    s->srcLowEnd = 0; s->srcHighBeg = nVox; s->tilesReady = false; s->actReady = false; drop_step_graph(s);
+    s->srcLowEnd = 0; s->srcHighBeg = nVox; invalidate_lists(s, false);
     if (nVox == 0) return 0;
     // keep the source voxels sorted by voxel index: the boundary/interior split of a half-step injects
     // the sources of the first and last z-chunk separately (build_tile_lists)
@@ -1122,12 +831,11 @@ int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const 
         return 0;
     }
     if ((rc = dev_alloc(s, &s->pulseT, np, false))) return rc;
-    double *tmp = nullptr;
-    BFD_HIP(hipMalloc((void **)&tmp, std::max<size_t>(np, 1) * sizeof(double)));
+    DevTemp<double> tmp;
+    BFD_HIP(tmp.alloc(std::max<size_t>(np, 1)));
     BFD_HIP(hipMemcpyAsync(tmp, pulse, np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(transpose_pulse, dim3(grid_for((long)np)), dim3(256), 0, s->stream, tmp, s->pulseT, nSources, lengthSource);
+    hipLaunchKernelGGL(transpose_pulse, dim3(grid_for((long)np)), dim3(256), 0, s->stream, tmp.p, s->pulseT, nSources, lengthSource);
     BFD_HIP(hipStreamSynchronize(s->stream));
-    hipFree(tmp);
     return 0;
 }
 
@@ -1160,81 +868,6 @@ int bfd_set_sources_separable(bfd_sim *s, int64_t nVox, const uint32_t *localInd
         return rc ? rc : -10;
     }
     s->srcK = K;
-    return 0;
-}
-
-int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3, int64_t *nSensors)
-{
-    if (!s || !map) BFD_FAIL(-1, "bfd_set_sensor_map: null argument");
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    { const int rc = flush_pending(s); if (rc) return rc; }
-    const bfd_dev &d = s->d;
-    const size_t span = span_elems(d.N1, d.N2, d.nk, s1, s2, s3);
-    uint32_t *tmp = nullptr; uint8_t *flags = nullptr; uint32_t *sel = nullptr; int *dcount = nullptr; void *work = nullptr;
-    hipError_t e = hipMalloc((void **)&tmp, span * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&flags, s->nloc);
-    if (e == hipSuccess) e = hipMalloc((void **)&sel, s->nloc * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&dcount, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, map, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream);
-    int count = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((gather_to_xfast<1, uint8_t>), dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream,
-                           tmp, (long)s1, (long)s2, (long)s3, flags, d.N1, d.N2, d.nk, 0, 0, d.nk - 1, 0u, (int *)nullptr);
-        size_t wbytes = 0;
-        hipcub::CountingInputIterator<uint32_t> ids(0);
-        e = hipcub::DeviceSelect::Flagged(nullptr, wbytes, ids, flags, sel, dcount, (int)s->nloc, s->stream);
-        if (e == hipSuccess) e = hipMalloc(&work, std::max<size_t>(wbytes, 1));
-        if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged(work, wbytes, ids, flags, sel, dcount, (int)s->nloc, s->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    }
-    int rc = 0;
-    if (e == hipSuccess) {
-        s->nSensors = count;
-        dev_release(s, &s->sensLin); dev_release(s, &s->sensOut); dev_release(s, &s->dftAcc); dev_release(s, &s->dftPk);
-        dev_release(s, &s->sensEnt); s->sensEntValid = false;
-        rc = dev_alloc(s, &s->sensLin, (size_t)count, false);
-        if (!rc && count) e = hipMemcpyAsync(s->sensLin, sel, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream);
-        if (!rc && s->nSelS && s->nTs > 0) {
-            if (s->cfg.sensorMode == 0) rc = dev_alloc(s, &s->sensOut, (size_t)s->nSelS * s->nTs * (size_t)count);
-            else {
-                rc = dev_alloc(s, &s->dftAcc, 2 * (size_t)s->nSelS * (size_t)count);
-                if (!rc) rc = dev_alloc(s, &s->dftPk, (size_t)s->nSelS * (size_t)std::max(count, 1), false);
-                if (!rc && count > 0) hipLaunchKernelGGL(fill_float, dim3(grid_for((long)s->nSelS * count)), dim3(256), 0, s->stream, s->dftPk, (long)s->nSelS * count, -INFINITY);
-                s->dftBin = dft_bin(s->nTs, s->cfg.dt * s->cfg.sensorSub, s->cfg.freq);
-            }
-        }
-        // a dense box of voxels? (count == volume of the bounding box: every voxel of the box is a sensor); BFD_SENSOR_BOX=0 keeps the index list in use
-        s->sensIsBox = false;
-        bool tryBox = count > 0;
-        if (const char *ev = getenv("BFD_SENSOR_BOX")) tryBox = tryBox && atoi(ev) != 0;
-        if (!rc && e == hipSuccess && tryBox) {
-            unsigned init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u}, mm[6];
-            unsigned *dmm = (unsigned *)dcount;          // reuse: 4 bytes are not enough
-            unsigned *dbox = nullptr;
-            e = hipMalloc((void **)&dbox, sizeof init);
-            if (e == hipSuccess) e = hipMemcpyAsync(dbox, init, sizeof init, hipMemcpyHostToDevice, s->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(sensor_bounds, dim3(std::min(grid_for((long)count), 1024)), dim3(256), 0, s->stream, d, s->sensLin, (long)count, dbox);
-                e = hipMemcpyAsync(mm, dbox, sizeof mm, hipMemcpyDeviceToHost, s->stream);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-            if (dbox) hipFree(dbox);
-            (void)dmm;
-            if (e == hipSuccess) {
-                const long bx = (long)mm[3] - mm[0] + 1, by = (long)mm[4] - mm[1] + 1, bz = (long)mm[5] - mm[2] + 1;
-                if (bx * by * bz == (long)count) {
-                    s->sensIsBox = true;
-                    s->sensBox[0] = (int)bx; s->sensBox[1] = (int)by; s->sensBox[2] = (int)mm[0]; s->sensBox[3] = (int)mm[1]; s->sensBox[4] = (int)mm[2];
-                }
-            }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    }
-    hipFree(tmp); hipFree(flags); hipFree(sel); hipFree(dcount); if (work) hipFree(work);
-    if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_set_sensor_map: ") + hipGetErrorString(e));
-    if (rc) return rc;
-    if (nSensors) *nSensors = s->nSensors;
     return 0;
 }
 
@@ -1285,16 +918,15 @@ static TileGrid choose_tile_grid(bfd_sim *s)
 // class flags and material of every sub-tile, from the device
 static int fetch_tile_classes(bfd_sim *s, int n, std::vector<int> &flags, std::vector<int> &mats)
 {
-    int *dflags = nullptr, *dmats = nullptr;
-    BFD_HIP(hipMalloc((void **)&dflags, n * sizeof(int)));
-    hipError_t e = hipMalloc((void **)&dmats, n * sizeof(int));
+    DevTemp<int> dflags, dmats;
+    BFD_HIP(dflags.alloc(n));
+    hipError_t e = dmats.alloc(n);
     if (e == hipSuccess) {
         bfd_launch_classify(s->d, s->stream, dflags, dmats);
         e = hipMemcpyAsync(flags.data(), dflags, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(mats.data(), dmats, n * sizeof(int), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(dflags); if (dmats) hipFree(dmats);
     if (e != hipSuccess) BFD_FAIL(-10, std::string("classify tiles: ") + hipGetErrorString(e));
     return 0;
 }
@@ -1513,18 +1145,14 @@ static int build_balance_maps(bfd_sim *s, const std::vector<int4> &all)
 // decides whether the solid state is compact
 static int build_shear_list(bfd_sim *s, const TileGrid &G, int *countOut, bool *compactOut, std::vector<unsigned> &hostCells)
 {
-    unsigned char *flag = nullptr; unsigned *sel = nullptr; int *dcount = nullptr; void *work = nullptr;
-    hipError_t e = hipMalloc((void **)&flag, s->nloc);
-    if (e == hipSuccess) e = hipMalloc((void **)&sel, s->nloc * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void **)&dcount, sizeof(int));
+    DevTemp<unsigned char> flag; DevTemp<unsigned> sel; DevTemp<int> dcount; DevTemp<char> work;
+    hipError_t e = flag.alloc(s->nloc);
+    if (e == hipSuccess) e = sel.alloc(s->nloc);
+    if (e == hipSuccess) e = dcount.alloc(1);
     int count = 0, rc = 0;
     if (e == hipSuccess) {
         bfd_launch_mark_solid(s->d, s->stream, flag, (long)s->nloc);
-        size_t wbytes = 0;
-        hipcub::CountingInputIterator<unsigned> ids(0);
-        e = hipcub::DeviceSelect::Flagged(nullptr, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
-        if (e == hipSuccess) e = hipMalloc(&work, std::max<size_t>(wbytes, 1));
-        if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged(work, wbytes, ids, flag, sel, dcount, (int)s->nloc, s->stream);
+        e = select_flagged(flag, sel, dcount, (int)s->nloc, s->stream, work);
         if (e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     }
@@ -1533,19 +1161,18 @@ static int build_shear_list(bfd_sim *s, const TileGrid &G, int *countOut, bool *
     // list order (bfd_kernels_v2.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
     // touched one band-plane earlier instead of one whole plane of the shell
     if (e == hipSuccess && count > 0) {
-        unsigned long long *k0 = nullptr, *k1 = nullptr; unsigned *v1 = nullptr; void *w2 = nullptr; size_t w2b = 0;
-        e = hipMalloc((void **)&k0, (size_t)count * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&k1, (size_t)count * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&v1, (size_t)count * 4);
+        DevTemp<unsigned long long> k0, k1; DevTemp<unsigned> v1; DevTemp<char> w2; size_t w2b = 0;
+        e = k0.alloc((size_t)count);
+        if (e == hipSuccess) e = k1.alloc((size_t)count);
+        if (e == hipSuccess) e = v1.alloc((size_t)count);
         if (e == hipSuccess) {
             bfd_launch_shear_order_keys(s->d, s->stream, sel, k0, count, G.lowPlanes, G.hiStart);
-            e = hipcub::DeviceRadixSort::SortPairs(nullptr, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
+            e = hipcub::DeviceRadixSort::SortPairs(nullptr, w2b, k0.p, k1.p, sel.p, v1.p, count, 0, 46, s->stream);
         }
-        if (e == hipSuccess) e = hipMalloc(&w2, std::max<size_t>(w2b, 1));
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(w2, w2b, k0, k1, sel, v1, count, 0, 46, s->stream);
+        if (e == hipSuccess) e = w2.alloc(std::max<size_t>(w2b, 1));
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs((void *)w2.p, w2b, k0.p, k1.p, sel.p, v1.p, count, 0, 46, s->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(sel, v1, (size_t)count * 4, hipMemcpyDeviceToDevice, s->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        if (k0) hipFree(k0); if (k1) hipFree(k1); if (v1) hipFree(v1); if (w2) hipFree(w2);
     }
     // Compact solid state (bfd_dev::cssRow): Sxx, Syy, the shear stresses and the five memory variables Rxx, Ryy, Rxy, Rxz, Ryz of the listed cells in
     // list order. Needs the row-contiguous list order. In a Z-slab the ghost planes of Sxz / Syz stay in the
@@ -1563,7 +1190,6 @@ static int build_shear_list(bfd_sim *s, const TileGrid &G, int *countOut, bool *
         if (!rc && e == hipSuccess) bfd_launch_shear_coefficients(s->d, s->stream, s->tiles.shearCells, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.shearTab, s->cfg.nMat, count);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     }
-    if (flag) hipFree(flag); if (sel) hipFree(sel); if (dcount) hipFree(dcount); if (work) hipFree(work);
     if (e != hipSuccess) BFD_FAIL(-10, std::string("shear list: ") + hipGetErrorString(e));
     if (rc) return rc;
     s->tiles.nShear = count;
@@ -1601,11 +1227,11 @@ static int setup_compact_state(bfd_sim *s, const TileGrid &G, int count, const s
 // a compact state set aside before a rebuild in the middle of a run: the values of the old list into the new one (or, should the new state not be compact, into the full-volume arrays)
 static int carry_compact_in(bfd_sim *s, int count, const unsigned *oldCells, long oldN, const float *oldComp)
 {
-    float *tmp = nullptr;
+    DevTemp<float> tmp(true);
     const size_t g = 2 * (size_t)s->d.plane;
     float *newComp[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
     float *full[10] = {s->d.Sxx, s->d.Syy, s->d.Sxy, s->d.Sxz, s->d.Syz, s->d.Rxx, s->d.Ryy, s->d.Rxy, s->d.Rxz, s->d.Ryz};
-    hipError_t e2 = s->d.cssRow ? malloc_or_release_cache((void **)&tmp, s->nalloc * sizeof(float)) : hipSuccess;
+    hipError_t e2 = s->d.cssRow ? tmp.alloc(s->nalloc) : hipSuccess;
     // the new state is not compact (no solid cell left, or the form was switched off): the full-volume arrays take over, and the owned planes
     // of buffers that hosted compact arrays hold list-ordered values, not fields: cleared before the old values are scattered into them
     for (int a = 0; a < 10 && e2 == hipSuccess && !s->d.cssRow; a++) e2 = hipMemsetAsync(full[a], 0, s->nloc * sizeof(float), s->stream);
@@ -1617,7 +1243,6 @@ static int carry_compact_in(bfd_sim *s, int count, const unsigned *oldCells, lon
         } else bfd_launch_css_scatter(s->stream, oldCells, oldN, oldComp + (size_t)a * oldN, full[a]);
     }
     if (e2 == hipSuccess) e2 = hipStreamSynchronize(s->stream);
-    if (tmp) hipFree(tmp);
     if (e2 != hipSuccess) BFD_FAIL(-10, std::string("compact solid state, list rebuilt in the middle of a run: ") + hipGetErrorString(e2));
     if (!s->d.cssRow && s->tiles.shearR) { bfd_launch_gather_shear_memory(s->d, s->stream, &s->tiles); BFD_HIP(hipStreamSynchronize(s->stream)); }
     return 0;
@@ -1635,13 +1260,12 @@ static int account_algorithmic_bytes(bfd_sim *s, int tx, const std::vector<int4>
     // class counts over the cells of the solid runs (fluid / solid centre, with / without memory variables, active edges)
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
     if (T.nSolid && s->cfg.kernelVariant != 2) {
-        unsigned long long *dc = nullptr;
-        BFD_HIP(hipMalloc((void **)&dc, sizeof cnt));
+        DevTemp<unsigned long long> dc;
+        BFD_HIP(dc.alloc(6));
         hipMemsetAsync(dc, 0, sizeof cnt, s->stream);
         bfd_launch_count_solid_cells(s->d, s->stream, s->tiles.runs + T.nFluid, T.nSolid, dc);
         hipMemcpyAsync(cnt, dc, sizeof cnt, hipMemcpyDeviceToHost, s->stream);
         const hipError_t e = hipStreamSynchronize(s->stream);
-        hipFree(dc);
         if (e != hipSuccess) BFD_FAIL(-10, std::string("solid cell counts: ") + hipGetErrorString(e));
     }
     auto overlap = [](int a, int b, int lo, int hi) { return (double)std::max(0, std::min(b, hi) - std::max(a, lo)); };
@@ -1686,13 +1310,12 @@ static int account_algorithmic_bytes(bfd_sim *s, int tx, const std::vector<int4>
         for (int a = 0; a < 2; a++) { if (s->d.cssRow) B[a][BFD_K_STRESS_FLUID] += bsf; else B[a][BFD_K_STRESS_SOLID] += bs; B[a][BFD_K_VELOCITY_SOLID] += bv; }
     }
     if (s->tiles.nShear) {       // sparse shear: cell index + 6 coefficients + V of the cell + read-modify-write of S and R per active edge
-        unsigned long long *dc = nullptr, hc[2] = {0, 0};
-        BFD_HIP(hipMalloc((void **)&dc, sizeof hc));
+        DevTemp<unsigned long long> dc; unsigned long long hc[2] = {0, 0};
+        BFD_HIP(dc.alloc(2));
         hipMemsetAsync(dc, 0, sizeof hc, s->stream);
-        hipLaunchKernelGGL(count_active_edges, dim3(grid_for(s->tiles.nShear)), dim3(256), 0, s->stream, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.nShear, dc);
+        hipLaunchKernelGGL(count_active_edges, dim3(grid_for(s->tiles.nShear)), dim3(256), 0, s->stream, s->tiles.shearCoef, s->tiles.shearCodes, s->tiles.nShear, dc.p);
         hipMemcpyAsync(hc, dc, sizeof hc, hipMemcpyDeviceToHost, s->stream);
         const hipError_t e = hipStreamSynchronize(s->stream);
-        hipFree(dc);
         if (e != hipSuccess) BFD_FAIL(-10, std::string("shear edge count: ") + hipGetErrorString(e));
         s->tiles.nShearExplicit = (long)hc[1];
         // per listed cell: index 4 + edge codes 4 + V 12; per edge with explicit coefficients 8; per active edge S and R r/w 16; compact solid
@@ -1715,11 +1338,10 @@ static int build_tile_lists(bfd_sim *s)
     // the same for a compact solid state: its ten arrays are set aside with their list (the full-volume buffers may host the compact arrays
     // themselves) and re-entered into the new list through one full-volume temporary, array by array, once that list exists
     const bool carryCompact = s->step > 0 && s->d.cssRow && s->tiles.nShear > 0;
-    unsigned *oldCells = nullptr; float *oldComp = nullptr; const long oldN = s->tiles.nShear;
-    struct FreeOnExit { float **p; ~FreeOnExit() { if (*p) hipFree(*p); } } freeOldComp{&oldComp};       // also on the error returns below
+    unsigned *oldCells = nullptr; DevTemp<float> oldComp; const long oldN = s->tiles.nShear;
     if (carryCompact) {
         float *src[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
-        BFD_HIP(hipMalloc((void **)&oldComp, 10 * (size_t)oldN * sizeof(float)));
+        BFD_HIP(oldComp.alloc(10 * (size_t)oldN));
         for (int a = 0; a < 10; a++) BFD_HIP(hipMemcpyAsync(oldComp + (size_t)a * oldN, src[a], (size_t)oldN * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
         BFD_HIP(hipStreamSynchronize(s->stream));
         oldCells = s->tiles.shearCells; s->tiles.shearCells = nullptr;       // released below, after the new list has taken the values over
@@ -1869,12 +1491,6 @@ static int check_ready(bfd_sim *s)
 // state flips where the step counter advances. Bit-identical to accumulating in every step; BFD_PAIR_ACC=0 selects that path.
 // Off with stress-type sources (they change Szz between the two kernels), outside variants 0 / 3, with the second copies of variant 4,
 // and with quiet runs (those flavours accumulate in 2 % of a call's steps). Graph replay covers non-accumulating steps only.
-static int pressure_slot(const bfd_sim *s)
-{
-    int qP = -1;
-    for (int q = 0; q < s->nSelR; q++) if (s->selR[q] == BFD_MAP_PRESSURE) qP = q;
-    return qP;
-}
 // The accumulating steps of this engine pair: ONE predicate for the byte tables (build_tile_lists: quiet = quiet_runs_wanted, the run count just
 // built) and for the launches (pairing_step: quiet = the activity map is in use, the current run count)
 static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid)
@@ -1887,18 +1503,6 @@ static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid)
 static bool pairing_step(const bfd_sim *s)
 {
     return s->pairDone || (s->step >= s->accStart && s->tilesReady && pair_engine(s, s->d.act != nullptr, s->tiles.nFluid));
-}
-// st: the stream the following launches go to (default: the engine's)
-static int flush_pending(bfd_sim *s, hipStream_t st)
-{
-    if (!s->pendingAcc) return 0;        // also between the half-steps of the second step of a pair: its stress half-step has added both (pairDone)
-    s->pendingAcc = false;
-    const int qP = pressure_slot(s);
-    if (qP < 0 || !s->tilesReady) return 0;
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    bfd_launch_flush_paired(s->d, st, s->acc ? s->acc + (size_t)qP * s->nloc : nullptr, s->pk ? s->pk + (size_t)qP * s->nloc : nullptr, &s->tiles);
-    BFD_HIP(hipGetLastError());
-    return 0;
 }
 
 // sources of one part of a half-step: part 0 all, 1 = first+last z-chunk, 2 = the chunks between
@@ -2009,38 +1613,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
     if (s->nSrcVox && s->cfg.typeSource < 2 && s->step < s->lengthSource) { rc = inject_part(s, part, new_velocity_view(d), st); if (rc) return rc; }
     if (part == 1) { BFD_HIP(hipGetLastError()); return 0; }
     if (s->pingpong) swap_fields(s->d);
-    // end of the time step: remaining accumulators, sensors
-    if (accNow && !(qP >= 0 && s->nSelR == 1)) {
-        SelList L; L.n = s->nSelR; memcpy(L.sel, s->selR, sizeof L.sel);
-        for (int q = 0; q < BFD_MAP_COUNT; q++) L.skip[q] = (q == qP);
-        dim3 block(64, 4, 1), grid((d.N1 + 63) / 64, (d.N2 + 3) / 4, d.nk);
-        hipLaunchKernelGGL(accumulate_maps, grid, block, 0, st, d, L, s->acc, s->pk, (long)s->nloc);
-    }
-    if (s->nSensors && (s->sensOut || s->dftAcc) && n % s->cfg.sensorSub == 0 && n / s->cfg.sensorSub >= s->cfg.sensorStart) {
-        const int col = n / s->cfg.sensorSub - s->cfg.sensorStart;
-        if (col < s->nTs) {
-            SelList L; L.n = s->nSelS; memcpy(L.sel, s->selS, sizeof L.sel); memset(L.skip, 0, sizeof L.skip);
-            // compact solid state: the sensors' list entries, resolved when first needed after a list was built (round 6; every capture used to
-            // walk the class bytes of the row for each solid sensor: 1.08 ms per capture on the shear medium at 512^3 against 0.42 ms at C3)
-            const int *ent = nullptr;
-            if (d.cssRow) {
-                if (!s->sensEntValid) {
-                    if (!s->sensEnt) { rc = dev_alloc(s, &s->sensEnt, (size_t)s->nSensors, false); if (rc) return rc; }
-                    hipLaunchKernelGGL(sensor_entries, dim3(grid_for(s->nSensors)), dim3(256), 0, st, d, s->sensLin, (long)s->nSensors, s->sensEnt);
-                    s->sensEntValid = true;
-                }
-                ent = s->sensEnt;
-            }
-            SensorBox B = {(unsigned)s->sensBox[0], (unsigned)s->sensBox[0] * (unsigned)s->sensBox[1], (unsigned)s->sensBox[2], (unsigned)s->sensBox[3], (unsigned)s->sensBox[4]};
-            const uint32_t *lin = s->sensIsBox ? nullptr : s->sensLin;
-            if (s->sensOut)
-                hipLaunchKernelGGL(record_sensors, dim3(grid_for(s->nSensors)), dim3(256), 0, st, d, L, lin, B, ent,
-                                   (long)s->nSensors, s->sensOut, col, s->nTs);
-            else
-                hipLaunchKernelGGL(accumulate_sensor_dft, dim3(grid_for(s->nSensors)), dim3(256), 0, st, d, L, lin, B, ent,
-                                   (long)s->nSensors, s->dftAcc, s->dftPk, col, s->nTs, s->dftBin);
-        }
-    }
+    rc = bfd_step_outputs(s, st, qP); if (rc) return rc;      // end of the time step: remaining accumulators, sensors
     BFD_HIP(hipGetLastError());
     if (paired) { s->pendingAcc = !s->pairDone; s->pairDone = false; }      // first step of a pair: the maps lack it; second: settled in its stress half-step
     s->step++;
@@ -2173,7 +1746,7 @@ int bfd_halo_region(bfd_sim *s, int32_t group, int32_t f, int32_t side, int32_t 
 int64_t bfd_placement_cache_release(void)
 {
     const int64_t freed = bfd_placement_cache_drop_all();
-    pin_release_all();          // host memory: not part of the count
+    bfd_release_pinned_pieces();          // host memory: not part of the count
     (void)hipGetLastError();
     return freed;
 }
@@ -2271,331 +1844,12 @@ int bfd_reset(bfd_sim *s)
     }
     if (s->tiles.shearR && s->tiles.nShear) BFD_HIP(hipMemsetAsync(s->tiles.shearR, 0, 3 * (size_t)s->tiles.nShear * sizeof(float), s->stream));
     if (s->tiles.css && s->tiles.cssCap) BFD_HIP(hipMemsetAsync(s->tiles.css, 0, 10 * (size_t)s->tiles.cssCap * sizeof(float), s->stream));      // hosted compact arrays were zeroed with their buffers
-    if (s->acc) BFD_HIP(hipMemsetAsync(s->acc, 0, (size_t)s->nSelR * s->nloc * sizeof(float), s->stream));
-    if (s->pk) BFD_HIP(hipMemsetAsync(s->pk, 0, (size_t)s->nSelR * s->nloc * sizeof(float), s->stream));
-    if (s->sensOut) BFD_HIP(hipMemsetAsync(s->sensOut, 0, (size_t)s->nSelS * s->nTs * (size_t)s->nSensors * sizeof(float), s->stream));
-    if (s->dftAcc) {
-        BFD_HIP(hipMemsetAsync(s->dftAcc, 0, 2 * (size_t)s->nSelS * (size_t)s->nSensors * sizeof(double), s->stream));
-        if (s->nSensors > 0) hipLaunchKernelGGL(fill_float, dim3(grid_for((long)s->nSelS * s->nSensors)), dim3(256), 0, s->stream, s->dftPk, (long)s->nSelS * s->nSensors, -INFINITY);
-    }
+    { const int rc = bfd_clear_outputs(s); if (rc) return rc; }
     s->step = 0; s->stepDevValid = false; s->actReady = false;         // the activity map starts over with the state
     s->pendingAcc = s->pairDone = false;                               // the maps were cleared: nothing is outstanding
     BFD_HIP(hipStreamSynchronize(s->stream));
     drain_pack_jobs(s);
     for (int b = 0; b < 2; b++) s->tileLoaded[b] = -1;        // the streamed source table starts over (tiles are re-packed on demand)
-    return 0;
-}
-
-int64_t bfd_num_sensors(bfd_sim *s) { return s ? s->nSensors : -1; }
-int32_t bfd_num_sensor_steps(bfd_sim *s) { return s ? s->nTs : -1; }
-
-int bfd_get_sensor_index(bfd_sim *s, uint32_t *index)
-{
-    if (!s || (!index && s->nSensors)) BFD_FAIL(-1, "bfd_get_sensor_index: null argument");
-    if ((long)s->d.N1 * s->d.N2 * s->d.N3 >= (1L << 32) - 1) BFD_FAIL(-2, "domain too large for 32-bit sensor indices");
-    if (!s->nSensors) return 0;
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    bfd_advise_result_buffer(index, (size_t)s->nSensors * sizeof(uint32_t));
-    BFD_HIP(hipMemcpy(index, s->sensLin, (size_t)s->nSensors * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t off = (uint32_t)((size_t)s->d.k0 * s->d.plane + 1);
-    for (int64_t v = 0; v < s->nSensors; v++) index[v] += off;
-    return 0;
-}
-
-}  // extern "C"
-
-// A large result block lands in host memory the caller has just allocated and never touched (a fresh numpy array): the copy then runs at the rate the
-// kernel can fault 4 KB pages in. Transparent huge pages are in `madvise` mode on the ROCm images, so the range is advised first: one hipMemcpy of
-// 4.3 GiB into untouched memory 0.46 -> 0.22 s on the MI355X box (profiles/r6/d2h_into_untouched_memory.txt). Advice only: a mapping that cannot
-// take it (file-backed, already populated) is left as it is.
-void bfd_advise_result_buffer(void *p, size_t bytes)
-{
-    if (!p || bytes < ((size_t)8 << 20)) return;
-    const uintptr_t a = ((uintptr_t)p + 4095) & ~(uintptr_t)4095, b = ((uintptr_t)p + bytes) & ~(uintptr_t)4095;
-    if (b > a) (void)madvise((void *)a, (size_t)(b - a), MADV_HUGEPAGE);
-}
-
-// Device -> pageable host for the large result blocks (sensor series, maps): T host threads, each moving its slice in 16 MB pieces through two pinned
-// buffers of its own (the next piece in flight while the last one is copied out). One hipMemcpy is bound by the single thread that copies out of the
-// runtime's staging buffers: 4.3 GiB into untouched huge-page memory 0.22 s, this way 0.11 s (profiles/r6/d2h_into_untouched_memory.txt). `after`: the
-// stream whose work produces src (waited for here). Anything that fails on the way falls back to the plain copy.
-// produce (optional): fills a device piece buffer with bytes [o, o + len) of the block on the given stream -- the block then never exists as a whole
-// on the device (the sensor series: no 4.6 GB scratch allocation, which in a short call waited 5 s when a placement search had just released its
-// candidates -- the runtime gives them back in the background). Returns hipErrorNotSupported when it declines (small block, threads off) and a producer was given: the caller takes its old way.
-static hipError_t copy_out_large(int device, void *dst, const void *src, size_t bytes, hipStream_t after,
-                                 const std::function<void(float *, size_t, size_t, hipStream_t)> *produce = nullptr)
-{
-    int T = 4;
-    if (const char *ev = getenv("BFD_D2H_THREADS")) T = atoi(ev);
-    size_t PIECE = (size_t)16 << 20, least = (size_t)256 << 20;
-    if (const char *ev = getenv("BFD_D2H_PIECE_KB")) PIECE = std::max((size_t)4096, ((size_t)atol(ev) << 10) & ~(size_t)4095);      // tests: small grids through the same code
-    if (const char *ev = getenv("BFD_D2H_MIN_MB")) least = (size_t)atol(ev) << 20;
-    if (T < 2 || bytes < least || bytes < (size_t)T * 4096) {
-        if (produce) return hipErrorNotSupported;
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, after);
-        return e == hipSuccess ? hipStreamSynchronize(after) : e;
-    }
-    T = std::min(T, 16);
-    hipError_t e = hipStreamSynchronize(after);
-    if (e != hipSuccess) return e;
-    std::vector<char *> pin(2 * (size_t)T, nullptr);
-    bool ok = true;
-    for (auto &q : pin) if (ok && !(q = pin_take(PIECE))) ok = false;
-    std::vector<float *> dpiece(produce ? 2 * (size_t)T : 0, nullptr);
-    for (auto &q : dpiece) if (ok && hipMalloc((void **)&q, PIECE) != hipSuccess) { q = nullptr; ok = false; (void)hipGetLastError(); }
-    std::vector<int> failed((size_t)T, 0);
-    if (ok) {
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; t++)
-            th.emplace_back([&, t] {
-                const size_t a = (bytes / T * t) & ~(size_t)4095, b = t + 1 == T ? bytes : (bytes / T * (t + 1)) & ~(size_t)4095;
-                hipStream_t st = nullptr;
-                hipEvent_t ev[2] = {nullptr, nullptr};
-                if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-                    hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess) failed[t] = 1;
-                const size_t np = (b - a + PIECE - 1) / PIECE;
-                auto issue = [&](size_t i) {
-                    const size_t o = a + i * PIECE, len = std::min(PIECE, b - o);
-                    const void *from = (const char *)src + o;
-                    if (produce) { (*produce)(dpiece[2 * t + (i & 1)], o, len, st); from = dpiece[2 * t + (i & 1)]; if (hipGetLastError() != hipSuccess) failed[t] = 1; }
-                    if (hipMemcpyAsync(pin[2 * t + (i & 1)], from, len, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(ev[i & 1], st) != hipSuccess) failed[t] = 1;
-                };
-                if (!failed[t] && np) issue(0);
-                for (size_t i = 0; i < np && !failed[t]; i++) {
-                    if (i + 1 < np) issue(i + 1);
-                    if (failed[t] || hipEventSynchronize(ev[i & 1]) != hipSuccess) { failed[t] = 1; break; }
-                    const size_t o = a + i * PIECE, len = std::min(PIECE, b - o);
-                    memcpy((char *)dst + o, pin[2 * t + (i & 1)], len);
-                }
-                if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-                for (int q = 0; q < 2; q++) if (ev[q]) hipEventDestroy(ev[q]);
-            });
-        for (auto &x : th) x.join();
-        for (int t = 0; t < T; t++) if (failed[t]) ok = false;
-    }
-    for (auto &q : pin) pin_give(q, PIECE);
-    for (auto &q : dpiece) if (q) hipFree(q);
-    if (ok) return hipSuccess;
-    (void)hipGetLastError();
-    if (produce) return hipErrorNotSupported;
-    return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);      // the plain way
-}
-
-int bfd_sensors_into(bfd_sim *s, float *out, int64_t rowElems)
-{
-    // the series of selected map q go to out + q * rowElems (rowElems >= nSensors * nTs): a slab of a group
-    // writes straight into its columns of the caller's array
-    if (!s) BFD_FAIL(-1, "null sim");
-    const size_t row = (size_t)s->nTs * (size_t)s->nSensors, n = (size_t)s->nSelS * row;
-    if (!n) return 0;
-    if (s->cfg.sensorMode != 0) BFD_FAIL(-6, "bfd_get_sensors: the series are not stored with sensorMode 1 (use bfd_get_sensor_dft)");
-    if (!out || !s->sensOut) BFD_FAIL(-1, "bfd_get_sensors: null argument");
-    if (rowElems < (int64_t)row) BFD_FAIL(-2, "bfd_get_sensors: row shorter than nSensors * nSteps");
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    {   // piece by piece through the host threads, no scratch block on the device
-        hipError_t e = hipSuccess;
-        for (int q = 0; q < s->nSelS; q++) bfd_advise_result_buffer(out + (size_t)q * rowElems, row * sizeof(float));
-        const bool oneBlock = (size_t)rowElems == row;
-        for (int q = 0; q < (oneBlock ? 1 : s->nSelS) && e == hipSuccess; q++) {
-            const long v00 = oneBlock ? 0 : (long)q * (long)row;
-            const std::function<void(float *, size_t, size_t, hipStream_t)> produce = [&, v00](float *piece, size_t o, size_t len, hipStream_t st) {
-                const long cnt = (long)(len / sizeof(float));
-                hipLaunchKernelGGL(transpose_sensors_range, dim3(grid_for(cnt)), dim3(256), 0, st, s->sensOut, piece, (long)s->nSensors, s->nTs, v00 + (long)(o / sizeof(float)), cnt);
-            };
-            e = copy_out_large(s->cfg.device, out + (size_t)q * rowElems, nullptr, (oneBlock ? n : row) * sizeof(float), s->stream, &produce);
-        }
-        if (e == hipSuccess) return 0;
-        (void)hipGetLastError();      // declined (small block, BFD_D2H_THREADS < 2) or failed on the way: the whole block through a scratch copy
-    }
-    float *tmp = nullptr;
-    BFD_HIP(hipMalloc((void **)&tmp, n * sizeof(float)));
-    hipLaunchKernelGGL(transpose_sensors, dim3(grid_for((long)n)), dim3(256), 0, s->stream, s->sensOut, tmp, (long)s->nSensors, s->nTs, s->nSelS);
-    hipError_t e = hipSuccess;
-    for (int q = 0; q < s->nSelS; q++) bfd_advise_result_buffer(out + (size_t)q * rowElems, row * sizeof(float));
-    if ((size_t)rowElems == row) e = copy_out_large(s->cfg.device, out, tmp, n * sizeof(float), s->stream);
-    else
-        for (int q = 0; q < s->nSelS && e == hipSuccess; q++)
-            e = copy_out_large(s->cfg.device, out + (size_t)q * rowElems, tmp + (size_t)q * row, row * sizeof(float), s->stream);
-    hipFree(tmp);
-    if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_get_sensors: ") + hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" {
-
-int bfd_get_sensors(bfd_sim *s, float *out)
-{
-    if (!s) BFD_FAIL(-1, "null sim");
-    return bfd_sensors_into(s, out, (int64_t)s->nTs * (int64_t)s->nSensors);
-}
-
-static int download_volume(bfd_sim *s, const float *devXfast, float *out, int64_t s1, int64_t s2, int64_t s3)
-{
-    const bfd_dev &d = s->d;
-    if (s1 < 0 || s2 < 0 || s3 < 0) BFD_FAIL(-2, "negative strides are not supported");
-    const size_t span = span_elems(d.N1, d.N2, d.nk, s1, s2, s3);
-    float *tmp = nullptr;
-    BFD_HIP(hipMalloc((void **)&tmp, span * sizeof(float)));
-    hipError_t e = hipSuccess;
-    bfd_advise_result_buffer(out, span * sizeof(float));
-    if (span != s->nloc) {   // non-dense view: keep what the caller has in the gaps
-        e = hipMemcpyAsync(tmp, out, span * sizeof(float), hipMemcpyHostToDevice, s->stream);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(scatter_from_xfast, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, devXfast, tmp,
-                           (long)s1, (long)s2, (long)s3, d.N1, d.N2, d.nk);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = copy_out_large(s->cfg.device, out, tmp, span * sizeof(float), s->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(tmp);
-    if (e != hipSuccess) BFD_FAIL(-10, std::string("download: ") + hipGetErrorString(e));
-    return 0;
-}
-
-static void expand_if_collapsed(bfd_sim *s);
-
-int bfd_get_map(bfd_sim *s, int32_t kind, int32_t map, float *out, int64_t s1, int64_t s2, int64_t s3)
-{
-    if (!s || !out) BFD_FAIL(-1, "bfd_get_map: null argument");
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    int q = -1;
-    for (int a = 0; a < s->nSelR; a++) if (s->selR[a] == map) q = a;
-    if (kind != BFD_KIND_LAST && q < 0) BFD_FAIL(-2, "bfd_get_map: map was not selected in selMapsRMS");
-    float *tmp = nullptr;
-    if (kind == BFD_KIND_RMS || kind == BFD_KIND_PEAK) { const int rf = flush_pending(s); if (rf) return rf; }
-    BFD_HIP(hipMalloc((void **)&tmp, s->nloc * sizeof(float)));
-    int rc = 0;
-    if (kind == BFD_KIND_RMS) {
-        if (!s->acc) { hipFree(tmp); BFD_FAIL(-2, "bfd_get_map: RMS was not selected (SelRMSorPeak)"); }
-        const int nAcc = s->step - s->accStart;
-        hipLaunchKernelGGL(finalize_rms, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, s->acc + (size_t)q * s->nloc, tmp,
-                           (long)s->nloc, (float)(nAcc > 0 ? nAcc : 1));
-        rc = download_volume(s, tmp, out, s1, s2, s3);
-    } else if (kind == BFD_KIND_PEAK) {
-        if (!s->pk) { hipFree(tmp); BFD_FAIL(-2, "bfd_get_map: peak was not selected (SelRMSorPeak)"); }
-        rc = download_volume(s, s->pk + (size_t)q * s->nloc, out, s1, s2, s3);
-    } else if (kind == BFD_KIND_LAST) {
-        if (map < 0 || map >= BFD_MAP_COUNT) { hipFree(tmp); BFD_FAIL(-2, "bfd_get_map: bad map id"); }
-        if (map >= BFD_MAP_SIGMAXX && map <= BFD_MAP_SIGMAZZ) expand_if_collapsed(s);
-        hipLaunchKernelGGL(last_map, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, s->d, map, tmp, (long)s->nloc);
-        rc = download_volume(s, tmp, out, s1, s2, s3);
-    } else {
-        rc = -2; bfd_set_error("bfd_get_map: bad kind");
-    }
-    hipFree(tmp);
-    return rc;
-}
-
-static void expand_if_collapsed(bfd_sim *s)
-{
-    if (s->d.cssRow) return;        // compact solid state: Sxx, Syy, Rxx, Ryy full-volume are not output scratch (they may host the compact arrays); bfd_get_field builds its outputs in a temporary
-    if (s->classesReady)
-        hipLaunchKernelGGL(expand_normal, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, s->d, (long)s->nloc);
-}
-
-int bfd_get_field(bfd_sim *s, int32_t a, float *out, int64_t s1, int64_t s2, int64_t s3)
-{
-    if (!s || !out || a < 0 || a > 14) BFD_FAIL(-1, "bfd_get_field: bad argument");
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    expand_if_collapsed(s);
-    const bfd_dev &d = s->d;
-    static const int cssOf[15] = {-1, -1, -1, 0, 1, -1, 2, 3, 4, 5, 6, -1, 7, 8, 9};
-    if (d.cssRow && cssOf[a] >= 0) {       // not on tilesReady: a setter at step > 0 clears that flag, but list, row table and compact arrays stay as they are until the next step rebuilds them
-        // compact solid state: the field is assembled in a temporary -- zeros, the Szz / Rzz copy at the fluid cells (Sxx, Syy, Rxx, Ryy), the compact
-        // values at the listed cells
-        const float *comp[10] = {d.cSxx, d.cSyy, d.cSxy, d.cSxz, d.cSyz, d.cRxx, d.cRyy, d.cRxy, d.cRxz, d.cRyz};
-        float *tmp = nullptr;
-        BFD_HIP(malloc_or_release_cache((void **)&tmp, s->nloc * sizeof(float)));
-        hipError_t e = hipMemsetAsync(tmp, 0, s->nloc * sizeof(float), s->stream);
-        if (e == hipSuccess && (a == 3 || a == 4 || a == 9 || a == 10))
-            hipLaunchKernelGGL(copy_at_fluid_cells, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, d, a >= 9 ? (const float *)d.Rzz : (const float *)d.Szz, tmp, (long)s->nloc);
-        bfd_launch_css_scatter(s->stream, s->tiles.shearCells, s->tiles.nShear, comp[cssOf[a]], tmp);
-        const int rc = e == hipSuccess ? download_volume(s, tmp, out, s1, s2, s3) : -10;
-        hipFree(tmp);
-        if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_get_field: ") + hipGetErrorString(e));
-        return rc;
-    }
-    if (a >= 12 && s->tilesReady && s->cfg.kernelVariant != 1) bfd_launch_scatter_shear_memory(s->d, s->stream, &s->tiles);   // Rxy, Rxz, Ryz live beside the sparse list
-    float *cur[15] = {d.Vx, d.Vy, d.Vz, d.Sxx, d.Syy, d.Szz, d.Sxy, d.Sxz, d.Syz, d.Rxx, d.Ryy, d.Rzz, d.Rxy, d.Rxz, d.Ryz};
-    return download_volume(s, cur[a], out, s1, s2, s3);
-}
-
-// numpy.fft.fftfreq(n, d) bin closest to freq (first minimum, like np.argmin; BASE:2498-2499)
-static int dft_bin(int n, double d, double freq)
-{
-    int best = 0; double bd = INFINITY;
-    for (int k = 0; k < n; k++) {
-        const int kk = (k < (n + 1) / 2) ? k : k - n;
-        const double f = (double)kk / ((double)n * d);
-        const double e = fabs(f - freq);
-        if (e < bd) { bd = e; best = k; }
-    }
-    return best;
-}
-
-int bfd_get_sensor_dft(bfd_sim *s, double freq, float *outReIm, float *outPeak)
-{
-    if (!s) BFD_FAIL(-1, "null sim");
-    const size_t n = (size_t)s->nSelS * (size_t)s->nSensors;
-    if (!n || s->nTs <= 0) return 0;
-    if (!outReIm || !(s->sensOut || s->dftAcc)) BFD_FAIL(-1, "bfd_get_sensor_dft: null argument");
-    BFD_HIP(hipSetDevice(s->cfg.device));
-    const int bin = dft_bin(s->nTs, s->cfg.dt * s->cfg.sensorSub, freq);
-    bfd_advise_result_buffer(outReIm, 2 * n * sizeof(float));
-    bfd_advise_result_buffer(outPeak, n * sizeof(float));
-    if (s->dftAcc) {         // accumulated in the loop
-        if (bin != s->dftBin) BFD_FAIL(-2, "bfd_get_sensor_dft: with sensorMode 1 the bin is the one of the sim's own frequency");
-        float *dre = nullptr;
-        BFD_HIP(hipMalloc((void **)&dre, 2 * n * sizeof(float)));
-        hipLaunchKernelGGL(finalize_sensor_dft, dim3(grid_for((long)(2 * n))), dim3(256), 0, s->stream, s->dftAcc, dre, (long)(2 * n), 2.0 / (double)s->nTs);
-        hipError_t e = hipMemcpyAsync(outReIm, dre, 2 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess && outPeak) e = hipMemcpyAsync(outPeak, s->dftPk, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        hipFree(dre);
-        if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_get_sensor_dft: ") + hipGetErrorString(e));
-        return 0;
-    }
-    float *dre = nullptr, *dpk = nullptr;
-    BFD_HIP(hipMalloc((void **)&dre, 2 * n * sizeof(float)));
-    hipError_t e = hipMalloc((void **)&dpk, n * sizeof(float));
-    for (int q = 0; q < s->nSelS && e == hipSuccess; q++) {      // device block is [q][nTs][nSensors]
-        hipLaunchKernelGGL(dft_series, dim3(grid_for(s->nSensors)), dim3(256), 0, s->stream,
-                           s->sensOut + (size_t)q * s->nTs * s->nSensors, 1L, (long)s->nSensors, (long)s->nSensors, s->nTs, bin,
-                           dre + 2 * (size_t)q * s->nSensors, dpk + (size_t)q * s->nSensors);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(outReIm, dre, 2 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && outPeak) e = hipMemcpyAsync(outPeak, dpk, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(dre); if (dpk) hipFree(dpk);
-    if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_get_sensor_dft: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int bfd_dft_series(int32_t device, int64_t nSensors, int32_t nTs, const float *series, double dtSensor, double freq,
-                   float *outReIm, float *outPeak)
-{
-    if (nSensors < 0 || nTs <= 0 || (nSensors && (!series || !outReIm))) BFD_FAIL(-1, "bfd_dft_series: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, "bfd_dft_series: no HIP device available (no CPU fallback)");
-    if (device < 0 || device >= ndev) BFD_FAIL(-3, "bfd_dft_series: device ordinal out of range");
-    if (!nSensors) return 0;
-    BFD_HIP(hipSetDevice(device));
-    const size_t n = (size_t)nSensors;
-    float *din = nullptr, *dre = nullptr, *dpk = nullptr;
-    hipError_t e = hipMalloc((void **)&din, n * nTs * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dre, 2 * n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dpk, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(din, series, n * nTs * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(dft_series, dim3(grid_for((long)n)), dim3(256), 0, 0, din, (long)nTs, 1L, (long)n, nTs, dft_bin(nTs, dtSensor, freq), dre, dpk);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(outReIm, dre, 2 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && outPeak) e = hipMemcpy(outPeak, dpk, n * sizeof(float), hipMemcpyDeviceToHost);
-    if (din) hipFree(din); if (dre) hipFree(dre); if (dpk) hipFree(dpk);
-    if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_dft_series: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <future>
 #include <string>
 #include <vector>
@@ -214,6 +215,65 @@ void bfd_set_error(const std::string &s);
     } while (0)
 #define BFD_FAIL(code, msg) do { bfd_set_error(msg); return (code); } while (0)
 
+// hipMalloc that gives idle buffers of the placement cache (bfd_placement.hip) back to the device before it reports that memory ran out
+hipError_t malloc_or_release_cache(void **q, size_t bytes);
+// A device block that lives as long as its scope: the temporaries of the setters and getters. cacheAware = the block is drawn through
+// malloc_or_release_cache. Engine-lifetime memory goes through dev_alloc instead. It converts to T * wherever a pointer is expected; `.p` is written
+// only where a template would deduce DevTemp itself (kernel launches, hipcub).
+template <typename T>
+struct DevTemp {
+    T *p = nullptr; bool cacheAware;
+    explicit DevTemp(bool cacheAware_ = false) : cacheAware(cacheAware_) {}
+    DevTemp(const DevTemp &) = delete;
+    DevTemp &operator=(const DevTemp &) = delete;
+    ~DevTemp() { if (p) hipFree(p); }
+    hipError_t alloc(size_t count) { return cacheAware ? malloc_or_release_cache((void **)&p, count * sizeof(T)) : hipMalloc((void **)&p, count * sizeof(T)); }
+    operator T *() const { return p; }
+};
+
+inline int grid_for(long n, int block = 256) { return (int)std::min<long>((n + block - 1) / block, 256L * 32); }
+
+template <typename T>
+int dev_alloc(bfd_sim *s, T **p, size_t count, bool zero = true)
+{
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    BFD_HIP(malloc_or_release_cache(&q, bytes));
+    if (zero) BFD_HIP(hipMemsetAsync(q, 0, bytes, s->stream));
+    s->allocs.push_back(q);
+    s->devBytes += (int64_t)bytes;
+    *p = (T *)q;
+    return 0;
+}
+
+// frees an array obtained from dev_alloc before the sim is destroyed (inputs that are set again)
+template <typename T>
+void dev_release(bfd_sim *s, T **p)
+{
+    if (!*p) return;
+    auto it = std::find(s->allocs.begin(), s->allocs.end(), (void *)*p);
+    if (it != s->allocs.end()) { hipFree(*it); s->allocs.erase(it); }
+    *p = nullptr;
+}
+
+inline size_t span_elems(int N1, int N2, int nk, int64_t s1, int64_t s2, int64_t s3)
+{
+    return (size_t)((N1 - 1) * s1 + (N2 - 1) * s2 + (nk - 1) * s3 + 1);
+}
+
+// the selected maps of a bit mask, ascending; returns their number (bfd_api.hip)
+int sel_list(uint32_t mask, int *sel);
+// paired accumulation (bfd_api.hip): adds the outstanding Pressure to the maps before anything reads or clears them, or changes what lies behind them;
+// st: the stream the following launches go to (default: the engine's)
+int flush_pending(bfd_sim *s, hipStream_t st);
+inline int flush_pending(bfd_sim *s) { return flush_pending(s, s->stream); }
+// flags[v] = 1 where the strided device copy `in` of a caller's uint32 map of the slab is not 0, v in x-fastest order; on the engine's stream
+// (bfd_api.hip: the layout kernel of the input setters)
+void bfd_launch_gather_flags(const bfd_sim *s, const uint32_t *in, long s1, long s2, long s3, uint8_t *flags);
+// ascending indices of the set flags among n, on the device: sel[0 .. *dcount). Queued on st; work = the select's scratch block, which the caller keeps
+// until it has synchronised (bfd_api.hip)
+hipError_t select_flagged(uint8_t *flags, uint32_t *sel, int *dcount, int n, hipStream_t st, DevTemp<char> &work);
+
 // an event from the engine's pool or a new one; null when none can be made (bfd_api.hip)
 hipEvent_t bfd_get_event(bfd_sim *s);
 // the kernels' views of the state arrays (bfd_dev) from the allocation bases stateBase / ppBase (bfd_api.hip)
@@ -225,9 +285,15 @@ int bfd_choose_placement(bfd_sim *s);
 bool bfd_placement_cache_put(int device, size_t bytes, void *p);
 void bfd_placement_cache_evict_other_sizes(int device, size_t bytes);
 int64_t bfd_placement_cache_drop_all(void);
-// madvise(MADV_HUGEPAGE) on a result buffer of the caller before a large device-to-host copy (bfd_api.hip)
+// what leaves the engine (bfd_outputs.hip): the end of a time step on stream st -- the maps the velocity kernels did not accumulate (qP = the slot
+// they did, -1 = none) and the sensor sample; the output arrays cleared on the engine's stream (bfd_reset); the pinned pieces of the large
+// device-to-host copies given back to the system (bfd_placement_cache_release)
+int bfd_step_outputs(bfd_sim *s, hipStream_t st, int qP);
+int bfd_clear_outputs(bfd_sim *s);
+void bfd_release_pinned_pieces(void);
+// madvise(MADV_HUGEPAGE) on a result buffer of the caller before a large device-to-host copy (bfd_outputs.hip)
 void bfd_advise_result_buffer(void *p, size_t bytes);
-// bfd_get_sensors with a row pitch: the series of selected map q at out + q * rowElems (bfd_group.hip: a slab writes into its columns)
+// bfd_get_sensors with a row pitch: the series of selected map q at out + q * rowElems (bfd_outputs.hip; bfd_group.hip: a slab writes into its columns)
 int bfd_sensors_into(bfd_sim *s, float *out, int64_t rowElems);
 // kernel launchers (bfd_kernels_*.hip)
 void bfd_launch_stress_v1(const bfd_dev &d, hipStream_t s);

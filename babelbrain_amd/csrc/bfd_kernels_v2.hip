@@ -642,7 +642,7 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
                 }
             }
             // COLLAPSED (no solid tile in the slab, no per-component stress output selected): nobody
-            // reads Sxx/Syy/Rxx/Ryy, so only the Szz/Rzz copy is kept (expanded on demand, bfd_api.hip)
+            // reads Sxx/Syy/Rxx/Ryy, so only the Szz/Rzz copy is kept (expanded on demand, bfd_outputs.hip)
             ST4((d.SzzW + ko), cij * 4u, val);
             if (PAIR) {
                 if (inner && k >= d.ND && k < d.N3 - d.ND) {

@@ -105,6 +105,16 @@ int64_t bfd_placement_cache_drop_all(void)
     if (haveCur) hipSetDevice(cur);
     return freed;
 }
+// hipMalloc that gives the idle buffers of the cache back to the device before it reports that memory ran out
+hipError_t malloc_or_release_cache(void **q, size_t bytes)
+{
+    hipError_t e = hipMalloc(q, bytes);
+    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+        (void)hipGetLastError();
+        if (bfd_placement_cache_release() > 0) e = hipMalloc(q, bytes);
+    }
+    return e;
+}
 
 // ---- the pair probe -----------------------------------------------------------------------------------------------------
 // device time of `reps` pair probes of the arrays at a and b (pointers to local plane 0), planes [0, kmax); < 0 on error

@@ -2,10 +2,15 @@
 """Per-kernel comparison of the gfx950 machine code of two builds of babelbrain_amd/csrc (refactor check).
 
     make -C <tree>/babelbrain_amd/csrc -j16 EXTRA=-Rpass-analysis=kernel-resource-usage > <tree>.log 2>&1     (both trees)
-    scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log
+    scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log [new=old ...]
+
+new=old (optional, e.g. bfd_outputs=bfd_api): kernels and resource records of object `new` of the second build are looked up under object `old`
+of the first (code that moved from one source file to another).
 
 The fat binary section of every object is unbundled (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler --unbundle),
 disassembled (llvm-objdump -d) and cut at the kernel symbols; the instruction text of a kernel (addresses and encodings dropped) and its resource remarks (registers, spills, scratch, occupancy, LDS) must be equal on both sides.
+The literal of the s_add_u32 behind an s_getpc_b64 is left out of the comparison: it is the distance from the instruction to a constant of the object, which changes with
+the kernels that lie between them and not with the kernel's code.
 Exit status 0 = nothing differs and no kernel exists only in the second build."""
 import collections
 import os
@@ -15,7 +20,7 @@ import sys
 import tempfile
 
 LLVM = os.environ.get('LLVM_BIN', '/opt/rocm/lib/llvm/bin')
-SRC = ['bfd_api', 'bfd_placement', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte']
+SRC = ['bfd_api', 'bfd_outputs', 'bfd_placement', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte', 'bfd_median']
 
 
 def kernels(obj, tmp):
@@ -31,7 +36,10 @@ def kernels(obj, tmp):
         if m:
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line.strip() and line.strip() != '...':      # '...': objdump's mark for the zero padding behind a kernel
-            cur.append(re.sub(r'\s*//.*$', '', line).strip())
+            ins = re.sub(r'\s*//.*$', '', line).strip()
+            if cur and cur[-1].startswith('s_getpc_b64'):      # the low word of a pc-relative address: where the object's data lies from here, not code
+                ins = re.sub(r'^(s_add_u32 \S+ \S+) 0x[0-9a-f]+$', r'\1 <pc-relative>', ins)
+            cur.append(ins)
     return out
 
 
@@ -60,13 +68,17 @@ def resources(log):
 
 def main():
     dirA, logA, dirB, logB = sys.argv[1:5]
+    moved = dict(a.split('=') for a in sys.argv[5:])
     with tempfile.TemporaryDirectory() as tmp:
         A, B = {}, {}
         for s in SRC:
             for d, K in ((dirA, A), (dirB, B)):
                 for name, ins in kernels(os.path.join(d, s + '.o'), tmp).items():
-                    K[(s, name)] = ins
-    RA, RB = resources(logA), resources(logB)
+                    key = (moved.get(s, s) if K is B else s, name)
+                    assert key not in K, 'kernel in two objects of one build (a copy): %s %s' % key
+                    K[key] = ins
+    RA = resources(logA)
+    RB = {(moved.get(f[:-4], f[:-4]) + '.hip', name): v for (f, name), v in resources(logB).items()}
     onlyA, onlyB = sorted(set(A) - set(B)), sorted(set(B) - set(A))
     print('code symbols: first build %d, second build %d, in both %d' % (len(A), len(B), len(set(A) & set(B))))
     print('instructions compared: %d' % sum(len(A[k]) for k in set(A) & set(B)))

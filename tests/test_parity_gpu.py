@@ -536,7 +536,7 @@ def test_cost_balanced_run_maps_do_not_change_results(monkeypatch):
 
 def test_large_result_blocks_through_threads_equal_the_plain_copy(monkeypatch):
     """Sensor series and maps of 256 MB and more leave the device through several host threads with pinned pieces of their own
-    (copy_out_large, bfd_api.hip). Here the same code on a small grid (thresholds lowered): every output equal to the one-copy path,
+    (copy_out_large, bfd_outputs.hip). Here the same code on a small grid (thresholds lowered): every output equal to the one-copy path,
     for an even and an odd number of threads, single engine and two slabs (row pitch)."""
     a, k, info = H.make_problem('C2', N=(192, 160, 160), steps=80, stable_dt_fn=oracle_dt)
     k['SelMapsRMSPeakList'] = ['Pressure', 'Vz', 'Sigmaxy']
