@@ -1,10 +1,11 @@
 """On-device single-bin DFT of the sensor block against (1) the golden output of the
 reference's own CalculatePhaseData (BASE:2460-2560, captured by tests/golden/make_golden.py) and
-(2) numpy's FFT of the series the engine itself returns."""
+(2) the float64 direct sum of the series the engine itself returns, sensor by sensor within the bound of tests/dft_reference.py."""
 import numpy as np
 import pytest
 
 from babelbrain_amd import harness as H
+from tests.dft_reference import assert_dft
 from tests.util import oracle_dt, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +16,9 @@ def test_dft_matches_reference_calculate_phase_data(golden):
     g, _ = golden
     N1, N2, N3, ppp, sub, f, dts = g['phase_args']
     F, pk = _engine.dft_series(g['phase_series'], dts, f)
+    assert_dft(F, pk, g['phase_series'], float(dts), float(f), 'dft_series of the golden series', (g['phase_index'], (int(N1), int(N2), int(N3))))
     four, phase, peak = H.phase_maps(F, pk, g['phase_index'], int(N1), int(N2), int(N3))
+    # the golden Fourier map is itself a float32-rounded FFT: its own tolerance stays a norm
     assert rel_l2(four.real, g['phase_fourier'].real) < 1e-6 and rel_l2(four.imag, g['phase_fourier'].imag) < 1e-6
     assert np.array_equal(peak, g['phase_peak'])
 
@@ -28,14 +31,12 @@ def test_engine_sensor_dft_matches_host_fft():
     S, Inp = out[0], out[-1]
     nTs = S['time'].size
     assert nTs == 2 * info['ppp'] // k['SensorSubSampling']
-    freqs = np.fft.fftfreq(nTs, np.diff(S['time']).mean())
-    ind = np.argmin(np.abs(freqs - info['freq']))
     for name in ('Pressure', 'Vz'):
-        ref = np.fft.fft(S[name].astype(np.float64), axis=1)[:, ind] * 2 / nTs
         got = Inp['SensorDFT'][name]
-        assert np.abs(ref).max() > 0
-        assert rel_l2(got.real, ref.real) < 1e-6 and rel_l2(got.imag, ref.imag) < 1e-6
-        assert np.array_equal(Inp['SensorPeak'][name], S[name].max(axis=1))
+        assert np.abs(got).max() > 0
+        worst = assert_dft(got, Inp['SensorPeak'][name], S[name], k['DT'] * k['SensorSubSampling'], info['freq'], 'SensorDFT[%s]' % name,
+                           (Inp['IndexSensorMap'], a[0].shape))
+        print('%s: largest ratio to the bound %.4f' % (name, worst))
 
 
 def test_in_loop_accumulation_equals_dft_of_stored_series():
