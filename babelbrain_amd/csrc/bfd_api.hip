@@ -419,6 +419,10 @@ hipError_t select_flagged(uint8_t *flags, uint32_t *sel, int *dcount, int n, hip
 
 // inputs changed: the run lists, the activity map and a recorded step graph are out of date, and (classes: materials, map, reflector) the cell classes
 static void invalidate_lists(bfd_sim *s, bool classes = true) { s->tilesReady = false; if (classes) s->classesReady = false; s->actReady = false; drop_step_graph(s); }
+// Advanced Vz: between the stress and the velocity half-step of a time step the runs that carry BFD_RUN_ADV_VZ hold the new Vz at their inner planes
+// and the old one elsewhere; only the velocity half-step over the SAME lists completes it. What would rebuild the lists waits for the step to end.
+static bool lists_held_mid_step(const bfd_sim *s) { return s->midStep && s->tilesReady && s->tiles.advVz; }
+#define BFD_REFUSE_MID_STEP(who) do { if (lists_held_mid_step(s)) BFD_FAIL(-6, who ": a stress half-step is outstanding: finish the time step first"); } while (0)
 
 static int pressure_slot(const bfd_sim *s)
 {
@@ -549,6 +553,8 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     s->acc = s->pk = nullptr; s->timing = s->perKernel = false;
     s->pairEnv = true; s->pendingAcc = s->pairDone = false; s->pairedLaunches = 0;
     if (const char *ev = getenv("BFD_PAIR_ACC")) s->pairEnv = atoi(ev) != 0;      // 0: every step accumulates in the velocity kernels (A/B, tests)
+    s->advEnv = true; s->midStep = false; s->tiles.advVz = false;
+    if (const char *ev = getenv("BFD_ADV_VZ")) s->advEnv = atoi(ev) != 0;         // 0: velocity_fluid updates Vz of every plane (A/B, tests)
     s->tables = nullptr; s->profiles = nullptr; s->cmax = 0;
     memset(s->algBytes, 0, sizeof s->algBytes); s->tiles.ktimer = nullptr;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; BFD_FAIL(-10, "hipStreamCreate failed"); }
@@ -660,6 +666,7 @@ int bfd_use_private_stream(bfd_sim *s)
 int bfd_set_materials(bfd_sim *s, const double *matlist, const double *qcorr)
 {
     if (!s || !matlist) BFD_FAIL(-1, "bfd_set_materials: null argument");
+    BFD_REFUSE_MID_STEP("bfd_set_materials");
     BFD_HIP(hipSetDevice(s->cfg.device));
     { const int rc = flush_pending(s); if (rc) return rc; }      // inputs set again in the middle of a run: the maps take the outstanding Pressure first
     const bfd_config &c = s->cfg;
@@ -701,6 +708,7 @@ int bfd_set_material_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2
 {
     if (!s || !map) BFD_FAIL(-1, "bfd_set_material_map: null argument");
     if (ghostLow < 0 || ghostLow > 2 || ghostHigh < 0 || ghostHigh > 2) BFD_FAIL(-2, "ghost plane counts must be 0..2");
+    BFD_REFUSE_MID_STEP("bfd_set_material_map");
     BFD_HIP(hipSetDevice(s->cfg.device));
     { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
@@ -733,6 +741,7 @@ int bfd_set_reflector(bfd_sim *s, const uint32_t *mask, int64_t s1, int64_t s2, 
 {
     if (!s) BFD_FAIL(-1, "null sim");
     if (!s->haveMap) BFD_FAIL(-6, "bfd_set_reflector: set the material map first");
+    BFD_REFUSE_MID_STEP("bfd_set_reflector");
     BFD_HIP(hipSetDevice(s->cfg.device));
     { const int rc = flush_pending(s); if (rc) return rc; }
     const bfd_dev &d = s->d;
@@ -800,6 +809,7 @@ int bfd_set_sources(bfd_sim *s, int64_t nVox, const uint32_t *localIndex, const 
     if (!s) BFD_FAIL(-1, "null sim");
     if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !pulse))) BFD_FAIL(-1, "bfd_set_sources: null argument");
     if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources: bad PulseSource shape");
+    BFD_REFUSE_MID_STEP("bfd_set_sources");
     { const int rc = flush_pending(s); if (rc) return rc; }
     int rc = set_source_voxels(s, "bfd_set_sources", nVox, localIndex, row, wx, wy, wz, nSources, lengthSource);
     if (rc || nVox == 0) return rc;
@@ -845,6 +855,7 @@ int bfd_set_sources_separable(bfd_sim *s, int64_t nVox, const uint32_t *localInd
 {
     if (!s) BFD_FAIL(-1, "null sim");
     if (K < 1 || K > 4) BFD_FAIL(-2, "bfd_set_sources_separable: K must be 1..4");
+    BFD_REFUSE_MID_STEP("bfd_set_sources_separable");
     { const int rc = flush_pending(s); if (rc) return rc; }
     if (nVox < 0 || (nVox > 0 && (!localIndex || !row || !weights || !signals))) BFD_FAIL(-1, "bfd_set_sources_separable: null argument");
     if (nSources < 0 || lengthSource < 0) BFD_FAIL(-2, "bfd_set_sources_separable: bad weights / signals shape");
@@ -884,6 +895,7 @@ static void bind_compact_views(bfd_sim *s)
 }
 static bool quiet_runs_wanted(const bfd_sim *s);
 static bool pair_engine(const bfd_sim *s, bool quiet, int nFluid);
+static bool adv_vz_engine(const bfd_sim *s, int nSolid);
 
 // The tile grid of one build: tx x ty columns of nsub sub-tiles (n in all) of SUB planes; a z-chunk, the longest run, is perChunk sub-tiles.
 // "boundary" sub-tiles hold the 2 first / 2 last planes of the slab (what a Z-neighbour reads): they form the
@@ -1290,6 +1302,12 @@ static int account_algorithmic_bytes(bfd_sim *s, int tx, const std::vector<int4>
             // Pressure sum read and written: by velocity_fluid in every accumulating step, or (paired accumulation) by stress_fluid in
             // every second one: 4 B per launch averaged over a step pair
             if (pairAcc) B[1][BFD_K_STRESS_FLUID] += 4.0 * inner; else B[1][BFD_K_VELOCITY_FLUID] += 8.0 * inner;
+            // advanced Vz: planes kbeg+1 .. kend-3 of the run get their new Vz from stress_fluid (a write; the read is in its 12 B of V already)
+            // and velocity_fluid neither reads nor writes it there
+            if (f & BFD_RUN_ADV_VZ) {
+                const double advCells = (double)(xb - xa) * (yb - ya) * std::max(0, ke - kb - 3);
+                for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_FLUID] += 4.0 * advCells; B[a][BFD_K_VELOCITY_FLUID] -= 8.0 * advCells; }
+            }
         } else if (s->cfg.kernelVariant == 2) {     // dense: V + 6 S + 6 R read, 6 S + 6 R written, id; 6 S + V read, V written, id
             for (int a = 0; a < 2; a++) { B[a][BFD_K_STRESS_SOLID] += 110.0 * cells; B[a][BFD_K_VELOCITY_SOLID] += 50.0 * cells + (a ? 8.0 * inner : 0.0); }
         } else {                                    // class-predicated solid kernels: per-cell terms come from the class counts below
@@ -1370,6 +1388,11 @@ static int build_tile_lists(bfd_sim *s)
     T.nFluidB = (int)lists[0].size(); T.nFluid = T.nFluidB + (int)lists[1].size();
     T.nSolidB = (int)lists[2].size(); T.nSolid = T.nSolidB + (int)lists[3].size();
     T.nFused = (int)lists[4].size();
+    T.advVz = false;
+    if (adv_vz_engine(s, T.nSolid))
+        for (int a = 0; a < 2; a++)
+            for (int4 &run : lists[a])
+                if (!(run.z & (1 | 8)) && (run.y >> 16) - (run.y & 0xFFFF) >= 4) { run.z |= BFD_RUN_ADV_VZ; T.advVz = true; }
     std::vector<int4> all;
     for (int a = 0; a < 5; a++) all.insert(all.end(), lists[a].begin(), lists[a].end());
     int rc = dev_alloc(s, &s->tiles.runs, all.size(), false);
@@ -1399,6 +1422,22 @@ static int build_tile_lists(bfd_sim *s)
     if (oldCells) dev_release(s, &oldCells);
     s->tilesReady = true;
     return 0;
+}
+
+// ---- advanced Vz -----------------------------------------------------------------------------------------------------------
+// velocity_fluid reads and writes Vz (8 B per cell), yet its Vz update needs only the column's new Szz, which stress_fluid produces plane by plane
+// while it holds the column's Vz in its z-queue. In a plain fluid run outside the absorbing layer stress_fluid therefore stores the new Vz of
+// the planes whose stencil lies inside the run (kbeg+1 .. kend-3; the range proof is at stress_fluid_body) and velocity_fluid skips Vz there:
+// + 4 B and - 8 B per advanced cell. The same expression in the same order (-ffp-contract=off): bit-identical. BFD_ADV_VZ=0 switches it off.
+// ONE bit in the run record (BFD_RUN_ADV_VZ), set here when the lists are built, tells both kernels; they cannot disagree. An engine qualifies with
+// the class-specialised kernels (variants 0 / 3) updating V in place, velocity-type sources (a stress-type source changes Szz between the two
+// kernels), no solid run (velocity_solid and the sparse kernel read their fluid neighbours' Vz) and no quiet runs (those flavours ignore the bit).
+// Z-slabs qualify: the planes a neighbour's stress half-step reads are a slab's first and last two, never inner planes of a run.
+// Between the two half-steps of a step Vz is of mixed time level (bfd_sim::midStep): the setters that would rebuild the lists refuse until the step ends.
+static bool adv_vz_engine(const bfd_sim *s, int nSolid)          // run lists just formed
+{
+    return s->advEnv && (s->cfg.kernelVariant == 0 || s->cfg.kernelVariant == 3) && !s->pingpong && s->d.VzW == s->d.Vz &&
+           s->cfg.typeSource < 2 && nSolid == 0 && !quiet_runs_wanted(s);
 }
 
 // Quiet runs (bfd_dev::act; bfd_kernels_v2.hip): a production call lets the runs ahead of the wave front return at entry. On when the
@@ -1574,6 +1613,7 @@ static int stress_part(bfd_sim *s, int part, hipStream_t st)
             s->pendingAcc = false; s->pairDone = true;
         }
         bfd_launch_stress_v2(s->d, st, &s->tiles, part, accP, pkP);
+        s->midStep = true;
     }
     if (e0) { hipEventRecord(e1, st); s->evStress.push_back(e0); s->evStress.push_back(e1); }
     if (s->nSrcVox && s->cfg.typeSource >= 2 && s->step < s->lengthSource) { rc = inject_part(s, part, new_stress_view(s->d), st); if (rc) return rc; }
@@ -1617,6 +1657,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
     BFD_HIP(hipGetLastError());
     if (paired) { s->pendingAcc = !s->pairDone; s->pairDone = false; }      // first step of a pair: the maps lack it; second: settled in its stress half-step
     s->step++;
+    s->midStep = false;
     s->stepDevValid = false;
     return 0;
 }
@@ -1847,6 +1888,7 @@ int bfd_reset(bfd_sim *s)
     { const int rc = bfd_clear_outputs(s); if (rc) return rc; }
     s->step = 0; s->stepDevValid = false; s->actReady = false;         // the activity map starts over with the state
     s->pendingAcc = s->pairDone = false;                               // the maps were cleared: nothing is outstanding
+    s->midStep = false;
     BFD_HIP(hipStreamSynchronize(s->stream));
     drain_pack_jobs(s);
     for (int b = 0; b < 2; b++) s->tileLoaded[b] = -1;        // the streamed source table starts over (tiles are re-packed on demand)

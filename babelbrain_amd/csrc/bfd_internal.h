@@ -109,6 +109,9 @@ static __device__ __forceinline__ long css_index(const bfd_dev &d, long c)
 // runs [fluid boundary | fluid interior | solid boundary | solid interior] (boundary = inside the first/last
 // 32 planes); run = (bx + tilesX*by, kbeg | kend<<16, flags: bit0 solid, bit1 lossy, bit2 UNI, bit3 PML, bit4 LEAN, material
 // id of UNI runs). n* counters after nSolidB are in 64x8x8 sub-tiles, for reporting.
+// BFD_RUN_ADV_VZ in the flags of a run: stress_fluid stores the new Vz of the run's planes kbeg+1 .. kend-3 and velocity_fluid leaves Vz alone there
+// (bfd_api.hip, "advanced Vz"); both kernels read the same record. bfd_tiles::advVz = some run of the current lists carries it.
+#define BFD_RUN_ADV_VZ 512
 // kernel classes of the per-kernel timing / byte accounting (bfd_timing_kernels, bfd_algorithmic_bytes)
 enum { BFD_K_STRESS_FLUID = 0, BFD_K_STRESS_SOLID = 1, BFD_K_STRESS_SHEAR = 2, BFD_K_VELOCITY_FLUID = 3, BFD_K_VELOCITY_SOLID = 4,
        BFD_K_FUSED = 5, BFD_K_COUNT = 6 };
@@ -131,6 +134,7 @@ struct bfd_tiles { bfd_sim *ktimer; int nMat; int4 *runs;
                    float *shearR;   /* full-volume solid state (BFD_COMPACT_SOLID=0) only: memory variables Rxy, Rxz, Ryz of the listed cells, [3][nShear] in list order, beside the list (dense, coalesced); the full-volume arrays are filled from here on demand (bfd_get_field). Null when the state is compact */
                    int nFluid, nFluidB, nSolid, nSolidB, nSolidBP /* leading boundary runs that touch the absorbing layer */, nSolidIP /* trailing interior ones */, nFused /* runs of the fused kernel, after the solid runs */;
                    int nLossless, nLossy, nSolidSub, nUni, nPml, nLean, nFusedSub;
+                   bool advVz;
                    /* cost-balanced block -> run maps (round 4): block b of a launch runs on XCD slot b & 7 and takes run seg[slot] + (b >> 3) of
                       the launched range if that is below seg[slot + 1]; the launch has 8 x maxcnt blocks. One map of 10 ints (seg[0..8], maxcnt)
                       per launched range and kernel class, on the device in xmap, on the host in xmapH. */
@@ -187,6 +191,10 @@ struct bfd_sim {
     // pairDone = the stress half-step of the current step took the pairing flavour (the maps hold this step already; cleared where the step counter
     // advances); pairedLaunches counts the launches of the pairing stress flavour (bfd_paired_launches)
     bool pairEnv, pendingAcc, pairDone; int64_t pairedLaunches;
+    // Advanced Vz (bfd_api.hip, "advanced Vz"): advEnv = BFD_ADV_VZ is not 0; midStep = a stress half-step of the current step has been queued and its
+    // velocity half-step has not ended (cleared where the step counter advances and in bfd_reset): Vz is then of mixed time level in the runs that
+    // carry BFD_RUN_ADV_VZ, and the run lists must stay as they are
+    bool advEnv, midStep;
     // timing
     bool timing, perKernel;
     hipEvent_t evBegin, evEnd;

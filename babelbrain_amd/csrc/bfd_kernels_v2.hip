@@ -524,10 +524,19 @@ __device__ __forceinline__ unsigned fbits(float v) { return __float_as_uint(v); 
 // sources never touch Szz) and the new one that of this step, so ONE read-modify-write of the running sum here, in every second accumulating step, adds
 // both squares in the order the velocity kernel adds them, (acc + p_old^2) + p_new^2, and velocity_fluid leaves the sum alone (bfd_api.hip, "paired
 // accumulation"). The sum runs one plane ahead like the other streams; the peak is read where it is used, as in velocity_fluid_body.
+// advVz (runs that carry BFD_RUN_ADV_VZ: plain fluid runs outside the absorbing layer, not QUIET; bfd_api.hip, "advanced Vz"): the Vz update of
+// velocity_fluid_body needs nothing from the x/y neighbours, only the column's NEW Szz of planes p-1 .. p+2, and this kernel holds the column's Vz in
+// its z-queue. So it keeps its last three new Szz (and two ids) and stores the new Vz of plane p = kl-2 at iteration kl, after dzVz has used the old
+// one: the very expression of velocity_fluid_body, which then neither loads nor stores Vz at those planes.
+// Which planes: iteration kl of a run reads Vz(kl-2 .. kl+1), all loaded at least one iteration before the store to kl-2; the run below reads up to
+// my kbeg, the run above down to my kend-2, x/y neighbours never read Vz; and the new Szz of p-1 .. p+2 must all be this run's. Hence exactly
+// p in [kbeg+1, kend-3]; a run shorter than 4 planes advances nothing.
 template <bool LOSSY, bool COLLAPSED, bool UNI, bool PML, bool SOLID = false, bool QUIET = false, bool PAIR = false>
 __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int by, int kbeg, int kend, int tm,
-                                                  float (*sV)[2][LH * LW], float *__restrict__ accP = nullptr, float *__restrict__ pkP = nullptr)
+                                                  float (*sV)[2][LH * LW], float *__restrict__ accP = nullptr, float *__restrict__ pkP = nullptr,
+                                                  bool advVz = false)
 {
+    constexpr bool ADVZ = !PML && !SOLID && !QUIET;
     static_assert(!PAIR || (!SOLID && !QUIET), "paired accumulation: plain fluid flavours only");
     unsigned nzb = 0u;          // QUIET: bits of everything stored
     // The three normal stresses are identical in a FLUID tile; Szz is the one that is read (it is
@@ -583,6 +592,10 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
         if (!UNI) mraw = U2((d.mat + kbeg * pl), cij * 2u);
     }
     float hv = t.ok ? F4(ph + kbeg * pl, hofs) : 0.0f;
+    // advanced Vz: new Szz of planes kl-1, kl-2, kl-3 and the ids of planes kl-1, kl-2
+    float sq1 = 0, sq2 = 0, sq3 = 0, ruv = 0;
+    unsigned mq1 = 0, mq2 = 0;
+    if (ADVZ && UNI) ruv = d.invRho[tm];
 
     for (int kl = kbeg; kl < kend; kl++) {
         const int b = kl & 1;
@@ -595,7 +608,7 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
         if (!UNI && valid) { const int m = mraw & BFD_MAT_MASK; AP = d.AP[m]; if (LOSSY) BP = d.BP[m]; if (SOLID) { AS2 = d.AS2[m]; BS2 = d.BS2[m]; } }
         __syncthreads();
 
-        float nvx = 0, nvy = 0, nvz = 0, nh = 0, nszz = 0, nrzz = 0, npx = 0, npy = 0, npz = 0, nav = 0;
+        float nvx = 0, nvy = 0, nvz = 0, nh = 0, nszz = 0, nrzz = 0, npx = 0, npy = 0, npz = 0, nav = 0, nsq = 0;
         unsigned nmraw = 0;
         if (kl + 1 < kend) {
             if (valid) {
@@ -664,7 +677,19 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
                 ST4((d.RzzW + ko), cij * 4u, rn);
                 if (!COLLAPSED) { F4((d.Rxx + ko), cij * 4u) = rn; F4((d.Ryy + ko), cij * 4u) = rn; }
             }
+            if (ADVZ) {
+                nsq = val;
+                if (advVz && kl >= kbeg + 3) {      // plane p = kl-2 in [kbeg+1, kend-3]: vzm2 is its old Vz, dzVz above was its last reader
+                    float r0 = ruv, r1 = ruv;
+                    if (!UNI) { r0 = d.invRho[mq2 & BFD_MAT_MASK]; r1 = d.invRho[mq1 & BFD_MAT_MASK]; }
+                    const float dz = dplus4(sq3, sq2, sq1, val);
+                    float w = vzm2 + (0.5f * (r0 + r1)) * dz;
+                    if (!UNI && (mq2 & BFD_REFLECTOR_BIT)) w = 0.f;
+                    ST4((d.VzW + ko - 2 * pl), cij * 4u, w);
+                }
+            }
         }
+        if (ADVZ) { sq3 = sq2; sq2 = sq1; sq1 = nsq; mq2 = mq1; mq1 = mraw; }
         vx0 = nvx; vy0 = nvy;
         vzm2 = vzm1; vzm1 = vz0; vz0 = vzp1; vzp1 = nvz;
         hv = nh; szz = nszz; rzz = nrzz; mraw = nmraw; av = nav;
@@ -673,10 +698,13 @@ __device__ __forceinline__ void stress_fluid_body(const bfd_dev &d, int bx, int 
     if (QUIET) run_mark_active(d, bx, by, kbeg, kend, nzb);
 }
 
+// advVz: the run carries BFD_RUN_ADV_VZ, so stress_fluid_body has already stored the new Vz of planes kbeg+1 .. kend-3 (see there): at those planes Vz
+// is neither loaded nor stored here (a block-uniform predicate per plane); Vx, Vy, the accumulation and the reflector's zeros of Vx / Vy are as ever.
 template <bool ACC, bool UNI, bool PML, bool QUIET = false>
 __device__ __forceinline__ void velocity_fluid_body(const bfd_dev &d, int bx, int by, int kbeg, int kend, int tm,
-                                                    float (*sS)[LH * LW], float *__restrict__ accP, float *__restrict__ pkP)
+                                                    float (*sS)[LH * LW], float *__restrict__ accP, float *__restrict__ pkP, bool advVz = false)
 {
+    const bool adv = !PML && !QUIET && advVz;
     const int N1 = d.N1, N2 = d.N2;
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TX + tx;
     const int i0 = bx * TX, j0 = by * TY;
@@ -753,7 +781,8 @@ __device__ __forceinline__ void velocity_fluid_body(const bfd_dev &d, int bx, in
         if (kl + 1 < kend) {
             if (valid) {
                 ns = F4((d.Szz + ko + 3 * pl), cij * 4u);
-                nvx = LD4((d.Vx + ko + pl), cij * 4u); nvy = LD4((d.Vy + ko + pl), cij * 4u); nvz = LD4((d.Vz + ko + pl), cij * 4u);
+                nvx = LD4((d.Vx + ko + pl), cij * 4u); nvy = LD4((d.Vy + ko + pl), cij * 4u);
+                if (!(adv && kl + 1 < kend - 2)) nvz = LD4((d.Vz + ko + pl), cij * 4u);      // plane kl+1 > kbeg: advanced unless one of the run's last two
                 if (!UNI) { nmx = U2((d.mat + ko + pl), cx * 2u); nmy = U2((d.mat + ko + pl), cy * 2u); }
                 if (accA) nav = LD4((accP + ko + pl), cij * 4u);
             }
@@ -765,6 +794,7 @@ __device__ __forceinline__ void velocity_fluid_body(const bfd_dev &d, int bx, in
                 if (valid && (kn < P || kn >= d.N3 - P)) npz = F4(d.psi[17], (unsigned)((long)(kn < P ? kn : kn - (d.N3 - 2 * P)) * pl + cij) * 4u);
             }
         }
+        const bool ownVz = !(adv && kl > kbeg && kl < kend - 2);      // false: stress_fluid_body has stored this plane's new Vz
         if (valid) {
             if (ACC) {
                 if (inner && k >= d.ND && k < d.N3 - d.ND) {
@@ -776,7 +806,8 @@ __device__ __forceinline__ void velocity_fluid_body(const bfd_dev &d, int bx, in
                 }
             }
             if (!UNI && (mraw & BFD_REFLECTOR_BIT)) {
-                F4((d.VxW + ko), cij * 4u) = 0.f; F4((d.VyW + ko), cij * 4u) = 0.f; F4((d.VzW + ko), cij * 4u) = 0.f;
+                F4((d.VxW + ko), cij * 4u) = 0.f; F4((d.VyW + ko), cij * 4u) = 0.f;
+                if (ownVz) F4((d.VzW + ko), cij * 4u) = 0.f;
             } else {
                 const float *p = &sS[b][own];
                 float dx = dplus4(p[-1], s0, p[1], p[2]);
@@ -794,7 +825,7 @@ __device__ __forceinline__ void velocity_fluid_body(const bfd_dev &d, int bx, in
                 if (!QUIET) {
                     ST4((d.VxW + ko), cij * 4u, vx + (0.5f * (r0 + rx)) * dx);
                     ST4((d.VyW + ko), cij * 4u, vy + (0.5f * (r0 + ry)) * dy);
-                    ST4((d.VzW + ko), cij * 4u, vz + (0.5f * (r0 + r1)) * dz);
+                    if (ownVz) ST4((d.VzW + ko), cij * 4u, vz + (0.5f * (r0 + r1)) * dz);
                 } else {
                     { const float w = vx + (0.5f * (r0 + rx)) * dx; ST4((d.VxW + ko), cij * 4u, w); nzb |= fbits(w); }
                     { const float w = vy + (0.5f * (r0 + ry)) * dy; ST4((d.VyW + ko), cij * 4u, w); nzb |= fbits(w); }
@@ -1683,12 +1714,13 @@ __global__ void shear_material_table(bfd_dev d, float *__restrict__ tab, int nMa
 
 // ---- dispatchers: one launch for all fluid runs; block-uniform switch on the run's flags ----
 // run = (x: bx + tilesX*by, y: kbeg | kend<<16, z: flags, w: material id of UNI runs)
-// flags: bit0 solid, bit1 lossy, bit2 UNI, bit3 PML, bit4 LEAN
+// flags: bit0 solid, bit1 lossy, bit2 UNI, bit3 PML, bit4 LEAN, BFD_RUN_ADV_VZ (bfd_internal.h)
 template <bool COLLAPSED, bool QUIET = false, bool PAIR = false>
 __device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4 &run, int tilesX, float (*sV)[2][LH * LW],
                                                     float *__restrict__ accP = nullptr, float *__restrict__ pkP = nullptr)
 {
     const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16, tm = run.w;
+    const bool adv = (run.z & BFD_RUN_ADV_VZ) != 0;
     if (QUIET && run_all_quiet(d, bx, by, kbeg, kend)) return;
     if (run.z & 1) {          // a solid run in the fluid launch (compact solid state): memory variables, several materials
         if (run.z & 8) stress_fluid_body<true, true, false, true, true, QUIET>(d, bx, by, kbeg, kend, tm, sV);
@@ -1696,10 +1728,10 @@ __device__ __forceinline__ void stress_fluid_switch(const bfd_dev &d, const int4
         return;
     }
     switch ((run.z >> 1) & 7) {
-    case 0: stress_fluid_body<false, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
-    case 1: stress_fluid_body<true, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
-    case 2: stress_fluid_body<false, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
-    case 3: stress_fluid_body<true, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
+    case 0: stress_fluid_body<false, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP, adv); break;
+    case 1: stress_fluid_body<true, COLLAPSED, false, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP, adv); break;
+    case 2: stress_fluid_body<false, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP, adv); break;
+    case 3: stress_fluid_body<true, COLLAPSED, true, false, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP, adv); break;
     case 4: stress_fluid_body<false, COLLAPSED, false, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
     case 5: stress_fluid_body<true, COLLAPSED, false, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
     case 6: stress_fluid_body<false, COLLAPSED, true, true, false, QUIET, PAIR>(d, bx, by, kbeg, kend, tm, sV, accP, pkP); break;
@@ -1755,10 +1787,11 @@ __global__ __launch_bounds__(NTHREADS, VELOCITY_FLUID_WAVES_PER_SIMD) void veloc
     if (ri < 0) return;
     const int4 run = runs[ri];
     const int bx = run.x % tilesX, by = run.x / tilesX, kbeg = run.y & 0xFFFF, kend = run.y >> 16, tm = run.w;
+    const bool adv = (run.z & BFD_RUN_ADV_VZ) != 0;
     if (QUIET && run_all_quiet(d, bx, by, kbeg, kend)) return;
     switch ((run.z >> 2) & 3) {
-    case 0: velocity_fluid_body<ACC, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
-    case 1: velocity_fluid_body<ACC, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
+    case 0: velocity_fluid_body<ACC, false, false, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP, adv); break;
+    case 1: velocity_fluid_body<ACC, true, false, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP, adv); break;
     case 2: velocity_fluid_body<ACC, false, true, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
     default: velocity_fluid_body<ACC, true, true, QUIET>(d, bx, by, kbeg, kend, tm, sS, accP, pkP); break;
     }

@@ -293,7 +293,7 @@ int classify(Probe &P, const Levels &L, Classes &C)
 
 // stream order: arrays that a kernel WRITES together are neighbours in this list, and the list alternates between the
 // most populated region M and "anywhere else":
-//   velocity kernels write Vx Vy Vz (+ accumulator); stress_fluid Szz Rzz; stress_solid Sxx Syy Szz Rxx Ryy Rzz;
+//   velocity kernels write Vx Vy Vz (+ accumulator); stress_fluid Szz Rzz (+ Vz of the advancing runs, which already lies apart from Szz); stress_solid Sxx Syy Szz Rxx Ryy Rzz;
 //   the sparse shear kernel Sxy Sxz Syz Rxy Rxz Ryz
 Order stream_order(bool pingpong, bool solids)
 {

@@ -215,7 +215,8 @@ int bfd_timing_kernels(bfd_sim *sim, double *msPerClass, int64_t *launchesPerCla
  * layer memory variables, coefficient tables and halo re-reads excluded). accumulating != 0 adds the
  * Pressure RMS accumulator (8 B per cell outside the absorbing layer) to the velocity classes; where the accumulation of the
  * fluid runs is paired (bfd_paired_launches) it is 4 B per launch of the fluid stress class instead: the average over a step
- * pair. DESIGN.md section 6. */
+ * pair. Where Vz is advanced (below) the fluid stress class moves 4 B more and the fluid velocity class 8 B less per advanced
+ * cell, with or without accumulation. DESIGN.md section 6. */
 int bfd_algorithmic_bytes(bfd_sim *sim, int32_t accumulating, double *bytesPerClass);
 /* Paired Pressure accumulation (all-fluid runs, velocity-type sources, rmsFirstStep >= 1 or quiet runs off): accumulating steps go in
  * pairs, the stress half-step of the second adds the Pressure of both to the RMS / peak maps; bfd_get_map, bfd_reset and the
@@ -224,6 +225,12 @@ int bfd_algorithmic_bytes(bfd_sim *sim, int32_t accumulating, double *bytesPerCl
  * otherwise they hold the steps before it, as without pairing); after bfd_half_step_velocity they are the same either way.
  * Returns the number of launches of the pairing stress flavour so far (0: every step accumulated in the velocity kernels). */
 int64_t bfd_paired_launches(bfd_sim *sim);
+/* Advanced Vz (no entry point of its own): in an engine of the class-specialised kernels (variants 0 / 3, in-place update) with velocity-type
+ * sources, no solid run and no quiet runs (rmsFirstStep >= 1 or BFD_SKIP_ZERO=0), the stress half-step also stores the new Vz of the inner planes
+ * of every fluid run outside the absorbing layer and the velocity half-step leaves Vz alone there; results are bit-identical, BFD_ADV_VZ=0
+ * switches it off. The two half-steps of a time step are then one unit: between them bfd_set_materials, bfd_set_material_map,
+ * bfd_set_reflector, bfd_set_sources and bfd_set_sources_separable return -6 ("finish the time step first") and change nothing;
+ * bfd_set_sensor_map and the getters stay available (see bfd_get_field for "Vz"). */
 /* back to step 0: fields, absorbing-layer memory, accumulators and the sensor block zeroed; inputs are kept */
 int bfd_reset(bfd_sim *sim);
 
@@ -249,7 +256,9 @@ int bfd_dft_series(int32_t device, int64_t nSensors, int32_t nTs, const float *s
                    float *outReIm, float *outPeak);
 /* one accumulated volume of this slab into a strided (N1,N2,nk) float32 view */
 int bfd_get_map(bfd_sim *sim, int32_t kind, int32_t map, float *out, int64_t s1, int64_t s2, int64_t s3);
-/* raw state array a (0..14: Vx Vy Vz Sxx Syy Szz Sxy Sxz Syz Rxx Ryy Rzz Rxy Rxz Ryz), for tests */
+/* raw state array a (0..14: Vx Vy Vz Sxx Syy Szz Sxy Sxz Syz Rxx Ryy Rzz Rxy Rxz Ryz), for tests.
+ * Between bfd_half_step_stress* and the matching velocity half-step, "Vz" (a = 2) is of mixed time level where Vz is advanced (below):
+ * the inner planes of the advancing runs hold the new Vz already, every other cell the old one; after the velocity half-step it is the new Vz everywhere. */
 int bfd_get_field(bfd_sim *sim, int32_t a, float *out, int64_t s1, int64_t s2, int64_t s3);
 /* number of 64x8x8-voxel sub-tiles per class of the class-specialised kernels (variant 0/3):
  * lossless fluid, lossy fluid, solid, and among the fluid ones how many hold one material only (UNI)
