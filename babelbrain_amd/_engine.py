@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     'bfd_group_set_reflector', 'bfd_group_set_sources', 'bfd_group_set_sources_separable', 'bfd_group_set_sensor_map', 'bfd_group_prepare', 'bfd_group_run', 'bfd_group_sync',
     'bfd_group_reset', 'bfd_group_timing_begin', 'bfd_group_timing_end', 'bfd_group_num_sensors', 'bfd_group_num_sensor_steps',
     'bfd_group_get_sensor_index', 'bfd_group_get_sensors', 'bfd_group_get_sensor_dft', 'bfd_group_get_map', 'bfd_group_device_bytes',
-    'bfd_group_peer_status', 'bfd_placement_cache_release', 'bfd_median_filter3d',
+    'bfd_group_peer_status', 'bfd_placement_cache_release', 'bfd_median_filter3d', 'bfd_binary_morphology3d', 'bfd_label3d',
 ]
 
 
@@ -195,6 +195,10 @@ def load_library():
     lib.bfd_group_peer_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.bfd_median_filter3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_float)]
+    lib.bfd_binary_morphology3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    lib.bfd_label3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_void_p,
+                                C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

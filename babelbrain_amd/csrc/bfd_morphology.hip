@@ -1,0 +1,442 @@
+// Binary morphology and component labelling of Step-1 masks on MI355X, in the caller's numpy C order (k fastest).
+//
+// Replaces, after the median of BabelDatasetPreps.py:870-876,
+//     BinaryClosingFilter(fct, structure=np.ones(sf2, int))          BabelDatasetPreps.py:881-883 (scipy.ndimage.binary_closing; sf2 = 14 at 0.3675 mm)
+//     binary_dilation(mask, iterations=6), binary_erosion(mask, iterations=n)     :901, :953, :1106
+//     LabelImage(nfct), regionprops, the largest region              :888-894, :910-929, :1055-1058, :1078-1081
+//
+// Morphology. The mask is packed to one bit per voxel along k (__ballot: 64 voxels per wave-wide word; layout in bfd_morph_core.h) and every pass
+// works on whole words, one thread per word:
+//   box path (all-ones structure, 1..31 per axis): three 1-D passes per erosion / dilation, k (shifts across the two neighbouring words), then
+//     j and i (AND / OR of whole words). s taps per word and pass, never s1 s2 s3.
+//   general path (any structure up to 7 x 7 x 7, NULL = the cross): the true elements as a tap list grouped by (di, dj), one launch per iteration.
+//   Both ping-pong two packed buffers. Outside the volume (and past N3 in a row's last word) every reader sees the border value.
+// Labelling. Union-find on linear voxel indices; a parent is never larger than its child, so a root is its component's first voxel in raster order:
+//   1. one workgroup per 8 x 8 x 64 tile: union-find of the tile in LDS (local ids), written out as global indices
+//   2. one thread per voxel: unions with the preceding neighbours that lie in another tile (faces, edges, corners), atomicMin in global memory
+//   3. flatten: every voxel points at its root
+//   4. roots (parent == self) flagged, inclusive prefix sum in raster order (rocPRIM): label of a component = rank of its root, scipy's numbering
+//   5. sizes by one histogram pass (one atomic per wave and distinct label), the largest by a reduction, its mask
+// No kernel waits for another workgroup; every loop is bounded, see the comment at each.
+#include <string.h>
+#include "bfd_internal.h"
+#include "bfd_morph_core.h"
+#include <rocprim/device/device_scan.hpp>
+
+namespace {
+
+constexpr int MB_THREADS = 256;
+constexpr int MAX_BOX = 31;
+
+inline unsigned blocks_for(long items, int perBlock) { return (unsigned)std::max<long>(1, std::min<long>((items + perBlock - 1) / perBlock, 1L << 16)); }
+
+// ---------------------------------------------------------------- morphology kernels ----------------------------------------------------------------
+
+// one wave per word: lane l holds voxel 64 w + l of the row
+__global__ __launch_bounds__(MB_THREADS) void morph_pack(const uint8_t *__restrict__ in, uint64_t *__restrict__ bits, const morph_dims g, long nWords)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // grid-stride, the same trip count for every lane of a wave (the word index is wave-uniform): ends after ceil(nWords / (4 gridDim)) rounds
+    for (long wd = (long)blockIdx.x * (MB_THREADS / 64) + wave; wd < nWords; wd += (long)gridDim.x * (MB_THREADS / 64)) {
+        const long row = wd / g.nW;
+        const int w = (int)(wd - row * g.nW), k = w * 64 + lane;
+        const bool on = k < g.N3 && in[row * g.N3 + k] != 0;
+        const unsigned long long b = __ballot(on);
+        if (lane == 0) bits[wd] = b;
+    }
+}
+
+__global__ __launch_bounds__(MB_THREADS) void morph_unpack(const uint64_t *__restrict__ bits, uint8_t *__restrict__ out, const morph_dims g, long nVox)
+{
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS) {      // grid-stride: ends
+        const long row = v / g.N3;
+        const int k = (int)(v - row * g.N3);
+        out[v] = (uint8_t)((bits[row * g.nW + (k >> 6)] >> (k & 63)) & 1u);
+    }
+}
+
+// axis 0, 1: whole words along i, j; axis 2: along k
+__global__ __launch_bounds__(MB_THREADS) void morph_box_pass(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, const morph_dims g, long nWords,
+                                                             int axis, int lo, int hi, int dilate, uint64_t fill)
+{
+    for (long wd = (long)blockIdx.x * MB_THREADS + threadIdx.x; wd < nWords; wd += (long)gridDim.x * MB_THREADS) {  // grid-stride: ends
+        const long row = wd / g.nW;
+        const int w = (int)(wd - row * g.nW), i = (int)(row / g.N2), j = (int)(row - (long)i * g.N2);
+        dst[wd] = axis == 2 ? morph_pass_k(src, g, i, j, w, lo, hi, dilate != 0, fill) : morph_pass_ij(src, g, i, j, w, axis, lo, hi, dilate != 0, fill);
+    }
+}
+
+__global__ __launch_bounds__(MB_THREADS) void morph_general_pass(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, const morph_dims g, long nWords,
+                                                                 const morph_taps t, int dilate, uint64_t fill)
+{
+    for (long wd = (long)blockIdx.x * MB_THREADS + threadIdx.x; wd < nWords; wd += (long)gridDim.x * MB_THREADS) {  // grid-stride: ends
+        const long row = wd / g.nW;
+        const int w = (int)(wd - row * g.nW), i = (int)(row / g.N2), j = (int)(row - (long)i * g.N2);
+        dst[wd] = morph_general(src, g, i, j, w, t, dilate != 0, fill);
+    }
+}
+
+// ---------------------------------------------------------------- labelling kernels ----------------------------------------------------------------
+
+// Parents are read with relaxed atomic loads: another thread may lower them at any time, and a value once read is still an ancestor-or-equal candidate
+// that the caller's atomicMin checks.
+static __device__ __forceinline__ int uf_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Root of x. Ends: a parent that is not the voxel itself is strictly smaller (the invariant parent <= child is kept by every write: uf_union only
+// stores values smaller than the index it stores to, and the flatten stores roots), so x strictly decreases and is bounded by 0.
+static __device__ __forceinline__ int uf_find(const int *L, int x)
+{
+    int p = uf_load(L + x);
+    while (p != x) { x = p; p = uf_load(L + x); }
+    return x;
+}
+
+// Joins the components of a and b. Ends: every round that does not return replaces a by a value read back from L[a] that differs from a; L[a] only
+// ever holds a or smaller, so the new a is strictly smaller, while b never grows (find only descends): a + b strictly decreases and is bounded by 0.
+// A retry therefore happens only after an atomicMin found L[a] already lowered by someone else; the link that our own atomicMin may have replaced
+// (old, when b < old) is re-made by the next round, which joins old with b.
+static __device__ __forceinline__ void uf_union(int *L, int a, int b)
+{
+    while (true) {
+        a = uf_find(L, a);
+        b = uf_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(L + a, b);        // a was a root when read: L[a] == a unless another thread linked it meanwhile
+        if (old == a) return;
+        a = old;
+    }
+}
+
+struct label_dims { int N1, N2, N3, nTj, nTk; long nTiles; int conn; };
+
+// 1. local union-find of one tile in LDS
+__global__ __launch_bounds__(MB_THREADS) void label_local(const uint8_t *__restrict__ in, int *__restrict__ L, const label_dims g)
+{
+    __shared__ int lab[LT_VOX];                       // 16 KiB
+    for (long t = blockIdx.x; t < g.nTiles; t += gridDim.x) {          // grid-stride over tiles, block-uniform: ends
+        const int bk = (int)(t % g.nTk);
+        const long q = t / g.nTk;
+        const int bj = (int)(q % g.nTj), bi = (int)(q / g.nTj);
+        const int i0 = bi * LT_I, j0 = bj * LT_J, k0 = bk * LT_K;
+        __syncthreads();                              // the tile before this one has been written out
+        for (int v = threadIdx.x; v < LT_VOX; v += MB_THREADS) {
+            const int i = i0 + v / (LT_J * LT_K), j = j0 + (v / LT_K) % LT_J, k = k0 + v % LT_K;
+            const bool on = i < g.N1 && j < g.N2 && k < g.N3 && in[((long)i * g.N2 + j) * g.N3 + k] != 0;
+            lab[v] = on ? v : -1;
+        }
+        __syncthreads();
+        for (int v = threadIdx.x; v < LT_VOX; v += MB_THREADS) {
+            if (uf_load(lab + v) < 0) continue;       // background stays -1 for ever
+            const int ii = v / (LT_J * LT_K), jj = (v / LT_K) % LT_J, kk = v % LT_K;
+            for (int nb = 0; nb < 13; nb++) {
+                int di, dj, dk;
+                if (!label_backward_neighbour(nb, g.conn, &di, &dj, &dk)) continue;
+                const int ni = ii + di, nj = jj + dj, nk = kk + dk;
+                if (ni < 0 || nj < 0 || nj >= LT_J || nk < 0 || nk >= LT_K) continue;       // in another tile: step 2
+                const int u = (ni * LT_J + nj) * LT_K + nk;
+                if (uf_load(lab + u) >= 0) uf_union(lab, v, u);
+            }
+        }
+        __syncthreads();
+        for (int v = threadIdx.x; v < LT_VOX; v += MB_THREADS) {
+            const int i = i0 + v / (LT_J * LT_K), j = j0 + (v / LT_K) % LT_J, k = k0 + v % LT_K;
+            if (i >= g.N1 || j >= g.N2 || k >= g.N3) continue;
+            int r = lab[v];
+            if (r >= 0) {
+                r = uf_find(lab, v);                  // nobody writes lab any more
+                r = (int)(((long)(i0 + r / (LT_J * LT_K)) * g.N2 + j0 + (r / LT_K) % LT_J) * g.N3 + k0 + r % LT_K);
+            }
+            L[((long)i * g.N2 + j) * g.N3 + k] = r;
+        }
+    }
+}
+
+// 2. unions across tile faces, edges and corners
+__global__ __launch_bounds__(MB_THREADS) void label_merge(int *__restrict__ L, const label_dims g, long nVox)
+{
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS) {      // grid-stride: ends
+        const long row = v / g.N3;
+        const int k = (int)(v - row * g.N3), i = (int)(row / g.N2), j = (int)(row - (long)i * g.N2);
+        // a preceding neighbour is (i - 1, j +- 1, k +- 1), (i, j - 1, k +- 1) or (i, j, k - 1): away from the tile's low i face and from both of
+        // its j and k faces all of them lie in the same tile
+        const int tj = j % LT_J, tk = k % LT_K;
+        if ((i % LT_I) && tj && tj != LT_J - 1 && tk && tk != LT_K - 1) continue;
+        if (uf_load(L + v) < 0) continue;
+        for (int nb = 0; nb < 13; nb++) {
+            int di, dj, dk;
+            if (!label_backward_neighbour(nb, g.conn, &di, &dj, &dk)) continue;
+            const int ni = i + di, nj = j + dj, nk = k + dk;
+            if (ni < 0 || nj < 0 || nj >= g.N2 || nk < 0 || nk >= g.N3) continue;
+            if (ni / LT_I == i / LT_I && nj / LT_J == j / LT_J && nk / LT_K == k / LT_K) continue;     // joined in step 1
+            const long u = ((long)ni * g.N2 + nj) * g.N3 + nk;
+            if (uf_load(L + u) >= 0) uf_union(L, (int)v, (int)u);
+        }
+    }
+}
+
+// 3. every voxel points at its root; flag[v] = 1 at roots. Concurrent flattening only replaces a parent by an ancestor: the invariant holds.
+__global__ __launch_bounds__(MB_THREADS) void label_flatten(int *__restrict__ L, int *__restrict__ flag, long nVox)
+{
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS) {      // grid-stride: ends
+        int r = uf_load(L + v);
+        if (r >= 0) {
+            r = uf_find(L, (int)v);
+            __hip_atomic_store(L + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        flag[v] = r == (int)v ? 1 : 0;
+    }
+}
+
+// 4. label = rank of the root among the roots (rank: inclusive prefix sum of the flags). In place: L[v] is read by thread v alone.
+__global__ __launch_bounds__(MB_THREADS) void label_assign(int *__restrict__ L, const int *__restrict__ rank, long nVox)
+{
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS) {      // grid-stride: ends
+        const int r = L[v];
+        L[v] = r >= 0 ? rank[r] : 0;
+    }
+}
+
+// 5a. voxel counts: the lanes of a wave that hold the same label add once
+__global__ __launch_bounds__(MB_THREADS) void label_sizes(const int *__restrict__ labels, unsigned long long *__restrict__ sizes, long nVox)
+{
+    const int lane = threadIdx.x & 63;
+    const long rounds = (nVox + (long)gridDim.x * MB_THREADS - 1) / ((long)gridDim.x * MB_THREADS);
+    for (long it = 0; it < rounds; it++) {            // the same trip count for every thread (the ballots below need whole waves)
+        const long v = (it * gridDim.x + blockIdx.x) * MB_THREADS + threadIdx.x;
+        const int lab = v < nVox ? labels[v] : 0;
+        unsigned long long todo = __ballot(lab > 0);
+        while (todo) {                                // ends: wave-uniform, and every round clears at least its leader's bit (at most 64 rounds)
+            const int leader = __ffsll(todo) - 1;
+            const int which = __shfl(lab, leader);
+            const unsigned long long same = __ballot(lab == which) & todo;
+            if (lane == leader) atomicAdd(sizes + (which - 1), (unsigned long long)__popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
+// 5b. the label with the most voxels, among equals the highest; one workgroup. best[0] = label (0: no component)
+__global__ __launch_bounds__(1024) void label_largest(const unsigned long long *__restrict__ sizes, int n, int *__restrict__ best)
+{
+    __shared__ unsigned long long sz[1024];
+    __shared__ int id[1024];
+    unsigned long long s = 0;
+    int b = 0;
+    for (int q = threadIdx.x; q < n; q += 1024)       // ascending labels: >= lets the later of two equals win
+        if (sizes[q] >= s) { s = sizes[q]; b = q + 1; }
+    sz[threadIdx.x] = s; id[threadIdx.x] = b;
+    __syncthreads();
+    for (int h = 512; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            const unsigned long long s2 = sz[threadIdx.x + h];
+            const int b2 = id[threadIdx.x + h];
+            if (s2 > sz[threadIdx.x] || (s2 == sz[threadIdx.x] && b2 > id[threadIdx.x])) { sz[threadIdx.x] = s2; id[threadIdx.x] = b2; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) best[0] = id[0];
+}
+
+__global__ __launch_bounds__(MB_THREADS) void label_select(const int *__restrict__ labels, const int *__restrict__ best, uint8_t *__restrict__ out, long nVox)
+{
+    const int b = best[0];
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS)        // grid-stride: ends
+        out[v] = (b > 0 && labels[v] == b) ? 1 : 0;
+}
+
+// fewer than 2^31 voxels; the product is formed without overflow
+bool volume_fits(int64_t N1, int64_t N2, int64_t N3)
+{
+    const int64_t LIMIT = (int64_t)1 << 31;
+    return !(N1 >= LIMIT || N2 >= LIMIT || N3 >= LIMIT || (N2 && N1 > (LIMIT - 1) / N2) || (N3 && N1 * N2 > (LIMIT - 1) / N3));
+}
+
+bool overlap(const void *p, size_t pb, const void *q, size_t qb)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qb && b < a + pb;
+}
+
+int pick_device(const char *who, int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, std::string(who) + ": no HIP device available (no CPU fallback)");
+    if (device < 0 || device >= ndev) BFD_FAIL(-3, std::string(who) + ": device ordinal out of range");
+    BFD_HIP(hipSetDevice(device));
+    return 0;
+}
+
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+    hipError_t create() { hipError_t e = hipEventCreate(&e0); return e == hipSuccess ? hipEventCreate(&e1) : e; }
+};
+
+}  // namespace
+
+extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3,
+                                       const uint8_t *structure, int s1, int s2, int s3, int iterations, int borderValue, float *kernelMs)
+{
+    static const char *who = "bfd_binary_morphology3d";
+    // every argument error is reported before a device is looked for
+    if (op < 0 || op > 3) BFD_FAIL(-1, std::string(who) + ": op must be 0 (erosion), 1 (dilation), 2 (closing) or 3 (opening)");
+    if (!in || !out) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (iterations < 1) BFD_FAIL(-1, std::string(who) + ": iterations must be at least 1");
+    if (borderValue != 0 && borderValue != 1) BFD_FAIL(-1, std::string(who) + ": borderValue must be 0 or 1");
+    if (op >= 2 && borderValue != 0) BFD_FAIL(-1, std::string(who) + ": borderValue is 0 for closing and opening");
+    const size_t n = (size_t)(N1 * N2 * N3);
+    if (overlap(in, n, out, n) && n) BFD_FAIL(-1, std::string(who) + ": out may not alias in");
+    static const uint8_t cross[27] = {0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 1, 1, 1, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
+    if (!structure) { structure = cross; s1 = s2 = s3 = 3; }
+    if (s1 < 1 || s2 < 1 || s3 < 1) BFD_FAIL(-1, std::string(who) + ": every structure size must be at least 1");
+    bool box = true;
+    long nTrue = 0;
+    for (long q = 0; q < (long)s1 * s2 * s3; q++) { if (structure[q]) nTrue++; else box = false; }
+    if (box && (s1 > MAX_BOX || s2 > MAX_BOX || s3 > MAX_BOX))
+        BFD_FAIL(-1, std::string(who) + ": an all-ones structure may have at most 31 elements per axis");
+    if (!box && (s1 > MORPH_GEN_MAX || s2 > MORPH_GEN_MAX || s3 > MORPH_GEN_MAX))
+        BFD_FAIL(-1, std::string(who) + ": a structure that is not all ones may have at most 7 elements per axis");
+    if (nTrue == 0) BFD_FAIL(-1, std::string(who) + ": the structure has no true element");
+    const int s[3] = {s1, s2, s3};
+    morph_taps taps[2];                               // [0] erosion, [1] dilation
+    if (!box) { morph_make_taps(structure, s1, s2, s3, false, &taps[0]); morph_make_taps(structure, s1, s2, s3, true, &taps[1]); }
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (n == 0) return 0;
+
+    const morph_dims g = morph_make_dims((int)N1, (int)N2, (int)N3);
+    const long nWords = (long)N1 * N2 * g.nW;
+    DevTemp<uint8_t> vol;
+    DevTemp<uint64_t> bitsA, bitsB;
+    EventPair ev;
+    hipError_t e = vol.alloc(n);
+    if (e == hipSuccess) e = bitsA.alloc((size_t)nWords);
+    if (e == hipSuccess) e = bitsB.alloc((size_t)nWords);
+    if (e == hipSuccess) e = hipMemcpy(vol, in, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+    if (e == hipSuccess) {
+        uint64_t *src = bitsA, *dst = bitsB;
+        hipLaunchKernelGGL(morph_pack, dim3(blocks_for(nWords, MB_THREADS / 64)), dim3(MB_THREADS), 0, 0, vol.p, src, g, nWords);
+        const unsigned wb = blocks_for(nWords, MB_THREADS);
+        // closing: dilations then erosions; opening: erosions then dilations (scipy: each `iterations` times)
+        const int first = (op == 1 || op == 2) ? 1 : 0, stages = op >= 2 ? 2 : 1;
+        for (int st = 0; st < stages; st++) {
+            const int dilate = st == 0 ? first : 1 - first;
+            const uint64_t fill = borderValue ? ~(uint64_t)0 : 0;
+            for (int it = 0; it < iterations; it++) {
+                if (box) {
+                    for (int axis = 2; axis >= 0; axis--) {
+                        if (s[axis] == 1) continue;
+                        int lo, hi;
+                        morph_box_taps(s[axis], dilate != 0, &lo, &hi);
+                        hipLaunchKernelGGL(morph_box_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, axis, lo, hi, dilate, fill);
+                        std::swap(src, dst);
+                    }
+                } else {
+                    hipLaunchKernelGGL(morph_general_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, taps[dilate], dilate, fill);
+                    std::swap(src, dst);
+                }
+            }
+        }
+        hipLaunchKernelGGL(morph_unpack, dim3(blocks_for((long)n, MB_THREADS)), dim3(MB_THREADS), 0, 0, src, vol.p, g, (long)n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
+    if (e == hipSuccess) e = hipMemcpy(out, vol, n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    return 0;
+}
+
+extern "C" int bfd_label3d(int device, const uint8_t *in, int32_t *labels, int64_t N1, int64_t N2, int64_t N3, int connectivity,
+                           int64_t *numLabels, int64_t *sizes, int64_t sizesCapacity, uint8_t *largest, float *kernelMs)
+{
+    static const char *who = "bfd_label3d";
+    if (!in) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (!labels && !numLabels && !sizes && !largest) BFD_FAIL(-1, std::string(who) + ": no output asked for");
+    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (connectivity < 1 || connectivity > 3) BFD_FAIL(-1, std::string(who) + ": connectivity must be 1, 2 or 3");
+    if (sizesCapacity < 0) BFD_FAIL(-1, std::string(who) + ": negative sizesCapacity");
+    const size_t n = (size_t)(N1 * N2 * N3);
+    if (n && ((labels && overlap(in, n, labels, 4 * n)) || (largest && overlap(in, n, largest, n)) || (labels && largest && overlap(labels, 4 * n, largest, n))))
+        BFD_FAIL(-1, std::string(who) + ": an output may not alias in or another output");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (numLabels) *numLabels = 0;
+    if (n == 0) return 0;
+
+    label_dims g;
+    g.N1 = (int)N1; g.N2 = (int)N2; g.N3 = (int)N3; g.conn = connectivity;
+    g.nTj = (int)((N2 + LT_J - 1) / LT_J); g.nTk = (int)((N3 + LT_K - 1) / LT_K);
+    g.nTiles = (long)g.nTk * g.nTj * ((N1 + LT_I - 1) / LT_I);
+    const long nv = (long)n;
+    const bool wantSizes = sizes || largest;
+
+    DevTemp<uint8_t> vol;                             // the input; afterwards the mask of the largest component
+    DevTemp<int> L, rank, best;
+    DevTemp<char> work;
+    DevTemp<unsigned long long> dsz;
+    EventPair ev;
+    size_t wbytes = 0;
+    int nl = 0;
+    float ms = 0.f, ms2 = 0.f;
+    hipError_t e = vol.alloc(n);
+    if (e == hipSuccess) e = L.alloc(n);
+    if (e == hipSuccess) e = rank.alloc(n);
+    if (e == hipSuccess) e = best.alloc(1);
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, rank.p, rank.p, n, rocprim::plus<int>(), (hipStream_t)0);
+    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
+    if (e == hipSuccess) e = hipMemcpy(vol, in, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+    const unsigned vb = blocks_for(nv, MB_THREADS);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(label_local, dim3(blocks_for(g.nTiles, 1)), dim3(MB_THREADS), 0, 0, vol.p, L.p, g);
+        hipLaunchKernelGGL(label_merge, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, g, nv);
+        hipLaunchKernelGGL(label_flatten, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, rank.p, rank.p, n, rocprim::plus<int>(), (hipStream_t)0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(label_assign, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev.e0, ev.e1);
+    // the number of components sizes the histogram: the one value the host needs between the kernels
+    if (e == hipSuccess) e = hipMemcpy(&nl, rank.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && wantSizes && nl > 0) {
+        e = dsz.alloc((size_t)nl);
+        if (e == hipSuccess) e = hipMemset(dsz, 0, (size_t)nl * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(label_sizes, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, dsz.p, nv);
+            if (largest) {
+                hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, dsz.p, nl, best.p);
+                hipLaunchKernelGGL(label_select, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, best.p, vol.p, nv);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+        if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms2, ev.e0, ev.e1);
+        if (e == hipSuccess && sizes && sizesCapacity >= nl) e = hipMemcpy(sizes, dsz, (size_t)nl * sizeof(int64_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && largest) e = hipMemcpy(largest, vol, n, hipMemcpyDeviceToHost);
+    } else if (e == hipSuccess && largest) {
+        memset(largest, 0, n);                        // no component: an all-zero mask
+    }
+    if (e == hipSuccess && labels) e = hipMemcpy(labels, L, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    if (numLabels) *numLabels = nl;
+    if (kernelMs) *kernelMs = ms + ms2;
+    return 0;
+}

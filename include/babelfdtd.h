@@ -458,6 +458,35 @@ int bfd_median_filter3d(int device, int dtype /*0 u8, 1 f32*/, const void *in, v
                         int64_t N1, int64_t N2, int64_t N3, int s1, int s2, int s3,
                         int mode /*0 reflect, 1 constant*/, double cval, float *kernelMs /*may be NULL*/);
 
+/* ---- binary morphology and component labelling of Step-1 masks: what follows the median in BabelDatasetPreps.py ----
+ * (:881-883 BinaryClosingFilter = scipy.ndimage.binary_closing with an all-ones structure of round(5 mm / voxel) per axis; :901, :953, :1106
+ * binary_dilation / binary_erosion with the default cross and iterations; :888-894, :910-929, :1055-1058, :1078-1081 LabelImage, the largest region.)
+ * Conventions of bfd_median_filter3d: HOST pointers to [N1][N2][N3] volumes in numpy C order (k fastest), fewer than 2^31 voxels; the input is never
+ * written and no output may overlap it; returns 0; -1 bad argument (reported before a device is looked for), -3 no such device, -10 device error;
+ * text in bfd_last_error; kernelMs (may be NULL): device time of the kernels alone, HIP events; device memory lives for the call; no CPU fallback.
+ *
+ * bfd_binary_morphology3d: op 0 erosion, 1 dilation, 2 closing, 3 opening of the uint8 mask `in` (non-zero = true) into `out` (exactly 0 or 1), equal
+ * voxel for voxel to scipy.ndimage.binary_erosion / binary_dilation / binary_closing / binary_opening(in, structure, iterations, border_value=...)
+ * with origin 0, scipy's mirrored window for even sizes included. structure: uint8 [s1][s2][s3] (non-zero = true), or NULL for the 3 x 3 x 3 cross
+ * generate_binary_structure(3, 1) (s1, s2, s3 are then ignored). An all-ones structure may have 1..31 elements per axis and is applied as three
+ * 1-D passes per erosion / dilation; any other structure at most 7 per axis and at least one true element (otherwise -1). iterations >= 1.
+ * borderValue (what lies outside the volume): 0 or 1 for erosion and dilation, 0 for closing and opening. Device memory during the call: the
+ * volume (1 B per voxel) and two bit-packed copies (1 bit per voxel each, rows padded to 64 voxels). */
+int bfd_binary_morphology3d(int device, int op /*0 erode, 1 dilate, 2 close, 3 open*/, const uint8_t *in, uint8_t *out,
+                            int64_t N1, int64_t N2, int64_t N3, const uint8_t *structure /*may be NULL: the cross*/, int s1, int s2, int s3,
+                            int iterations, int borderValue, float *kernelMs /*may be NULL*/);
+
+/* bfd_label3d: connected components of the uint8 mask `in` (non-zero = foreground). connectivity 1, 2, 3 = 6, 18, 26 neighbours, scipy's
+ * generate_binary_structure(3, connectivity). labels (int32 [N1][N2][N3], may be NULL): 0 = background, components numbered 1..n in the order of their
+ * first voxel in C-order raster scan -- equal element for element to scipy.ndimage.label(in, generate_binary_structure(3, connectivity))[0].
+ * numLabels (may be NULL) receives n. sizes (int64, may be NULL) receives the voxel counts of labels 1..n when sizesCapacity >= n, and is left alone
+ * otherwise. largest (uint8 [N1][N2][N3], may be NULL) receives the mask (0 / 1) of the component with the most voxels, among equals the one with
+ * the highest label; all zero when there is no component. At least one output must be asked for. Device memory during the call: 9 B per voxel
+ * (the mask, parents / labels, root ranks), the prefix sum's scratch block and 8 B per component. */
+int bfd_label3d(int device, const uint8_t *in, int32_t *labels /*may be NULL*/, int64_t N1, int64_t N2, int64_t N3, int connectivity,
+                int64_t *numLabels /*may be NULL*/, int64_t *sizes /*may be NULL*/, int64_t sizesCapacity, uint8_t *largest /*may be NULL*/,
+                float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

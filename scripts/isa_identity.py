@@ -20,7 +20,7 @@ import sys
 import tempfile
 
 LLVM = os.environ.get('LLVM_BIN', '/opt/rocm/lib/llvm/bin')
-SRC = ['bfd_api', 'bfd_outputs', 'bfd_placement', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte', 'bfd_median']
+SRC = ['bfd_api', 'bfd_outputs', 'bfd_placement', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte', 'bfd_median', 'bfd_morphology']
 
 
 def kernels(obj, tmp):
