@@ -190,3 +190,23 @@ def save_step10(FILENAMES, volumes, mask_data=None, mask_affine=None):
         if mask_data is not None and key in ('FullElasticSolution_Sub__', 'FullElasticSolutionRefocus_Sub__'):
             written.append(resave_normalized(fn, mask_data, mask_affine))
     return written
+
+
+class SpatialImage:
+    """The least of a nibabel image that `Resample.ResampleFromTo` reads and returns: `dataobj`, `affine` (4 x 4 float64), `header` (kept as
+    given, never read here) and `shape`, with `get_fdata()` as nibabel has it (the voxels as float64). `SpatialImage(data, affine, header)`
+    has nibabel's constructor order, so it can stand in for `out_class`."""
+
+    def __init__(self, dataobj, affine, header=None):
+        self.dataobj = np.asarray(dataobj)
+        self.affine = np.array(affine, np.float64)
+        if self.affine.shape != (4, 4):
+            raise ValueError('affine must be 4 x 4, not %s' % (self.affine.shape,))
+        self.header = header
+
+    @property
+    def shape(self):
+        return self.dataobj.shape
+
+    def get_fdata(self):
+        return np.asarray(self.dataobj, np.float64)

@@ -487,6 +487,32 @@ int bfd_label3d(int device, const uint8_t *in, int32_t *labels /*may be NULL*/, 
                 int64_t *numLabels /*may be NULL*/, int64_t *sizes /*may be NULL*/, int64_t sizesCapacity, uint8_t *largest /*may be NULL*/,
                 float *kernelMs /*may be NULL*/);
 
+/* ---- spline resampling of Step-1 volumes: scipy.ndimage.affine_transform / spline_filter behind GPUFunctions/GPUResample/Resample.py::ResampleFromTo ----
+ * (callback installed at CalculateMaskProcess.py:65-74; callers BabelDatasetPreps.py:859 CT, order 3; :1168 T1, order 0; CTZTEProcessing.py:258.)
+ * Conventions of bfd_median_filter3d: HOST pointers to C-order volumes (k fastest), input and output each fewer than 2^31 voxels, the input is
+ * never written and out may not overlap it; returns 0; -1 bad argument (reported before a device is looked for), -3 no such device, -10 device
+ * error; text in bfd_last_error; kernelMs (may be NULL): device time of the kernels alone, HIP events; device memory lives for the call and is
+ * freed on every path; no CPU fallback.
+ * dtype: 0 uint8, 1 float32, 2 int16, 3 float64, of in and of out alike. matrix: twelve doubles, row a = (m_a0, m_a1, m_a2, offset_a); output
+ * voxel (i, j, k) takes the input at coordinate_a = offset_a + m_a0 i + m_a1 j + m_a2 k. order 0..3; mode 0 constant (cval outside
+ * [0, N - 1]), 1 nearest, 2 mirror, with scipy's meaning, scipy's 12-sample edge padding before the prefilter of `nearest` included.
+ * flags: bit 0 (1) = prefilter: with order >= 2, in holds samples and the B-spline coefficients are computed first (float64, on the device);
+ * otherwise in is interpolated as it is. Bit 1 (2) = gathered interpolation also at order 3, where the default stages the source box of each
+ * 4 x 8 x 32 output tile in LDS; the two give the same bits (for checks and timing). kernelMs here points to TWO floats: device time of the
+ * prefilter and of the interpolation. All arithmetic is float64, rounded once at the store: to float32 by the conversion, to the integer dtypes by scipy's
+ * rule, trunc(t + 0.5) for t > 0 and trunc(t - 0.5) otherwise (half away from zero), saturating; uint8 gives 0 for every t <= 0. cval takes the
+ * same conversion and must be finite for integer dtypes; the matrix must be finite. Device memory: in, out and, with the prefilter,
+ * 8 B per (padded) input voxel. */
+int bfd_affine_transform3d(int device, int dtype, const void *in, void *out, int64_t N1, int64_t N2, int64_t N3,
+                           int64_t O1, int64_t O2, int64_t O3, const double *matrix /*[12]*/, int order, int mode, double cval, int flags,
+                           float *kernelMs /*[2], may be NULL*/);
+
+/* bfd_spline_filter3d: the prefilter alone, scipy.ndimage.spline_filter(in, order, output=float64, mode): out is float64 [N1][N2][N3]. Modes
+ * constant and mirror filter with mirror boundaries, nearest with reflect boundaries (no padding here, as in scipy); orders 0 and 1 and axes of
+ * length 1 pass through. */
+int bfd_spline_filter3d(int device, int dtype, const void *in, double *out, int64_t N1, int64_t N2, int64_t N3, int order, int mode,
+                        float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
