@@ -1,10 +1,13 @@
 """RunBHTECycles (one bfd_bhte_run_protocol call for a whole repeated-sonication protocol) against the reference's loop of
 BHTE / BHTEMultiplePressureFields calls (CalculateTemperatureEffects.py:259-460), restated here over the existing drop-ins:
-every output is bit-equal. Small grids: the whole file takes a few seconds."""
+every output is bit-equal. And against the numpy oracle run over protocol_schedule (tests/bhte_reference.py): the temperature maximum over the capture
+steps, the final temperature and the whole point series to equality, the dose at the last capture and the final dose voxel by voxel to the
+derived bound. Small grids: the whole file takes a few seconds."""
 import numpy as np
 import pytest
 
 from oracle import bhte_oracle as BO
+from tests import bhte_reference as BR
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +73,33 @@ def _equal(a, b):
     assert a[5] == b[5]
 
 
+def _ftz(a):
+    """the library flushes subnormal float32 results to zero (tests/test_bhte_gpu.py holds the returned heat source to this)"""
+    a = np.array(a, np.float32)
+    a[np.abs(a) < np.finfo(np.float32).tiny] = 0
+    return a
+
+
+def _against_oracle(got, args, fields, mm, ml, dx, nOn, nStepsOn, dt, duty, mpm, T0, what):
+    """RunBHTECycles' six returns of a run from nCurrent = 0 (start T0, no dose) against the oracle's history over protocol_schedule"""
+    from babelbrain_amd import RayleighAndBHTE as R
+    fields = np.asarray(fields)
+    single = fields.ndim == 3
+    sched, caps, _, nNext = R.protocol_schedule(*args, nOn, nStepsOn, multi_field=not single)
+    cd, cp, qf = R.bhte_coefficients(ml, dx, dt, duty if single else 1.0)
+    q = _ftz((fields.astype(np.float32) ** 2) * qf[mm])
+    h = BR.history(T0, np.zeros(mm.shape, np.float32), q, mm, cd, cp, 37.0, dt, sched)
+    assert h.n == len(sched) == got[4].shape[1] and got[5] == nNext and len(caps) >= 1
+    BR.assert_equal(got[0], h.running_max(caps), what + ': maximum over the captures', 'ijk', mm)
+    BR.assert_equal(got[2], h.T, what + ': final temperature', 'ijk', mm)
+    BR.assert_equal(got[4], h.points(BR.points_of(mpm)), what + ': point series', 'ps')
+    last = int(caps[-1])
+    a = BR.assert_dose(got[1], h.dose64(last), last, what + ': dose at the last capture', T=h.at_boundary(last), mat=mm)
+    b = BR.assert_dose(got[3], h.dose64(), h.n, what + ': final dose', T=h.T, mat=mm)
+    print('%s: dose at the last capture at %.3f of the bound, final dose at %.3f' % (what, a, b))
+    return h
+
+
 def test_single_field_protocol_equals_chained_calls():
     from babelbrain_amd import RayleighAndBHTE as R
     N = (40, 36, 44)
@@ -97,6 +127,7 @@ def test_steered_fields_protocol_equals_chained_calls():
     ref = _chained(*args, False, fields, mm, ml, dx, 29, onoff, dt, 0.5, mpm, 37.0, None, None, None, None)
     _equal(got, ref)
     assert got[0].max() > 38.0
+    _against_oracle(got, args, fields, mm, ml, dx, 29, onoff, dt, 0.5, mpm, np.full(N, 37.0, np.float32), 'steered protocol 36x40x44')
 
 
 def test_no_off_no_pause_from_previous_data():
@@ -156,3 +187,5 @@ def test_short_segments_split_the_passes(nOn, nStepsOn, off, pause):
     q = (fields.astype(np.float32) ** 2) * qf[mm]
     To, Do = BO.bhte(np.full(N, 37.0, np.float32), np.zeros(N, np.float32), q, mm, cd, cp, 37.0, dt, len(sched), 0, field_of_step=sched)
     assert rel_l2(got[2] - 37.0, To - 37.0) < 1e-5 and rel_l2(got[3], Do) < 1e-5
+    h = _against_oracle(got, args, fields[0], mm, ml, dx, nOn, nStepsOn, dt, 1.0, mpm, np.full(N, 37.0, np.float32), 'protocol on %d off %d pause %d' % (nOn, off, pause))
+    assert np.array_equal(h.T, To)

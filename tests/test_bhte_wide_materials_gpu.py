@@ -1,8 +1,8 @@
 """The bio-heat solver on a CT-derived material list (16-bit ids: bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16). A CT plan quantises bone to
 2^10 bins behind the soft tissues, one thermal row per bin (CalculateTemperatureEffects.py:804-841): 6 + 1024 = 1030 rows here, density,
 speed of sound and attenuation varying across the bins. Every kernel that reads the ids has a 16-bit instantiation with the same expressions in
-the same order, so: every multi-step path has the bits of one step per launch; the temperature has the bits of the numpy oracle (dose 1e-6,
-exp2 against numpy's power: the bounds of tests/test_bhte_gpu.py); and a five-material problem whose rows are scattered over the 1030-row list
+the same order, so: every multi-step path has the bits of one step per launch; the temperature has the bits of the numpy oracle and the dose lies,
+voxel by voxel, within the derived bound of tests/bhte_reference.py; and a five-material problem whose rows are scattered over the 1030-row list
 has the bits of the 8-bit run -- which a dropped high byte or an id queue shifted by one plane cannot give."""
 import ctypes as C
 
@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 
 from oracle import bhte_oracle as BO
+from tests import bhte_reference as BR
 from tests.util import rel_l2
 from tests.test_bhte_gpu import _ftz, _materials
-from tests.test_bhte_protocol_gpu import _chained, _equal
+from tests.test_bhte_protocol_gpu import _against_oracle, _chained, _equal
 
 pytestmark = pytest.mark.gpu
 
@@ -105,6 +106,10 @@ def test_against_the_oracle(steps, monkeypatch):
     To, Do = BO.bhte(T0, np.zeros(N, np.float32), Q, mm, cd, cp, 37.0, DT, 23, 13)
     assert To.max() > 44.0
     assert np.array_equal(T, To) and rel_l2(D, Do) < 1e-6
+    h = BR.history(T0, np.zeros(N, np.float32), Q, mm, cd, cp, 37.0, DT, BO.single_field_schedule(23, 13))
+    BR.assert_equal(T, h.T, '16-bit ids, steps %s: temperature' % steps, 'ijk', mm)
+    worst = BR.assert_dose(D, h.dose64(), 23, '16-bit ids, steps %s: dose' % steps, T=h.T, mat=mm)
+    print('16-bit ids, steps per pass %s: dose at %.3f of the bound' % (steps, worst))
 
 
 def test_relabelled_five_material_problem_has_the_bits_of_the_8_bit_run(monkeypatch):
@@ -200,6 +205,7 @@ def test_protocol_on_the_wide_list_equals_chained_calls(monkeypatch):
     ref = _chained(*args, True, fields[0], mm, ml, DX, 13, 7, DT, 0.7, mpm, 37.0, None, None, None, None)
     _equal(got, ref)
     assert got[4].shape == (3, 4 * (13 + 6) + 2 * 10) and got[0].max() > 44.0
+    _against_oracle(got, args, fields[0], mm, ml, DX, 13, 7, DT, 0.7, mpm, ml['InitTemperature'].astype(np.float32)[mm], 'protocol on the 1030-row list 36x40x44')
     # steered fields (BHTEMultiplePressureFields calls)
     onoff = np.array([[5, 3]] * 2, np.int32)
     args = (0, 2, 2, 5, 4, 100)
