@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     'bfd_group_reset', 'bfd_group_timing_begin', 'bfd_group_timing_end', 'bfd_group_num_sensors', 'bfd_group_num_sensor_steps',
     'bfd_group_get_sensor_index', 'bfd_group_get_sensors', 'bfd_group_get_sensor_dft', 'bfd_group_get_map', 'bfd_group_device_bytes',
     'bfd_group_peer_status', 'bfd_placement_cache_release', 'bfd_median_filter3d', 'bfd_binary_morphology3d', 'bfd_label3d',
-    'bfd_affine_transform3d', 'bfd_spline_filter3d',
+    'bfd_affine_transform3d', 'bfd_spline_filter3d', 'bfd_voxelize_mesh', 'bfd_voxel_points', 'bfd_map_values3d',
 ]
 
 
@@ -203,6 +203,11 @@ def load_library():
     lib.bfd_affine_transform3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int64] * 6 + [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int,
                                            C.c_void_p]
     lib.bfd_spline_filter3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    lib.bfd_voxelize_mesh.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    lib.bfd_voxel_points.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    lib.bfd_map_values3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

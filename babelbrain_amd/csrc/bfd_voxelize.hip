@@ -1,0 +1,405 @@
+// Mesh voxelisation and CT value mapping of Step 1 on MI355X: the last two callbacks CalculateMaskProcess.py:37-73 installs.
+//
+// Replaces
+//     GPUFunctions.GPUVoxelize.Voxelize(mesh, targetResolution)        BabelDatasetPreps.py:570, :667, :670, :673 (skin, skull, CSF surfaces to
+//                                                                      lists of voxel centres; host fallback trimesh.voxelized(...).fill())
+//     GPUFunctions.GPUMapping.MappingFilter.MapFilter(HU, Sel, Unique) BabelDatasetPreps.py:1039 (host fallback :1034-1037, one pass per unique value)
+//
+// Voxelisation. The definition is in include/babelfdtd.h and, operation for operation, in bfd_voxelize_core.h: voxel (i, j, k) is set iff an odd
+// number of triangles cover the column centre (j, k) in projection and lie at or beyond the voxel centre along x. Float64 throughout.
+//   1. setup       one lane per triangle: the counter-clockwise projection, the normal, the clamped column box, its column count (vox_tri record);
+//                  inclusive prefix sum of the counts (rocPRIM, the scan the labelling uses): ends[t] = pairs of triangles 0 .. t
+//   2. crossings   one lane per (triangle, column) PAIR, not per triangle: a lane finds its triangle by binary search in ends[] (the lanes of a
+//                  large face take the same path: one broadcast load per step), runs the three edge tests and, where they pass, issues ONE
+//                  atomicXor of one bit: position c = min(floor(q), gx - 1) + 1 of the column's row in the crossing table (rows of gx + 1 bits
+//                  padded to 64-bit words, x fastest). The per-voxel formulation issues xmax + 1 atomics here. A launch sweeps VOX_SWEEP pairs;
+//                  longer pair ranges take further rounds of the same lanes (grid-stride).
+//                  XOR is commutative and associative: the table, and everything derived from it, is the same from run to run and for every
+//                  order of the triangles, whatever the arrival order of the atomics.
+//   3. scan        one lane per table word (loads coalesce along x and across columns): suffix parity inside the word by shifts, the parity of
+//                  the column's words above it as the carry. Voxel i is set iff an odd number of crossing bits sit at positions > i.
+//   4. pack/count  one lane per word of the caller's table (bit 31 - (index % 32) of word index / 32, index = i + gx (j + gy k), the reference's
+//                  packing): gathers its up-to-32 indices from the occupancy rows; popcounts are summed per wave, one atomic per wave (integer:
+//                  order-free). The mask, when asked for, is expanded from the packed table.
+//   bfd_voxel_points: popcount per table word, inclusive prefix sum, every word writes its points: ascending index order, deterministic
+//   (the reference's atomic counter returns them in a different order every run).
+// Scan and pack are two kernels where one could carry both: the scan is coalesced along the padded rows, the pack along the dense table, and the
+// occupancy rows between them cost 1 bit per voxel each way.
+// No kernel waits for another workgroup; every loop is bounded, see the comment at each.
+//
+// CT value mapping: one pass, 5 B read and 4 B written per voxel, four voxels per lane; binary search in the strictly increasing table, which is
+// staged in LDS up to MAP_LDS_ROWS rows and read from global memory (L2) beyond. Values are compared as integer keys (bfd_voxelize_core.h).
+#include <cmath>
+#include <string.h>
+#include "bfd_internal.h"
+#include "bfd_voxelize_core.h"
+#include <rocprim/device/device_scan.hpp>
+
+namespace {
+
+constexpr int VX_THREADS = 256;
+constexpr long VOX_SWEEP_BLOCKS = 4096;                        // pairs per sweep of the crossing kernel: 4096 x 256 = 2^20
+constexpr int64_t VOX_MAX_VOXELS = (int64_t)1 << 40;
+constexpr int MAP_LDS_ROWS = 4096;                             // 16 KiB of LDS
+constexpr int MAP_MAX_ROWS = 65536;
+
+inline unsigned blocks_for(int64_t items, int perBlock, int64_t cap = 1L << 16)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + perBlock - 1) / perBlock, cap));
+}
+
+// ---------------------------------------------------------------- voxelisation kernels ----------------------------------------------------------------
+
+__global__ __launch_bounds__(VX_THREADS) void vox_setup(const float *__restrict__ tris, int64_t n, const vox_grid g, vox_tri *__restrict__ recs,
+                                                        int64_t *__restrict__ counts)
+{
+    for (int64_t t = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; t < n; t += (int64_t)gridDim.x * VX_THREADS) {      // grid-stride: ends
+        float v[9];
+#pragma unroll
+        for (int q = 0; q < 9; q++) v[q] = tris[9 * t + q];
+        vox_tri r;
+        counts[t] = vox_setup_triangle(v, g, &r);
+        recs[t] = r;
+    }
+}
+
+__global__ __launch_bounds__(VX_THREADS) void vox_crossings(const vox_tri *__restrict__ recs, const int64_t *__restrict__ ends, int64_t n, const vox_grid g,
+                                                            unsigned long long *__restrict__ cross)
+{
+    const int64_t nPairs = ends[n - 1];
+    for (int64_t p = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; p < nPairs; p += (int64_t)gridDim.x * VX_THREADS) { // grid-stride: ends
+        int64_t lo = 0, hi = n - 1;                  // the first triangle with ends[t] > p; ends[n - 1] > p holds. Ends: hi - lo halves
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (ends[mid] > p) hi = mid; else lo = mid + 1;
+        }
+        const vox_tri &t = recs[lo];
+        const int64_t local = p - (lo ? ends[lo - 1] : 0);      // 0 <= local < nj nk
+        const int64_t kk = local / t.nj, jj = local - kk * t.nj;           // j fastest: neighbouring lanes, neighbouring rows of the table
+        const int64_t j = t.jl + jj, k = t.kl + kk;
+        const int64_t c = vox_crossing(t, g, j, k);              // 0, or 1 .. gx
+        if (c > 0) atomicXor(cross + (j + g.gy * k) * g.rowWords + (c >> 6), 1ull << (c & 63));
+    }
+}
+
+__global__ __launch_bounds__(VX_THREADS) void vox_scan(const uint64_t *__restrict__ cross, uint64_t *__restrict__ occ, const vox_grid g, int64_t nWords)
+{
+    for (int64_t wd = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; wd < nWords; wd += (int64_t)gridDim.x * VX_THREADS) {     // grid-stride: ends
+        const int64_t col = wd / g.rowWords;
+        occ[wd] = vox_scan_word(cross + col * g.rowWords, wd - col * g.rowWords, g);      // its loop: at most rowWords - 1 rounds
+    }
+}
+
+// count: the wave's popcounts in one atomic. The shuffles come after the loop, where every lane of the wave arrives.
+__global__ __launch_bounds__(VX_THREADS) void vox_pack(const uint64_t *__restrict__ occ, uint32_t *__restrict__ table, const vox_grid g, int64_t nTable,
+                                                       unsigned long long *__restrict__ count)
+{
+    unsigned long long mine = 0;
+    for (int64_t o = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; o < nTable; o += (int64_t)gridDim.x * VX_THREADS) {        // grid-stride: ends
+        const uint32_t w = vox_table_word(occ, o, g);            // its loop: at most 32 rounds
+        table[o] = w;
+        mine += (unsigned)__popc(w);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mine += __shfl_xor(mine, s);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
+}
+
+// one lane per table word: 32 bytes of the mask
+__global__ __launch_bounds__(VX_THREADS) void vox_expand(const uint32_t *__restrict__ table, uint8_t *__restrict__ mask, int64_t nTable, int64_t nVoxels)
+{
+    for (int64_t o = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; o < nTable; o += (int64_t)gridDim.x * VX_THREADS) {        // grid-stride: ends
+        const uint32_t w = table[o];
+        const int64_t left = nVoxels - 32 * o;
+        if (left >= 32) {
+            uint32_t b[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+                b[q] = ((w >> (31 - 4 * q)) & 1u) | (((w >> (30 - 4 * q)) & 1u) << 8) | (((w >> (29 - 4 * q)) & 1u) << 16) | (((w >> (28 - 4 * q)) & 1u) << 24);
+            uint4 *dst = (uint4 *)(mask + 32 * o);               // 32-byte aligned: the base comes from hipMalloc
+            dst[0] = make_uint4(b[0], b[1], b[2], b[3]);
+            dst[1] = make_uint4(b[4], b[5], b[6], b[7]);
+        } else {
+            for (int q = 0; q < (int)left; q++) mask[32 * o + q] = (uint8_t)((w >> (31 - q)) & 1u);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- points ----------------------------------------------------------------
+
+__global__ __launch_bounds__(VX_THREADS) void pts_count(const uint32_t *__restrict__ table, int64_t *__restrict__ cnt, int64_t nTable, int64_t nVoxels)
+{
+    for (int64_t o = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; o < nTable; o += (int64_t)gridDim.x * VX_THREADS)         // grid-stride: ends
+        cnt[o] = __popc(table[o] & vox_table_valid(o, nVoxels));
+}
+
+struct pts_args { int64_t gx, gy, nVoxels; double min[3], unit[3]; };
+
+__global__ __launch_bounds__(VX_THREADS) void pts_write(const uint32_t *__restrict__ table, const int64_t *__restrict__ ends, float *__restrict__ points,
+                                                        int64_t nTable, const pts_args a)
+{
+    for (int64_t o = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; o < nTable; o += (int64_t)gridDim.x * VX_THREADS) {        // grid-stride: ends
+        uint32_t r = __brev(table[o] & vox_table_valid(o, a.nVoxels));      // bit b = index 32 o + b
+        int64_t at = o ? ends[o - 1] : 0;
+        while (r) {                                              // ends: every round clears a bit
+            const int b = __ffs((int)r) - 1;
+            r &= r - 1;
+            const int64_t idx = 32 * o + b;
+            const int64_t row = idx / a.gx;
+            const int64_t i = idx - row * a.gx, k = row / a.gy, j = row - k * a.gy;
+            points[3 * at] = vox_centre(a.min[0], a.unit[0], i);
+            points[3 * at + 1] = vox_centre(a.min[1], a.unit[1], j);
+            points[3 * at + 2] = vox_centre(a.min[2], a.unit[2], k);
+            at++;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- CT value mapping ----------------------------------------------------------------
+
+// hu arrives as the bits of its float32 values, the table as keys (map_key): no float comparison is made on the device
+template <bool LDS>
+__global__ __launch_bounds__(VX_THREADS) void map_values(const uint32_t *__restrict__ hu, const uint8_t *__restrict__ sel, const uint32_t *__restrict__ keys, int nU,
+                                                         uint32_t *__restrict__ out, int64_t N)
+{
+    __shared__ uint32_t tab[LDS ? MAP_LDS_ROWS : 1];
+    if (LDS) {
+        for (int q = threadIdx.x; q < nU; q += VX_THREADS) tab[q] = keys[q];
+        __syncthreads();
+    }
+    const uint32_t *t = LDS ? tab : keys;
+    const int64_t n4 = N >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * VX_THREADS + threadIdx.x; q < n4; q += (int64_t)gridDim.x * VX_THREADS) {            // grid-stride: ends
+        const uint4 h = ((const uint4 *)hu)[q];
+        const uint32_t s = ((const uint32_t *)sel)[q];
+        uint4 r;
+        r.x = (s & 0xFFu) ? map_lookup(t, nU, h.x) : 0u;
+        r.y = (s & 0xFF00u) ? map_lookup(t, nU, h.y) : 0u;
+        r.z = (s & 0xFF0000u) ? map_lookup(t, nU, h.z) : 0u;
+        r.w = (s & 0xFF000000u) ? map_lookup(t, nU, h.w) : 0u;
+        ((uint4 *)out)[q] = r;
+    }
+    const int64_t v = 4 * n4 + (int64_t)blockIdx.x * VX_THREADS + threadIdx.x;      // the last N % 4 voxels
+    if (v < N) out[v] = sel[v] ? map_lookup(t, nU, hu[v]) : 0u;
+}
+
+bool overlap(const void *p, size_t pb, const void *q, size_t qb)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qb && b < a + pb;
+}
+
+int pick_device(const char *who, int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, std::string(who) + ": no HIP device available (no CPU fallback)");
+    if (device < 0 || device >= ndev) BFD_FAIL(-3, std::string(who) + ": device ordinal out of range");
+    BFD_HIP(hipSetDevice(device));
+    return 0;
+}
+
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+    hipError_t create() { hipError_t e = hipEventCreate(&e0); return e == hipSuccess ? hipEventCreate(&e1) : e; }
+};
+
+// the grid is usable: every extent in 1 .. 2^31 - 1 and at most VOX_MAX_VOXELS voxels, the product formed without overflow
+bool grid_fits(int64_t gx, int64_t gy, int64_t gz)
+{
+    const int64_t LIMIT = ((int64_t)1 << 31) - 1;
+    if (gx < 1 || gy < 1 || gz < 1 || gx > LIMIT || gy > LIMIT || gz > LIMIT) return false;
+    if (gx > VOX_MAX_VOXELS / gy) return false;
+    return gx * gy <= VOX_MAX_VOXELS / gz;
+}
+
+}  // namespace
+
+extern "C" int bfd_voxelize_mesh(int device, const float *triangles, int64_t nTriangles, const double *min, const double *max,
+                                 int64_t gx, int64_t gy, int64_t gz, uint32_t *table, uint8_t *mask, int64_t *count, float *kernelMs)
+{
+    static const char *who = "bfd_voxelize_mesh";
+    // every argument error is reported before a device is looked for
+    if (!triangles || !min || !max) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (!table && !mask && !count) BFD_FAIL(-1, std::string(who) + ": no output asked for");
+    if (nTriangles < 1) BFD_FAIL(-1, std::string(who) + ": at least one triangle is needed");
+    if (nTriangles >= ((int64_t)1 << 31)) BFD_FAIL(-1, std::string(who) + ": 2^31 triangles or more");
+    if (gx < 1 || gy < 1 || gz < 1) BFD_FAIL(-1, std::string(who) + ": every grid extent must be at least 1");
+    if (!grid_fits(gx, gy, gz)) BFD_FAIL(-1, std::string(who) + ": the grid has an extent of 2^31 or more, or more than 2^40 voxels");
+    for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(min[a]) || !std::isfinite(max[a])) BFD_FAIL(-1, std::string(who) + ": the box is not finite");
+        if (!(max[a] > min[a])) BFD_FAIL(-1, std::string(who) + ": the box must have max > min on every axis");
+    }
+    const vox_grid g = vox_make_grid(min, max, gx, gy, gz);
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(g.u[a]) || !(g.u[a] > 0)) BFD_FAIL(-1, std::string(who) + ": the voxel size (max - min) / g is not a positive finite number");
+    if (mask && g.nVoxels >= ((int64_t)1 << 31)) BFD_FAIL(-1, std::string(who) + ": a mask is written only below 2^31 voxels (ask for the table)");
+    for (int64_t q = 0; q < 9 * nTriangles; q++)
+        if (!std::isfinite(triangles[q])) BFD_FAIL(-1, std::string(who) + ": vertex coordinate " + std::to_string(q) + " is not finite");
+    const int64_t nTable = (g.nVoxels + 31) / 32;
+    const size_t tb = (size_t)nTable * 4, mb = (size_t)g.nVoxels;
+    if ((table && overlap(table, tb, triangles, (size_t)nTriangles * 36)) || (mask && overlap(mask, mb, triangles, (size_t)nTriangles * 36)) ||
+        (table && mask && overlap(table, tb, mask, mb)))
+        BFD_FAIL(-1, std::string(who) + ": an output may not alias the triangles or another output");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+
+    const int64_t n = nTriangles, nWords = g.nColumns * g.rowWords;
+    DevTemp<float> dtri;
+    DevTemp<vox_tri> recs;
+    DevTemp<int64_t> ends;
+    DevTemp<uint64_t> cross, occ;
+    DevTemp<uint32_t> dtable;
+    DevTemp<uint8_t> dmask;
+    DevTemp<unsigned long long> dcount;
+    DevTemp<char> work;
+    EventPair ev;
+    size_t wbytes = 0;
+    unsigned long long total = 0;
+    hipError_t e = dtri.alloc((size_t)n * 9);
+    if (e == hipSuccess) e = recs.alloc((size_t)n);
+    if (e == hipSuccess) e = ends.alloc((size_t)n);
+    if (e == hipSuccess) e = cross.alloc((size_t)nWords);
+    if (e == hipSuccess) e = occ.alloc((size_t)nWords);
+    if (e == hipSuccess) e = dtable.alloc((size_t)nTable);
+    if (e == hipSuccess && mask) e = dmask.alloc(mb);
+    if (e == hipSuccess) e = dcount.alloc(1);
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, ends.p, ends.p, (size_t)n, rocprim::plus<int64_t>(), (hipStream_t)0);
+    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
+    if (e == hipSuccess) e = hipMemcpy(dtri, triangles, (size_t)n * 36, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(cross, 0, (size_t)nWords * 8, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(dcount, 0, 8, 0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(vox_setup, dim3(blocks_for(n, VX_THREADS)), dim3(VX_THREADS), 0, 0, dtri.p, n, g, recs.p, ends.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, ends.p, ends.p, (size_t)n, rocprim::plus<int64_t>(), (hipStream_t)0);
+    if (e == hipSuccess) {
+        // the pair count stays on the device: the launch is sized by its bound n gy gz, the kernel reads the count itself
+        const int64_t bound = n > VOX_SWEEP_BLOCKS * VX_THREADS / g.nColumns ? VOX_SWEEP_BLOCKS * VX_THREADS : n * g.nColumns;
+        hipLaunchKernelGGL(vox_crossings, dim3(blocks_for(bound, VX_THREADS, VOX_SWEEP_BLOCKS)), dim3(VX_THREADS), 0, 0, recs.p, ends.p, n, g,
+                           (unsigned long long *)cross.p);
+        hipLaunchKernelGGL(vox_scan, dim3(blocks_for(nWords, VX_THREADS)), dim3(VX_THREADS), 0, 0, cross.p, occ.p, g, nWords);
+        hipLaunchKernelGGL(vox_pack, dim3(blocks_for(nTable, VX_THREADS)), dim3(VX_THREADS), 0, 0, occ.p, dtable.p, g, nTable, dcount.p);
+        if (mask) hipLaunchKernelGGL(vox_expand, dim3(blocks_for(nTable, VX_THREADS)), dim3(VX_THREADS), 0, 0, dtable.p, dmask.p, nTable, g.nVoxels);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
+    if (e == hipSuccess && table) e = hipMemcpy(table, dtable, tb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mask) e = hipMemcpy(mask, dmask, mb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(&total, dcount, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    if (count) *count = (int64_t)total;
+    return 0;
+}
+
+extern "C" int bfd_voxel_points(int device, const uint32_t *table, int64_t gx, int64_t gy, int64_t gz, const double *min, const double *unit,
+                                float *points, int64_t capacity, int64_t *count, float *kernelMs)
+{
+    static const char *who = "bfd_voxel_points";
+    if (!table || !min || !unit) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (gx < 1 || gy < 1 || gz < 1) BFD_FAIL(-1, std::string(who) + ": every grid extent must be at least 1");
+    if (!grid_fits(gx, gy, gz)) BFD_FAIL(-1, std::string(who) + ": the grid has an extent of 2^31 or more, or more than 2^40 voxels");
+    if (capacity < 0) BFD_FAIL(-1, std::string(who) + ": negative capacity");
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(min[a]) || !std::isfinite(unit[a])) BFD_FAIL(-1, std::string(who) + ": min and unit must be finite");
+    const int64_t nVoxels = gx * gy * gz, nTable = (nVoxels + 31) / 32;
+    // the table is the caller's: its population is known before a device is, and so is whether the points fit
+    int64_t total = 0;
+    for (int64_t o = 0; o < nTable; o++) total += __builtin_popcount(table[o] & vox_table_valid(o, nVoxels));
+    if (count) *count = total;
+    if (capacity < total) BFD_FAIL(-1, std::string(who) + ": the table holds " + std::to_string(total) + " voxels, capacity is " + std::to_string(capacity));
+    if (total > 0 && !points) BFD_FAIL(-1, std::string(who) + ": null points");
+    if (total > 0 && overlap(points, (size_t)total * 12, table, (size_t)nTable * 4)) BFD_FAIL(-1, std::string(who) + ": points may not alias the table");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (total == 0) return 0;
+
+    pts_args a;
+    a.gx = gx; a.gy = gy; a.nVoxels = nVoxels;
+    for (int q = 0; q < 3; q++) { a.min[q] = min[q]; a.unit[q] = unit[q]; }
+    DevTemp<uint32_t> dtable;
+    DevTemp<int64_t> ends;
+    DevTemp<float> dpts;
+    DevTemp<char> work;
+    EventPair ev;
+    size_t wbytes = 0;
+    hipError_t e = dtable.alloc((size_t)nTable);
+    if (e == hipSuccess) e = ends.alloc((size_t)nTable);
+    if (e == hipSuccess) e = dpts.alloc((size_t)total * 3);
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, ends.p, ends.p, (size_t)nTable, rocprim::plus<int64_t>(), (hipStream_t)0);
+    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
+    if (e == hipSuccess) e = hipMemcpy(dtable, table, (size_t)nTable * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+    const unsigned tbk = blocks_for(nTable, VX_THREADS);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pts_count, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, nTable, nVoxels);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, ends.p, ends.p, (size_t)nTable, rocprim::plus<int64_t>(), (hipStream_t)0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pts_write, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, dpts.p, nTable, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
+    if (e == hipSuccess) e = hipMemcpy(points, dpts, (size_t)total * 12, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    return 0;
+}
+
+extern "C" int bfd_map_values3d(int device, const float *hu, const uint8_t *sel, const float *unique, int64_t nU, uint32_t *out, int64_t N,
+                                float *kernelMs)
+{
+    static const char *who = "bfd_map_values3d";
+    if (!hu || !sel || !unique || !out) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (N < 0) BFD_FAIL(-1, std::string(who) + ": negative size");
+    if (nU < 1 || nU > MAP_MAX_ROWS) BFD_FAIL(-1, std::string(who) + ": the table must have 1 .. 65536 rows");
+    if (unique[0] != unique[0]) BFD_FAIL(-1, std::string(who) + ": the table holds a NaN");
+    for (int64_t m = 1; m < nU; m++)
+        if (!(unique[m - 1] < unique[m])) BFD_FAIL(-1, std::string(who) + ": the table must be strictly increasing (row " + std::to_string(m) + " is not above the row before it)");
+    const size_t n = (size_t)N;
+    if (n && (overlap(out, 4 * n, hu, 4 * n) || overlap(out, 4 * n, sel, n) || overlap(out, 4 * n, unique, (size_t)nU * 4)))
+        BFD_FAIL(-1, std::string(who) + ": out may not alias an input");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (n == 0) return 0;
+
+    std::vector<uint32_t> keys((size_t)nU);
+    memcpy(keys.data(), unique, (size_t)nU * 4);
+    for (uint32_t &k : keys) k = map_key(k);
+    DevTemp<uint32_t> dhu, duni, dout;
+    DevTemp<uint8_t> dsel;
+    EventPair ev;
+    hipError_t e = dhu.alloc(n);
+    if (e == hipSuccess) e = dsel.alloc(n);
+    if (e == hipSuccess) e = duni.alloc((size_t)nU);
+    if (e == hipSuccess) e = dout.alloc(n);
+    if (e == hipSuccess) e = hipMemcpy(dhu, hu, 4 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dsel, sel, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(duni, keys.data(), (size_t)nU * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+    if (e == hipSuccess) {
+        // at least one block's worth of lanes for the N % 4 tail; every block stages the table, so no more blocks than keep the device full
+        const unsigned blocks = blocks_for(N / 4, VX_THREADS, 8192);
+        if (nU <= MAP_LDS_ROWS) hipLaunchKernelGGL(map_values<true>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
+        else hipLaunchKernelGGL(map_values<false>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, 4 * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    return 0;
+}

@@ -513,6 +513,56 @@ int bfd_affine_transform3d(int device, int dtype, const void *in, void *out, int
 int bfd_spline_filter3d(int device, int dtype, const void *in, double *out, int64_t N1, int64_t N2, int64_t N3, int order, int mode,
                         float *kernelMs /*may be NULL*/);
 
+/* ---- mesh voxelisation: GPUFunctions.GPUVoxelize.Voxelize (BabelDatasetPreps.py:570, :667, :670, :673; callback installed at CalculateMaskProcess.py) ----
+ * Conventions of bfd_median_filter3d: HOST pointers; returns 0; -1 bad argument (reported before a device is looked for), -3 no such device, -10
+ * device error; text in bfd_last_error; kernelMs (may be NULL): device time of the kernels alone, HIP events; device memory lives for the call and
+ * is freed on every path; no CPU fallback.
+ *
+ * bfd_voxelize_mesh: solid voxelisation of a surface mesh by parity along x. triangles: float32 [n][3][3]; box min[3], max[3]; grid (gx, gy, gz);
+ * u_a = (max_a - min_a) / g_a. All arithmetic is float64, one operation per rounding (no fused multiply-add, no sqrt: the normal is not normalised),
+ * on coordinates relative to min. Voxel (i, j, k) is set iff an ODD number of triangles satisfy (a) and (b):
+ *   (a) the triangle's projection onto (y, z) contains the column centre p = ((j + 1/2) u_y, (k + 1/2) u_z). The projection is made counter-clockwise
+ *       by exchanging its second and third vertex when its signed area (b - a) x (c - a) is negative; a triangle of signed area exactly 0 is skipped.
+ *       The edge function of edge a->b is t = (p_y - a_y)(p_z - b_z) - (p_z - a_z)(p_y - b_y), evaluated in that form: the neighbouring triangle, which
+ *       sees the edge as b->a, then gets exactly -t, which keeps a closed mesh watertight. The test passes for t > 0 on all three edges, and for
+ *       t == 0 on an edge that is top-left: b_z < a_z, or b_z == a_z and a_y > b_y (the reference's TopLeftEdge).
+ *   (b) the surface lies at or beyond the voxel centre: floor(xs / u_x - 1/2) >= i, with xs = v0_x - (n_y (p_y - v0_y) + n_z (p_z - v0_z)) / n_x and
+ *       n = (v1 - v0) x (v2 - v1) of the vertices as given. A surface beyond the last voxel counts for every i; one below the first voxel centre,
+ *       or a NaN (n_x == 0 under a zero numerator), for none.
+ *   Only columns inside the triangle's box ceil(min / u - 1/2) .. floor(max / u - 1/2), clamped to the grid, are looked at.
+ * Differences from the reference's voxelize.cpp, on purpose: it truncates toward zero where (b) floors (a surface within half a voxel of the box's low
+ * x face empties voxel 0 there); it takes |t| < 1e-6, an absolute threshold, as "on the edge"; it drops triangles with |n_x| / |n| < 1e-6; it computes
+ * in float32. Outputs, each may be NULL but not all:
+ *   table  uint32 [ceil(gx gy gz / 32)]: one bit per voxel, bit 31 - (index % 32) of word index / 32 with index = i + gx (j + gy k) (the reference's
+ *          packing); the padding bits of the last word are 0
+ *   mask   uint8 [gz][gy][gx] (0 / 1), only below 2^31 voxels
+ *   count  the number of set voxels
+ * The result does not depend on the order of the triangles, nor on which vertex of a triangle comes first (a cyclic rotation), and is the same bits
+ * from run to run: every crossing is one atomic XOR of one bit, and XOR commutes. One atomic per (triangle, column) that passes (a), where the
+ * reference issues one per voxel below the surface. -1: n < 1, g_a < 1 or >= 2^31, more than 2^40 voxels, a non-finite vertex or box, max_a <= min_a,
+ * a voxel size that is not positive and finite, a mask at 2^31 voxels or more, outputs that overlap. float32 denormals among the vertices may be read
+ * as 0. Device memory during the call: 36 + 128 B per triangle, 2 bits per voxel in rows of gx + 1 bits padded to 64 (crossings, occupancy), the table,
+ * the mask when asked for. */
+int bfd_voxelize_mesh(int device, const float *triangles, int64_t nTriangles, const double *min /*[3]*/, const double *max /*[3]*/,
+                      int64_t gx, int64_t gy, int64_t gz, uint32_t *table /*may be NULL*/, uint8_t *mask /*may be NULL*/,
+                      int64_t *count /*may be NULL*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_voxel_points: the centres of the set voxels of a table in bfd_voxelize_mesh's packing (padding bits are ignored), in ascending index
+ * i + gx (j + gy k) -- the same order in every run, where the reference's atomic counter gives another each time. points: float32 [count][3];
+ * coordinate a = (float)(min_a + (idx_a + 0.5) unit_a), formed in float64 and rounded once. count (may be NULL) receives the table's population, which
+ * is taken on the host before a device is looked for: with capacity below it the call returns -1 and count is still written (call with capacity 0 and
+ * points NULL to size the array). Stateless: the table need not come from bfd_voxelize_mesh. Device memory: the table, 8 B per table word, the points. */
+int bfd_voxel_points(int device, const uint32_t *table, int64_t gx, int64_t gy, int64_t gz, const double *min /*[3]*/, const double *unit /*[3]*/,
+                     float *points /*may be NULL when capacity is 0*/, int64_t capacity, int64_t *count /*may be NULL*/, float *kernelMs /*may be NULL*/);
+
+/* ---- CT value mapping: GPUFunctions.GPUMapping.MappingFilter.MapFilter (BabelDatasetPreps.py:1039; host loop :1034-1037) ----
+ * Same conventions. out[v] (uint32) = the row m with unique[m] == hu[v] where sel[v] != 0 and such a row exists, 0 everywhere else -- what the
+ * reference's kernel leaves in its zero-initialised output. == is float32 equality: -0.0 matches +0.0, a NaN in hu matches nothing. unique: float32
+ * [nU], 1 <= nU <= 65536, STRICTLY INCREASING (np.unique output is; checked, a NaN included: -1), searched by bisection; staged in LDS up to 4096 rows.
+ * hu float32 [N], sel uint8 [N], N >= 0 elements in any shape; out may not overlap an input. One pass: 5 B read and 4 B written per element. */
+int bfd_map_values3d(int device, const float *hu, const uint8_t *sel, const float *unique, int64_t nU, uint32_t *out, int64_t N,
+                     float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
