@@ -1236,7 +1236,8 @@ static int setup_compact_state(bfd_sim *s, const TileGrid &G, int count, const s
     return 0;
 }
 
-// a compact state set aside before a rebuild in the middle of a run: the values of the old list into the new one (or, should the new state not be compact, into the full-volume arrays)
+// a compact state set aside before a rebuild in the middle of a run: the values of the old list into the new one (or, should the new state not be compact -- the
+// form was switched off, or no solid run is left and build_tile_lists calls with count 0 -- into the full-volume arrays)
 static int carry_compact_in(bfd_sim *s, int count, const unsigned *oldCells, long oldN, const float *oldComp)
 {
     DevTemp<float> tmp(true);
@@ -1407,9 +1408,19 @@ static int build_tile_lists(bfd_sim *s)
         rc = build_shear_list(s, G, &count, &compact, hostCells);
         if (!rc && compact) rc = setup_compact_state(s, G, count, listsAll);
         if (!rc && carryCompact) rc = carry_compact_in(s, count, oldCells, oldN, oldComp);
+        if (!rc && compact && s->step > 0 && !carryCompact) {
+            // the first solid cells of a run in progress (they may only appear where every field is zero, include/babelfdtd.h): the compact arrays
+            // start at zero. Hosted, they lie in full-volume buffers that an all-fluid engine uses as output scratch (expand_if_collapsed).
+            float *comp[10] = {s->d.cSxx, s->d.cSyy, s->d.cSxy, s->d.cSxz, s->d.cSyz, s->d.cRxx, s->d.cRyy, s->d.cRxy, s->d.cRxz, s->d.cRyz};
+            for (int a = 0; a < 10; a++) BFD_HIP(hipMemsetAsync(comp[a], 0, (size_t)count * sizeof(float), s->stream));
+            BFD_HIP(hipStreamSynchronize(s->stream));
+        }
         if (rc) return rc;
         s->tiles.shearLowEnd = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)G.lowPlanes * (unsigned)s->d.plane) - hostCells.begin();
         s->tiles.shearHighBeg = std::lower_bound(hostCells.begin(), hostCells.end(), (unsigned)G.hiStart * (unsigned)s->d.plane) - hostCells.begin();
+    } else if (carryCompact) {                       // no solid run is left: the full-volume arrays take the old compact values back
+        rc = carry_compact_in(s, 0, oldCells, oldN, oldComp);
+        if (rc) return rc;
     }
     {   // sources of the first / last z-chunk (bfd_set_sources sorted them by voxel)
         std::vector<uint32_t> lin((size_t)s->nSrcVox);

@@ -109,11 +109,18 @@ int bfd_use_private_stream(bfd_sim *sim);
 
 /* MaterialList + QCorrection (BASE:2340,2362) */
 int bfd_set_materials(bfd_sim *sim, const double *matlist, const double *qcorr);
+/* Replacing inputs on a live sim. Every setter may be called again: after bfd_reset, and between two time steps of a run (from then on
+ * the run uses the new input; sources index their table by the absolute step). Between time steps the material of a cell may change only
+ * where the cell's 15 fields and those of its neighbours within 4 cells are all exactly zero (ahead of the wave front): such a cell does
+ * not know its material, and the run equals one that had the new map from step 0. What becomes of non-zero stresses in a cell whose
+ * material changes is undefined (a solid cell that turns fluid loses its shear stresses and memory variables). The same holds for the
+ * cells a reflector mask adds or releases. */
 /* MaterialMap slab (BASE:2339). ghostLow/ghostHigh (0..2): planes readable below k=0 / above
- * k=nk-1 of the view (neighbour slab's cells); missing ghost planes replicate the edge plane. */
+ * k=nk-1 of the view (neighbour slab's cells); missing ghost planes replicate the edge plane.
+ * A new map CLEARS THE REFLECTOR: the mask lives in the ids this call rewrites, so bfd_set_reflector must be called again after it. */
 int bfd_set_material_map(bfd_sim *sim, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3,
                          int32_t ghostLow, int32_t ghostHigh);
-/* ReflectorMask slab (BASE:2365); NULL clears it */
+/* ReflectorMask slab (BASE:2365); NULL clears it. A mask REPLACES the previous one (it is not added to it). Set it after the material map. */
 int bfd_set_reflector(bfd_sim *sim, const uint32_t *mask, int64_t s1, int64_t s2, int64_t s3);
 /* SourceMap/PulseSource/Ox,Oy,Oz (BASE:2342-2349) in compact form: nVox source voxels of this
  * slab, local x-fastest linear index, 0-based PulseSource row, per-voxel weights (NULL = 1),
