@@ -15,7 +15,7 @@ import operator
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
@@ -27,14 +27,7 @@ _OPS = {'erosion': 0, 'dilation': 1, 'closing': 2, 'opening': 3}
 def InitBinaryClosing(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as InitMedianFilter does. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -72,9 +65,7 @@ def _checked(op, input, structure, iterations, output, origin, mask, border_valu
         zero_origin = False
     if not zero_origin:
         raise NotImplementedError('only origin 0 is supported, not %r' % (origin,))
-    a = np.asarray(input)
-    if a.dtype == np.bool_:
-        a = a.view(np.uint8) if a.flags.c_contiguous else a.astype(np.uint8)
+    a = _step1.bool_as_uint8(np.asarray(input))
     if a.dtype != np.uint8:
         raise TypeError('binary morphology takes bool or uint8 masks, not %s' % a.dtype)
     if a.ndim != 3:
@@ -97,14 +88,11 @@ def _checked(op, input, structure, iterations, output, origin, mask, border_valu
 
 def _run(op, a, s, it, border):
     global last_kernel_ms
-    lib = _engine.load_library()
     out = np.empty_like(a)
     ms = C.c_float()
     sh = s.shape if s is not None else (3, 3, 3)
-    rc = lib.bfd_binary_morphology3d(_device, _OPS[op], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2],
-                                     _engine._ptr(s), sh[0], sh[1], sh[2], it, border, C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_binary_morphology3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_binary_morphology3d', _device, _OPS[op], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2],
+                _engine._ptr(s), sh[0], sh[1], sh[2], it, border, C.byref(ms))
     last_kernel_ms = ms.value
     return out.view(np.bool_)
 

@@ -14,7 +14,7 @@ import operator
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
@@ -23,14 +23,7 @@ last_kernel_ms = None
 def InitLabel(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as InitMedianFilter does. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -59,17 +52,14 @@ def _checked(image, background, connectivity):
 def _run(a, c, want_labels=False, want_sizes=False, want_largest=False):
     """(labels or None, n, sizes or None, largest or None)"""
     global last_kernel_ms
-    lib = _engine.load_library()
     labels = np.empty(a.shape, np.int32) if want_labels else None
     largest = np.empty(a.shape, np.uint8) if want_largest else None
     # a component has at least one voxel: the foreground count bounds n, so one call suffices
     sizes = np.zeros(int(np.count_nonzero(a)), np.int64) if want_sizes else None
     n = C.c_int64()
     ms = C.c_float()
-    rc = lib.bfd_label3d(_device, _engine._ptr(a), _engine._ptr(labels), a.shape[0], a.shape[1], a.shape[2], c, C.byref(n),
-                         _engine._ptr(sizes), 0 if sizes is None else sizes.size, _engine._ptr(largest), C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_label3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_label3d', _device, _engine._ptr(a), _engine._ptr(labels), a.shape[0], a.shape[1], a.shape[2], c, C.byref(n),
+                _engine._ptr(sizes), 0 if sizes is None else sizes.size, _engine._ptr(largest), C.byref(ms))
     last_kernel_ms = ms.value
     return (labels, int(n.value), None if sizes is None else sizes[:n.value].copy(), None if largest is None else largest.view(np.bool_))
 

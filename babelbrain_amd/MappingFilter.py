@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
@@ -23,14 +23,7 @@ MAX_ROWS = 65536
 def InitMapFilter(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as InitLabel does. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -62,11 +55,8 @@ def MapFilter(HUMap, SelBone, UniqueHU, GPUBackend=None):
     ignored."""
     global last_kernel_ms
     hu, sel, uni = _checked(HUMap, SelBone, UniqueHU)
-    lib = _engine.load_library()
     out = np.empty(hu.shape, np.uint32)
     ms = C.c_float()
-    rc = lib.bfd_map_values3d(_device, _engine._ptr(hu), _engine._ptr(sel), _engine._ptr(uni), uni.size, _engine._ptr(out), hu.size, C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_map_values3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_map_values3d', _device, _engine._ptr(hu), _engine._ptr(sel), _engine._ptr(uni), uni.size, _engine._ptr(out), hu.size, C.byref(ms))
     last_kernel_ms = ms.value
     return out

@@ -15,7 +15,7 @@ import operator
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
@@ -26,14 +26,7 @@ MAX_SIZE = 7               # per axis, the reference's limit
 def InitMedianFilter(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as RayleighAndBHTE's Init* functions do. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -56,9 +49,7 @@ def _sizes(size):
 
 def _checked(data, size, mode, cval, mask):
     """Everything that can be refused without the library: returns (contiguous array of uint8 or float32, sizes, mode code, cval, mask or None)."""
-    a = np.asarray(data)
-    if a.dtype == np.bool_:
-        a = a.view(np.uint8) if a.flags.c_contiguous else a.astype(np.uint8)
+    a = _step1.bool_as_uint8(np.asarray(data))
     if a.dtype != np.uint8 and a.dtype != np.float32:
         raise TypeError('MedianFilter takes uint8 (or bool) and float32 volumes, not %s' % a.dtype)
     if a.ndim != 3:
@@ -84,13 +75,10 @@ def _checked(data, size, mode, cval, mask):
 
 def _run(a, s, mode, cval, m):
     global last_kernel_ms
-    lib = _engine.load_library()
     out = np.empty_like(a)
     ms = C.c_float()
-    rc = lib.bfd_median_filter3d(_device, 0 if a.dtype == np.uint8 else 1, _engine._ptr(a), _engine._ptr(out), _engine._ptr(m),
-                                 a.shape[0], a.shape[1], a.shape[2], s[0], s[1], s[2], mode, cval, C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_median_filter3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_median_filter3d', _device, 0 if a.dtype == np.uint8 else 1, _engine._ptr(a), _engine._ptr(out), _engine._ptr(m),
+                a.shape[0], a.shape[1], a.shape[2], s[0], s[1], s[2], mode, cval, C.byref(ms))
     last_kernel_ms = ms.value
     return out
 

@@ -18,7 +18,7 @@ import operator
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 from .nifti import SpatialImage
 
 _device = 0
@@ -34,14 +34,7 @@ _LIMIT = 1 << 31
 def InitResample(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as InitMedianFilter does. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -145,13 +138,10 @@ def affine_transform(input, matrix, offset=0.0, output_shape=None, order=3, mode
     last bit of a coordinate. _gathered=True (checks and timing) keeps order 3 off the LDS-staged path; the result has the same bits."""
     global last_kernel_ms, last_prefilter_ms, last_interpolation_ms
     a, m, shape, o, mc, cval = _checked(input, matrix, offset, output_shape, order, mode, cval)
-    lib = _engine.load_library()
     out = np.empty(shape, a.dtype)
     ms = (C.c_float * 2)()
-    rc = lib.bfd_affine_transform3d(_device, _DTYPES[a.dtype], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2],
-                                    shape[0], shape[1], shape[2], _engine._ptr(m), o, mc, cval, (1 if prefilter else 0) | (2 if _gathered else 0), ms)
-    if rc != 0:
-        raise _engine.EngineError('bfd_affine_transform3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_affine_transform3d', _device, _DTYPES[a.dtype], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2],
+                shape[0], shape[1], shape[2], _engine._ptr(m), o, mc, cval, (1 if prefilter else 0) | (2 if _gathered else 0), ms)
     last_prefilter_ms, last_interpolation_ms = ms[0], ms[1]
     last_kernel_ms = ms[0] + ms[1]
     return out
@@ -163,12 +153,9 @@ def spline_filter(input, order=3, mode='mirror'):
     global last_kernel_ms
     a = _volume(input, 'spline_filter')
     o, mc = _order(order), _mode(mode)
-    lib = _engine.load_library()
     out = np.empty(a.shape, np.float64)
     ms = C.c_float()
-    rc = lib.bfd_spline_filter3d(_device, _DTYPES[a.dtype], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2], o, mc, C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_spline_filter3d failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_spline_filter3d', _device, _DTYPES[a.dtype], _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2], o, mc, C.byref(ms))
     last_kernel_ms = ms.value
     return out
 

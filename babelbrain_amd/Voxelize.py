@@ -19,7 +19,7 @@ import operator
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
@@ -29,14 +29,7 @@ DEFAULT_RESOLUTION = 1333 / 500e3 / 6 * 0.75 * 1e3
 def InitVoxelize(DeviceName=None, GPUBackend=None):
     """Selects the HIP device by name substring, as InitLabel does. GPUBackend is accepted and ignored."""
     global _device
-    devs = _engine.list_devices()
-    if not devs:
-        raise _engine.EngineError('no HIP device visible')
-    if DeviceName:
-        for d, name in devs:
-            if DeviceName.lower() in name.lower():
-                _device = d
-                break
+    devs, _device = _step1.pick_device(DeviceName, _device)
     return devs
 
 
@@ -107,16 +100,13 @@ def _run(triangles, bounds, grid, want_table=False, want_mask=False):
     n = g[0] * g[1] * g[2]
     if want_mask and n >= 2 ** 31:
         raise ValueError('a mask is written only below 2^31 voxels; ask for the table')
-    lib = _engine.load_library()
     table = np.empty((n + 31) // 32, np.uint32) if want_table else None
     mask = np.empty((g[2], g[1], g[0]), np.uint8) if want_mask else None
     count = C.c_int64()
     ms = C.c_float()
     lo, hi = np.ascontiguousarray(r[0]), np.ascontiguousarray(r[1])
-    rc = lib.bfd_voxelize_mesh(_device, _engine._ptr(t), t.shape[0], _engine._ptr(lo), _engine._ptr(hi), g[0], g[1], g[2], _engine._ptr(table),
-                               _engine._ptr(mask), C.byref(count), C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_voxelize_mesh failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+    _step1.call('bfd_voxelize_mesh', _device, _engine._ptr(t), t.shape[0], _engine._ptr(lo), _engine._ptr(hi), g[0], g[1], g[2], _engine._ptr(table),
+                _engine._ptr(mask), C.byref(count), C.byref(ms))
     last_kernel_ms = ms.value
     return table, mask, int(count.value)
 
@@ -147,17 +137,18 @@ def voxel_points(table, grid, origin, unit):
     o, u = np.ascontiguousarray(origin, np.float64), np.ascontiguousarray(unit, np.float64)
     if o.shape != (3,) or u.shape != (3,) or not (np.all(np.isfinite(o)) and np.all(np.isfinite(u))):
         raise ValueError('origin and unit are three finite numbers each')
-    lib = _engine.load_library()
     count = C.c_int64()
     ms = C.c_float()
+    args = (_device, _engine._ptr(tb), g[0], g[1], g[2], _engine._ptr(o), _engine._ptr(u))
     # the population is taken on the host, before a device is looked for: the refusal of capacity 0 sizes the array
-    rc = lib.bfd_voxel_points(_device, _engine._ptr(tb), g[0], g[1], g[2], _engine._ptr(o), _engine._ptr(u), None, 0, C.byref(count), None)
+    try:
+        _step1.call('bfd_voxel_points', *args, None, 0, C.byref(count), None)
+    except _engine.EngineError:
+        if count.value == 0:            # an empty table is not refused for its capacity: this is another failure
+            raise
     pts = np.empty((int(count.value), 3), np.float32)
     if pts.shape[0] > 0:
-        rc = lib.bfd_voxel_points(_device, _engine._ptr(tb), g[0], g[1], g[2], _engine._ptr(o), _engine._ptr(u), _engine._ptr(pts), pts.shape[0],
-                                  C.byref(count), C.byref(ms))
-    if rc != 0:
-        raise _engine.EngineError('bfd_voxel_points failed (rc=%d): %s' % (rc, lib.bfd_last_error().decode()))
+        _step1.call('bfd_voxel_points', *args, _engine._ptr(pts), pts.shape[0], C.byref(count), C.byref(ms))
     last_kernel_ms = ms.value
     return pts
 

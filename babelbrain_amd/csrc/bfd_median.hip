@@ -20,6 +20,7 @@
 // Bound: LDS read issue together with the vector ALU (one ds_read and three VALU operations per window element and round); HBM traffic
 // (2-8 B per voxel) and the halo re-reads (through L2) are negligible beside 27-343 LDS reads per voxel and round. DESIGN.md, "Median filter".
 #include "bfd_internal.h"
+#include "bfd_call.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -29,7 +30,7 @@ namespace {
 constexpr int MT_I = 4, MT_J = 4, MT_K = 64;      // output tile: MT_J x MT_K threads, every thread MT_I voxels
 constexpr int MT_THREADS = MT_J * MT_K;
 constexpr int MR_MAX = 3;                         // largest radius (size 7)
-constexpr unsigned MAX_BLOCKS = 1u << 20;         // tiles beyond this are taken by a grid-stride loop
+constexpr long MAX_BLOCKS = 1L << 20;             // tiles beyond this are taken by a grid-stride loop
 
 struct median_args {
     int N1, N2, N3;
@@ -185,37 +186,32 @@ void launch_median(const T *in, T *out, const uint8_t *mask, const median_args &
 extern "C" int bfd_median_filter3d(int device, int dtype, const void *in, void *out, const uint8_t *regionMask,
                                    int64_t N1, int64_t N2, int64_t N3, int s1, int s2, int s3, int mode, double cval, float *kernelMs)
 {
+    static const char *who = "bfd_median_filter3d";
     // every argument error is reported before a device is looked for
-    if (dtype != 0 && dtype != 1) BFD_FAIL(-1, "bfd_median_filter3d: dtype must be 0 (uint8) or 1 (float32)");
-    if (!in || !out) BFD_FAIL(-1, "bfd_median_filter3d: null argument");
-    if (in == out) BFD_FAIL(-1, "bfd_median_filter3d: out may not alias in");
-    if (mode != 0 && mode != 1) BFD_FAIL(-1, "bfd_median_filter3d: mode must be 0 (reflect) or 1 (constant)");
-    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, "bfd_median_filter3d: negative dimension");
+    if (dtype != 0 && dtype != 1) BFD_FAIL(-1, std::string(who) + ": dtype must be 0 (uint8) or 1 (float32)");
+    if (!in || !out) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (in == out) BFD_FAIL(-1, std::string(who) + ": out may not alias in");
+    if (mode != 0 && mode != 1) BFD_FAIL(-1, std::string(who) + ": mode must be 0 (reflect) or 1 (constant)");
+    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
     const int s[3] = {s1, s2, s3};
     const int64_t N[3] = {N1, N2, N3};
     for (int a = 0; a < 3; a++) {
         if (s[a] != 1 && s[a] != 3 && s[a] != 5 && s[a] != 7)
-            BFD_FAIL(-1, "bfd_median_filter3d: every size must be 1, 3, 5 or 7");
+            BFD_FAIL(-1, std::string(who) + ": every size must be 1, 3, 5 or 7");
         if (N[a] < s[a] / 2)
-            BFD_FAIL(-1, "bfd_median_filter3d: axis " + std::to_string(a) + " has " + std::to_string(N[a]) + " elements, fewer than size / 2 = " +
+            BFD_FAIL(-1, std::string(who) + ": axis " + std::to_string(a) + " has " + std::to_string(N[a]) + " elements, fewer than size / 2 = " +
                          std::to_string(s[a] / 2) + ": one reflection would not reach");
     }
-    const int64_t LIMIT = (int64_t)1 << 31;
-    // the product is formed without overflow: each factor is checked against what is left of the limit
-    if (N1 >= LIMIT || N2 >= LIMIT || N3 >= LIMIT || (N2 && N1 > (LIMIT - 1) / N2) || (N3 && N1 * N2 > (LIMIT - 1) / N3))
-        BFD_FAIL(-1, "bfd_median_filter3d: the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
     const size_t n = (size_t)(N1 * N2 * N3);
     const size_t esz = dtype == 0 ? 1 : 4;
-    {   // partial overlap of the two buffers
-        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-        if (a < b + n * esz && b < a + n * esz) BFD_FAIL(-1, "bfd_median_filter3d: out may not alias in");
-    }
+    if (overlap(in, n * esz, out, n * esz)) BFD_FAIL(-1, std::string(who) + ": out may not alias in");      // partial overlap of the two buffers
     median_args p;
     p.N1 = (int)N1; p.N2 = (int)N2; p.N3 = (int)N3;
     p.r1 = s1 / 2; p.r2 = s2 / 2; p.r3 = s3 / 2;
     p.mode = mode;
     if (dtype == 0) {
-        if (!(cval >= 0.0 && cval <= 255.0) || cval != floor(cval)) BFD_FAIL(-1, "bfd_median_filter3d: cval is not a uint8 value");
+        if (!(cval >= 0.0 && cval <= 255.0) || cval != floor(cval)) BFD_FAIL(-1, std::string(who) + ": cval is not a uint8 value");
         p.cvalKey = (unsigned)cval;
     } else {
         const float f = (float)cval;
@@ -227,37 +223,27 @@ extern "C" int bfd_median_filter3d(int device, int dtype, const void *in, void *
     p.nTj = (int)((N2 + MT_J - 1) / MT_J);
     p.nTiles = (long)p.nTk * p.nTj * ((N1 + MT_I - 1) / MT_I);
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, "bfd_median_filter3d: no HIP device available (no CPU fallback)");
-    if (device < 0 || device >= ndev) BFD_FAIL(-3, "bfd_median_filter3d: device ordinal out of range");
-    BFD_HIP(hipSetDevice(device));
+    if (int rc = pick_device(who, device)) return rc;
     if (kernelMs) *kernelMs = 0.f;
     if (n == 0) return 0;
 
-    void *din = nullptr, *dout = nullptr;
-    uint8_t *dmask = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&din, n * esz);
-    if (e == hipSuccess) e = hipMalloc(&dout, n * esz);
-    if (e == hipSuccess && regionMask) e = hipMalloc((void **)&dmask, n);
-    if (e == hipSuccess) e = hipMemcpy(din, in, n * esz, hipMemcpyHostToDevice);
-    if (e == hipSuccess && regionMask) e = hipMemcpy(dmask, regionMask, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, 0);
-    if (e == hipSuccess) {
-        const unsigned blocks = (unsigned)std::min<long>(p.nTiles, (long)MAX_BLOCKS);
-        if (dtype == 0) launch_median<uint8_t>((const uint8_t *)din, (uint8_t *)dout, dmask, p, blocks);
-        else launch_median<uint32_t>((const uint32_t *)din, (uint32_t *)dout, dmask, p, blocks);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, e0, e1);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * esz, hipMemcpyDeviceToHost);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    hipFree(din); hipFree(dout); hipFree(dmask);
-    if (e != hipSuccess) { bfd_set_error(std::string("bfd_median_filter3d: ") + hipGetErrorString(e)); return -10; }
+    DevTemp<char> din, dout;
+    DevTemp<uint8_t> dmask;
+    Events ev;
+    BFD_STEP(din.alloc(n * esz));
+    BFD_STEP(dout.alloc(n * esz));
+    if (regionMask) BFD_STEP(dmask.alloc(n));
+    BFD_STEP(hipMemcpy(din, in, n * esz, hipMemcpyHostToDevice));
+    if (regionMask) BFD_STEP(hipMemcpy(dmask, regionMask, n, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    const unsigned blocks = blocks_for(p.nTiles, 1, MAX_BLOCKS);
+    if (dtype == 0) launch_median<uint8_t>((const uint8_t *)din.p, (uint8_t *)dout.p, dmask, p, blocks);
+    else launch_median<uint32_t>((const uint32_t *)din.p, (uint32_t *)dout.p, dmask, p, blocks);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(hipMemcpy(out, dout, n * esz, hipMemcpyDeviceToHost));
     return 0;
 }

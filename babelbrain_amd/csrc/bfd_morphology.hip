@@ -20,15 +20,15 @@
 // No kernel waits for another workgroup; every loop is bounded, see the comment at each.
 #include <string.h>
 #include "bfd_internal.h"
+#include "bfd_call.h"
+#include "bfd_scan.h"
 #include "bfd_morph_core.h"
-#include <rocprim/device/device_scan.hpp>
 
 namespace {
 
 constexpr int MB_THREADS = 256;
 constexpr int MAX_BOX = 31;
-
-inline unsigned blocks_for(long items, int perBlock) { return (unsigned)std::max<long>(1, std::min<long>((items + perBlock - 1) / perBlock, 1L << 16)); }
+constexpr long MAX_BLOCKS = 1L << 16;             // work beyond this is taken by grid-stride loops
 
 // ---------------------------------------------------------------- morphology kernels ----------------------------------------------------------------
 
@@ -245,34 +245,6 @@ __global__ __launch_bounds__(MB_THREADS) void label_select(const int *__restrict
         out[v] = (b > 0 && labels[v] == b) ? 1 : 0;
 }
 
-// fewer than 2^31 voxels; the product is formed without overflow
-bool volume_fits(int64_t N1, int64_t N2, int64_t N3)
-{
-    const int64_t LIMIT = (int64_t)1 << 31;
-    return !(N1 >= LIMIT || N2 >= LIMIT || N3 >= LIMIT || (N2 && N1 > (LIMIT - 1) / N2) || (N3 && N1 * N2 > (LIMIT - 1) / N3));
-}
-
-bool overlap(const void *p, size_t pb, const void *q, size_t qb)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qb && b < a + pb;
-}
-
-int pick_device(const char *who, int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, std::string(who) + ": no HIP device available (no CPU fallback)");
-    if (device < 0 || device >= ndev) BFD_FAIL(-3, std::string(who) + ": device ordinal out of range");
-    BFD_HIP(hipSetDevice(device));
-    return 0;
-}
-
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-    hipError_t create() { hipError_t e = hipEventCreate(&e0); return e == hipSuccess ? hipEventCreate(&e1) : e; }
-};
-
 }  // namespace
 
 extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3,
@@ -312,45 +284,42 @@ extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, ui
     const long nWords = (long)N1 * N2 * g.nW;
     DevTemp<uint8_t> vol;
     DevTemp<uint64_t> bitsA, bitsB;
-    EventPair ev;
-    hipError_t e = vol.alloc(n);
-    if (e == hipSuccess) e = bitsA.alloc((size_t)nWords);
-    if (e == hipSuccess) e = bitsB.alloc((size_t)nWords);
-    if (e == hipSuccess) e = hipMemcpy(vol, in, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ev.create();
-    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-    if (e == hipSuccess) {
-        uint64_t *src = bitsA, *dst = bitsB;
-        hipLaunchKernelGGL(morph_pack, dim3(blocks_for(nWords, MB_THREADS / 64)), dim3(MB_THREADS), 0, 0, vol.p, src, g, nWords);
-        const unsigned wb = blocks_for(nWords, MB_THREADS);
-        // closing: dilations then erosions; opening: erosions then dilations (scipy: each `iterations` times)
-        const int first = (op == 1 || op == 2) ? 1 : 0, stages = op >= 2 ? 2 : 1;
-        for (int st = 0; st < stages; st++) {
-            const int dilate = st == 0 ? first : 1 - first;
-            const uint64_t fill = borderValue ? ~(uint64_t)0 : 0;
-            for (int it = 0; it < iterations; it++) {
-                if (box) {
-                    for (int axis = 2; axis >= 0; axis--) {
-                        if (s[axis] == 1) continue;
-                        int lo, hi;
-                        morph_box_taps(s[axis], dilate != 0, &lo, &hi);
-                        hipLaunchKernelGGL(morph_box_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, axis, lo, hi, dilate, fill);
-                        std::swap(src, dst);
-                    }
-                } else {
-                    hipLaunchKernelGGL(morph_general_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, taps[dilate], dilate, fill);
+    Events ev;
+    BFD_STEP(vol.alloc(n));
+    BFD_STEP(bitsA.alloc((size_t)nWords));
+    BFD_STEP(bitsB.alloc((size_t)nWords));
+    BFD_STEP(hipMemcpy(vol, in, n, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    uint64_t *src = bitsA, *dst = bitsB;
+    hipLaunchKernelGGL(morph_pack, dim3(blocks_for(nWords, MB_THREADS / 64, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, vol.p, src, g, nWords);
+    const unsigned wb = blocks_for(nWords, MB_THREADS, MAX_BLOCKS);
+    // closing: dilations then erosions; opening: erosions then dilations (scipy: each `iterations` times)
+    const int first = (op == 1 || op == 2) ? 1 : 0, stages = op >= 2 ? 2 : 1;
+    for (int st = 0; st < stages; st++) {
+        const int dilate = st == 0 ? first : 1 - first;
+        const uint64_t fill = borderValue ? ~(uint64_t)0 : 0;
+        for (int it = 0; it < iterations; it++) {
+            if (box) {
+                for (int axis = 2; axis >= 0; axis--) {
+                    if (s[axis] == 1) continue;
+                    int lo, hi;
+                    morph_box_taps(s[axis], dilate != 0, &lo, &hi);
+                    hipLaunchKernelGGL(morph_box_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, axis, lo, hi, dilate, fill);
                     std::swap(src, dst);
                 }
+            } else {
+                hipLaunchKernelGGL(morph_general_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, taps[dilate], dilate, fill);
+                std::swap(src, dst);
             }
         }
-        hipLaunchKernelGGL(morph_unpack, dim3(blocks_for((long)n, MB_THREADS)), dim3(MB_THREADS), 0, 0, src, vol.p, g, (long)n);
-        e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
-    if (e == hipSuccess) e = hipMemcpy(out, vol, n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    hipLaunchKernelGGL(morph_unpack, dim3(blocks_for((long)n, MB_THREADS, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, src, vol.p, g, (long)n);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(hipMemcpy(out, vol, n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -382,60 +351,51 @@ extern "C" int bfd_label3d(int device, const uint8_t *in, int32_t *labels, int64
 
     DevTemp<uint8_t> vol;                             // the input; afterwards the mask of the largest component
     DevTemp<int> L, rank, best;
-    DevTemp<char> work;
+    InclusiveSum<int> sum;
     DevTemp<unsigned long long> dsz;
-    EventPair ev;
-    size_t wbytes = 0;
+    Events ev;
     int nl = 0;
     float ms = 0.f, ms2 = 0.f;
-    hipError_t e = vol.alloc(n);
-    if (e == hipSuccess) e = L.alloc(n);
-    if (e == hipSuccess) e = rank.alloc(n);
-    if (e == hipSuccess) e = best.alloc(1);
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, rank.p, rank.p, n, rocprim::plus<int>(), (hipStream_t)0);
-    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
-    if (e == hipSuccess) e = hipMemcpy(vol, in, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ev.create();
-    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-    const unsigned vb = blocks_for(nv, MB_THREADS);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(label_local, dim3(blocks_for(g.nTiles, 1)), dim3(MB_THREADS), 0, 0, vol.p, L.p, g);
-        hipLaunchKernelGGL(label_merge, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, g, nv);
-        hipLaunchKernelGGL(label_flatten, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, rank.p, rank.p, n, rocprim::plus<int>(), (hipStream_t)0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(label_assign, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev.e0, ev.e1);
+    BFD_STEP(vol.alloc(n));
+    BFD_STEP(L.alloc(n));
+    BFD_STEP(rank.alloc(n));
+    BFD_STEP(best.alloc(1));
+    BFD_STEP(sum.reserve(rank, n));
+    BFD_STEP(hipMemcpy(vol, in, n, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    const unsigned vb = blocks_for(nv, MB_THREADS, MAX_BLOCKS);
+    hipLaunchKernelGGL(label_local, dim3(blocks_for(g.nTiles, 1, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, vol.p, L.p, g);
+    hipLaunchKernelGGL(label_merge, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, g, nv);
+    hipLaunchKernelGGL(label_flatten, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(sum.run(rank, n));
+    hipLaunchKernelGGL(label_assign, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(&ms, 0, 1));
     // the number of components sizes the histogram: the one value the host needs between the kernels
-    if (e == hipSuccess) e = hipMemcpy(&nl, rank.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && wantSizes && nl > 0) {
-        e = dsz.alloc((size_t)nl);
-        if (e == hipSuccess) e = hipMemset(dsz, 0, (size_t)nl * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(label_sizes, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, dsz.p, nv);
-            if (largest) {
-                hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, dsz.p, nl, best.p);
-                hipLaunchKernelGGL(label_select, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, best.p, vol.p, nv);
-            }
-            e = hipGetLastError();
+    BFD_STEP(hipMemcpy(&nl, rank.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost));
+    if (wantSizes && nl > 0) {
+        BFD_STEP(dsz.alloc((size_t)nl));
+        BFD_STEP(hipMemset(dsz, 0, (size_t)nl * sizeof(unsigned long long)));
+        BFD_STEP(ev.record(0));
+        hipLaunchKernelGGL(label_sizes, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, dsz.p, nv);
+        if (largest) {
+            hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, dsz.p, nl, best.p);
+            hipLaunchKernelGGL(label_select, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, best.p, vol.p, nv);
         }
-        if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-        if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms2, ev.e0, ev.e1);
-        if (e == hipSuccess && sizes && sizesCapacity >= nl) e = hipMemcpy(sizes, dsz, (size_t)nl * sizeof(int64_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && largest) e = hipMemcpy(largest, vol, n, hipMemcpyDeviceToHost);
-    } else if (e == hipSuccess && largest) {
+        BFD_STEP(hipGetLastError());
+        BFD_STEP(ev.record(1));
+        BFD_STEP(ev.sync(1));
+        BFD_STEP(ev.elapsed(&ms2, 0, 1));
+        if (sizes && sizesCapacity >= nl) BFD_STEP(hipMemcpy(sizes, dsz, (size_t)nl * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (largest) BFD_STEP(hipMemcpy(largest, vol, n, hipMemcpyDeviceToHost));
+    } else if (largest) {
         memset(largest, 0, n);                        // no component: an all-zero mask
     }
-    if (e == hipSuccess && labels) e = hipMemcpy(labels, L, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    if (labels) BFD_STEP(hipMemcpy(labels, L, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (numLabels) *numLabels = nl;
     if (kernelMs) *kernelMs = ms + ms2;
     return 0;

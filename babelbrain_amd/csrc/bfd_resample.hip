@@ -18,6 +18,7 @@
 //     Same arithmetic, same bits. Larger boxes, and voxels whose taps leave the box, gather.
 // DESIGN.md, "Resampling".
 #include "bfd_internal.h"
+#include "bfd_call.h"
 #include "bfd_resample_core.h"
 #include <math.h>
 #include <string.h>
@@ -25,7 +26,7 @@
 
 namespace {
 
-constexpr unsigned MAX_BLOCKS = 1u << 20;         // work beyond this is taken by grid-stride loops
+constexpr long MAX_BLOCKS = 1L << 20;             // work beyond this is taken by grid-stride loops
 constexpr int PK_LINES = 64, PK_COLS = 32;        // axis-2 prefilter: lines per block (one per lane) and columns per LDS tile
 constexpr int IT_K = 64, IT_J = 4;                // interpolation: threads along k and j
 
@@ -175,12 +176,12 @@ void launch_interp(const void *coef, void *out, const rs_geom &g, int order, boo
 {
     if (order == 3 && !gathered) {
         const long sTk = (g.O[2] + ST_K - 1) / ST_K, sTj = (g.O[1] + ST_J - 1) / ST_J, sTiles = sTk * sTj * ((g.O[0] + ST_I - 1) / ST_I);
-        hipLaunchKernelGGL((interp3d_staged<TIn, TOut>), dim3((unsigned)std::min<long>(sTiles, (long)MAX_BLOCKS)), dim3(ST_J * ST_K), 0, 0,
+        hipLaunchKernelGGL((interp3d_staged<TIn, TOut>), dim3(blocks_for(sTiles, 1, MAX_BLOCKS)), dim3(ST_J * ST_K), 0, 0,
                            (const TIn *)coef, (TOut *)out, g, sTk, sTj, sTiles);
         return;
     }
     const long nTk = (g.O[2] + IT_K - 1) / IT_K, nTj = (g.O[1] + IT_J - 1) / IT_J, nTiles = nTk * nTj * g.O[0];
-    const dim3 grid((unsigned)std::min<long>(nTiles, (long)MAX_BLOCKS)), block(IT_K * IT_J);
+    const dim3 grid(blocks_for(nTiles, 1, MAX_BLOCKS)), block(IT_K * IT_J);
     const TIn *c = (const TIn *)coef;
     TOut *o = (TOut *)out;
     if (order == 0) hipLaunchKernelGGL((interp3d<TIn, TOut, 0>), grid, block, 0, 0, c, o, g, nTk, nTj, nTiles);
@@ -196,79 +197,40 @@ void launch_dtype(bool fromCoef, const void *coef, void *out, const rs_geom &g, 
     else launch_interp<T, T>(coef, out, g, order, gathered);
 }
 
-unsigned blocks_for(long items, int perBlock)
-{
-    return (unsigned)std::max<long>(1, std::min<long>((items + perBlock - 1) / perBlock, (long)MAX_BLOCKS));
-}
-
 // dtype codes of the two entries
 constexpr int DT_U8 = 0, DT_F32 = 1, DT_I16 = 2;       // 3: float64
 size_t dtype_size(int dtype) { return dtype == DT_U8 ? 1 : dtype == DT_I16 ? 2 : dtype == DT_F32 ? 4 : sizeof(double) /* DT_F64 */; }
 
-// fewer than 2^31 voxels, the product formed without overflow
-bool fits(int64_t N1, int64_t N2, int64_t N3)
-{
-    const int64_t LIMIT = (int64_t)1 << 31;
-    return !(N1 >= LIMIT || N2 >= LIMIT || N3 >= LIMIT || (N2 && N1 > (LIMIT - 1) / N2) || (N3 && N1 * N2 > (LIMIT - 1) / N3));
-}
-
-bool overlap(const void *p, size_t np, const void *q, size_t nq)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
-}
-
-// everything the device holds during a call; freed on every path
-struct scoped {
-    void *din = nullptr, *dcoef = nullptr, *dout = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    ~scoped()
-    {
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-        hipFree(din); hipFree(dcoef); hipFree(dout);
-    }
-};
-
-// d.din of any dtype -> float64 [N + 2 npad]
+// in (device, any dtype, [N]) -> out (float64, [N + 2 npad])
 void launch_to_f64(int dtype, const void *in, double *out, const int64_t N[3], int npad)
 {
     const long n1 = (long)N[0], n2 = (long)N[1], n3 = (long)N[2];
-    const dim3 grid(blocks_for((n1 + 2 * npad) * (n2 + 2 * npad) * (n3 + 2 * npad), 256)), block(256);
+    const dim3 grid(blocks_for((n1 + 2 * npad) * (n2 + 2 * npad) * (n3 + 2 * npad), 256, MAX_BLOCKS)), block(256);
     if (dtype == DT_U8) hipLaunchKernelGGL(to_f64_padded<uint8_t>, grid, block, 0, 0, (const uint8_t *)in, out, n1, n2, n3, npad);
     else if (dtype == DT_I16) hipLaunchKernelGGL(to_f64_padded<int16_t>, grid, block, 0, 0, (const int16_t *)in, out, n1, n2, n3, npad);
     else if (dtype == DT_F32) hipLaunchKernelGGL(to_f64_padded<float>, grid, block, 0, 0, (const float *)in, out, n1, n2, n3, npad);
     else hipLaunchKernelGGL(to_f64_padded<double>, grid, block, 0, 0, (const double *)in, out, n1, n2, n3, npad);
 }
 
-// d.din (dtype, [N]) -> d.dcoef (float64, [N + 2 npad]), filtered along the three axes
-hipError_t prefilter_on_device(scoped &d, int dtype, const int64_t N[3], int npad, int order, int mode)
+// in (device, dtype, [N]) -> c (float64, [N + 2 npad]), filtered along the three axes
+hipError_t prefilter_on_device(const void *in, double *c, int dtype, const int64_t N[3], int npad, int order, int mode)
 {
     const long P[3] = {(long)N[0] + 2 * npad, (long)N[1] + 2 * npad, (long)N[2] + 2 * npad};
-    launch_to_f64(dtype, d.din, (double *)d.dcoef, N, npad);
-    double *c = (double *)d.dcoef;
+    launch_to_f64(dtype, in, c, N, npad);
     // axes of length 1 pass through, as in scipy
     if (P[0] > 1) {
         const long lines = P[1] * P[2];
-        hipLaunchKernelGGL(prefilter_strided, dim3(blocks_for(lines, 256)), dim3(256), 0, 0, c, lines, lines, 0L, P[0], P[1] * P[2], rs_make_filter(order, P[0], mode));
+        hipLaunchKernelGGL(prefilter_strided, dim3(blocks_for(lines, 256, MAX_BLOCKS)), dim3(256), 0, 0, c, lines, lines, 0L, P[0], P[1] * P[2], rs_make_filter(order, P[0], mode));
     }
     if (P[1] > 1) {
         const long lines = P[0] * P[2];
-        hipLaunchKernelGGL(prefilter_strided, dim3(blocks_for(lines, 256)), dim3(256), 0, 0, c, lines, P[2], P[1] * P[2], P[1], P[2], rs_make_filter(order, P[1], mode));
+        hipLaunchKernelGGL(prefilter_strided, dim3(blocks_for(lines, 256, MAX_BLOCKS)), dim3(256), 0, 0, c, lines, P[2], P[1] * P[2], P[1], P[2], rs_make_filter(order, P[1], mode));
     }
     if (P[2] > 1) {
         const long lines = P[0] * P[1];
-        hipLaunchKernelGGL(prefilter_k, dim3(blocks_for(lines, PK_LINES)), dim3(PK_LINES), 0, 0, c, lines, P[2], rs_make_filter(order, P[2], mode));
+        hipLaunchKernelGGL(prefilter_k, dim3(blocks_for(lines, PK_LINES, MAX_BLOCKS)), dim3(PK_LINES), 0, 0, c, lines, P[2], rs_make_filter(order, P[2], mode));
     }
     return hipGetLastError();
-}
-
-int pick_device(const char *who, int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, std::string(who) + ": no HIP device available (no CPU fallback)");
-    if (device < 0 || device >= ndev) BFD_FAIL(-3, std::string(who) + ": device ordinal out of range");
-    BFD_HIP(hipSetDevice(device));
-    return 0;
 }
 
 }  // namespace
@@ -285,8 +247,8 @@ extern "C" int bfd_affine_transform3d(int device, int dtype, const void *in, voi
     if (order < 0 || order > 3) BFD_FAIL(-1, std::string(who) + ": order must be 0, 1, 2 or 3");
     if (mode < 0 || mode > 2) BFD_FAIL(-1, std::string(who) + ": mode must be 0 (constant), 1 (nearest) or 2 (mirror)");
     if (N1 < 0 || N2 < 0 || N3 < 0 || O1 < 0 || O2 < 0 || O3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
-    if (!fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the input has 2^31 voxels or more (limit: fewer than 2^31)");
-    if (!fits(O1, O2, O3)) BFD_FAIL(-1, std::string(who) + ": the output has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the input has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (!volume_fits(O1, O2, O3)) BFD_FAIL(-1, std::string(who) + ": the output has 2^31 voxels or more (limit: fewer than 2^31)");
     for (int q = 0; q < 12; q++)
         if (!std::isfinite(matrix[q])) BFD_FAIL(-1, std::string(who) + ": the matrix has an element that is not finite");
     if ((dtype == DT_U8 || dtype == DT_I16) && !std::isfinite(cval)) BFD_FAIL(-1, std::string(who) + ": cval is not finite and the dtype is an integer");
@@ -310,29 +272,28 @@ extern "C" int bfd_affine_transform3d(int device, int dtype, const void *in, voi
     if (kernelMs) kernelMs[0] = kernelMs[1] = 0.f;
     if (nOut == 0) return 0;
 
-    scoped d;
-    hipError_t e = hipMalloc(&d.din, nIn * esz);
-    if (e == hipSuccess) e = hipMalloc(&d.dout, nOut * esz);
-    if (e == hipSuccess && filt) e = hipMalloc(&d.dcoef, (size_t)(g.I[0] * g.I[1] * g.I[2]) * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(d.din, in, nIn * esz, hipMemcpyHostToDevice);
-    for (int q = 0; q < 3 && e == hipSuccess; q++) e = hipEventCreate(&d.ev[q]);
-    if (e == hipSuccess) e = hipEventRecord(d.ev[0], 0);
-    if (e == hipSuccess && filt) e = prefilter_on_device(d, dtype, N, g.npad, order, mode);
-    if (e == hipSuccess) e = hipEventRecord(d.ev[1], 0);
-    if (e == hipSuccess) {
-        const void *src = filt ? d.dcoef : d.din;
-        if (dtype == DT_U8) launch_dtype<uint8_t>(filt, src, d.dout, g, order, gathered);
-        else if (dtype == DT_I16) launch_dtype<int16_t>(filt, src, d.dout, g, order, gathered);
-        else if (dtype == DT_F32) launch_dtype<float>(filt, src, d.dout, g, order, gathered);
-        else launch_dtype<double>(filt, src, d.dout, g, order, gathered);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(d.ev[2], 0);
-    if (e == hipSuccess) e = hipEventSynchronize(d.ev[2]);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(&kernelMs[0], d.ev[0], d.ev[1]);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(&kernelMs[1], d.ev[1], d.ev[2]);
-    if (e == hipSuccess) e = hipMemcpy(out, d.dout, nOut * esz, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    DevTemp<char> din, dout;
+    DevTemp<double> dcoef;
+    Events ev;
+    BFD_STEP(din.alloc(nIn * esz));
+    BFD_STEP(dout.alloc(nOut * esz));
+    if (filt) BFD_STEP(dcoef.alloc((size_t)(g.I[0] * g.I[1] * g.I[2])));
+    BFD_STEP(hipMemcpy(din, in, nIn * esz, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create(3));
+    BFD_STEP(ev.record(0));
+    if (filt) BFD_STEP(prefilter_on_device(din, dcoef, dtype, N, g.npad, order, mode));
+    BFD_STEP(ev.record(1));
+    const void *src = filt ? (const void *)dcoef.p : (const void *)din.p;
+    if (dtype == DT_U8) launch_dtype<uint8_t>(filt, src, dout, g, order, gathered);
+    else if (dtype == DT_I16) launch_dtype<int16_t>(filt, src, dout, g, order, gathered);
+    else if (dtype == DT_F32) launch_dtype<float>(filt, src, dout, g, order, gathered);
+    else launch_dtype<double>(filt, src, dout, g, order, gathered);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(2));
+    BFD_STEP(ev.sync(2));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(ev.elapsed(kernelMs ? kernelMs + 1 : nullptr, 1, 2));
+    BFD_STEP(hipMemcpy(out, dout, nOut * esz, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -346,7 +307,7 @@ extern "C" int bfd_spline_filter3d(int device, int dtype, const void *in, double
     if (order < 0 || order > 3) BFD_FAIL(-1, std::string(who) + ": order must be 0, 1, 2 or 3");
     if (mode < 0 || mode > 2) BFD_FAIL(-1, std::string(who) + ": mode must be 0 (constant), 1 (nearest) or 2 (mirror)");
     if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
-    if (!fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
     const size_t esz = dtype_size(dtype);
     const size_t n = (size_t)(N1 * N2 * N3);
     if (overlap(in, n * esz, out, n * sizeof(double))) BFD_FAIL(-1, std::string(who) + ": out may not alias in");
@@ -355,24 +316,23 @@ extern "C" int bfd_spline_filter3d(int device, int dtype, const void *in, double
     if (kernelMs) *kernelMs = 0.f;
     if (n == 0) return 0;
 
-    scoped d;
+    DevTemp<char> din;
+    DevTemp<double> dcoef;
+    Events ev;
     const int64_t N[3] = {N1, N2, N3};
-    hipError_t e = hipMalloc(&d.din, n * esz);
-    if (e == hipSuccess) e = hipMalloc(&d.dcoef, n * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(d.din, in, n * esz, hipMemcpyHostToDevice);
-    for (int q = 0; q < 2 && e == hipSuccess; q++) e = hipEventCreate(&d.ev[q]);
-    if (e == hipSuccess) e = hipEventRecord(d.ev[0], 0);
-    if (e == hipSuccess) {
-        if (order > 1) e = prefilter_on_device(d, dtype, N, 0, order, mode);
-        else {                                            // orders 0 and 1 have no poles: the values themselves, as float64
-            launch_to_f64(dtype, d.din, (double *)d.dcoef, N, 0);
-            e = hipGetLastError();
-        }
+    BFD_STEP(din.alloc(n * esz));
+    BFD_STEP(dcoef.alloc(n));
+    BFD_STEP(hipMemcpy(din, in, n * esz, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    if (order > 1) BFD_STEP(prefilter_on_device(din, dcoef, dtype, N, 0, order, mode));
+    else {                                                // orders 0 and 1 have no poles: the values themselves, as float64
+        launch_to_f64(dtype, din, dcoef, N, 0);
+        BFD_STEP(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipEventRecord(d.ev[1], 0);
-    if (e == hipSuccess) e = hipEventSynchronize(d.ev[1]);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, d.ev[0], d.ev[1]);
-    if (e == hipSuccess) e = hipMemcpy(out, d.dcoef, n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(hipMemcpy(out, dcoef, n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }

@@ -32,8 +32,9 @@
 #include <cmath>
 #include <string.h>
 #include "bfd_internal.h"
+#include "bfd_call.h"
+#include "bfd_scan.h"
 #include "bfd_voxelize_core.h"
-#include <rocprim/device/device_scan.hpp>
 
 namespace {
 
@@ -42,11 +43,7 @@ constexpr long VOX_SWEEP_BLOCKS = 4096;                        // pairs per swee
 constexpr int64_t VOX_MAX_VOXELS = (int64_t)1 << 40;
 constexpr int MAP_LDS_ROWS = 4096;                             // 16 KiB of LDS
 constexpr int MAP_MAX_ROWS = 65536;
-
-inline unsigned blocks_for(int64_t items, int perBlock, int64_t cap = 1L << 16)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + perBlock - 1) / perBlock, cap));
-}
+constexpr long MAX_BLOCKS = 1L << 16;                          // work beyond this is taken by grid-stride loops
 
 // ---------------------------------------------------------------- voxelisation kernels ----------------------------------------------------------------
 
@@ -183,27 +180,6 @@ __global__ __launch_bounds__(VX_THREADS) void map_values(const uint32_t *__restr
     if (v < N) out[v] = sel[v] ? map_lookup(t, nU, hu[v]) : 0u;
 }
 
-bool overlap(const void *p, size_t pb, const void *q, size_t qb)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qb && b < a + pb;
-}
-
-int pick_device(const char *who, int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) BFD_FAIL(-3, std::string(who) + ": no HIP device available (no CPU fallback)");
-    if (device < 0 || device >= ndev) BFD_FAIL(-3, std::string(who) + ": device ordinal out of range");
-    BFD_HIP(hipSetDevice(device));
-    return 0;
-}
-
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-    hipError_t create() { hipError_t e = hipEventCreate(&e0); return e == hipSuccess ? hipEventCreate(&e1) : e; }
-};
-
 // the grid is usable: every extent in 1 .. 2^31 - 1 and at most VOX_MAX_VOXELS voxels, the product formed without overflow
 bool grid_fits(int64_t gx, int64_t gy, int64_t gz)
 {
@@ -253,48 +229,43 @@ extern "C" int bfd_voxelize_mesh(int device, const float *triangles, int64_t nTr
     DevTemp<uint32_t> dtable;
     DevTemp<uint8_t> dmask;
     DevTemp<unsigned long long> dcount;
-    DevTemp<char> work;
-    EventPair ev;
-    size_t wbytes = 0;
+    InclusiveSum<int64_t> sum;
+    Events ev;
     unsigned long long total = 0;
-    hipError_t e = dtri.alloc((size_t)n * 9);
-    if (e == hipSuccess) e = recs.alloc((size_t)n);
-    if (e == hipSuccess) e = ends.alloc((size_t)n);
-    if (e == hipSuccess) e = cross.alloc((size_t)nWords);
-    if (e == hipSuccess) e = occ.alloc((size_t)nWords);
-    if (e == hipSuccess) e = dtable.alloc((size_t)nTable);
-    if (e == hipSuccess && mask) e = dmask.alloc(mb);
-    if (e == hipSuccess) e = dcount.alloc(1);
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, ends.p, ends.p, (size_t)n, rocprim::plus<int64_t>(), (hipStream_t)0);
-    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
-    if (e == hipSuccess) e = hipMemcpy(dtri, triangles, (size_t)n * 36, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ev.create();
-    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-    if (e == hipSuccess) e = hipMemsetAsync(cross, 0, (size_t)nWords * 8, 0);
-    if (e == hipSuccess) e = hipMemsetAsync(dcount, 0, 8, 0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(vox_setup, dim3(blocks_for(n, VX_THREADS)), dim3(VX_THREADS), 0, 0, dtri.p, n, g, recs.p, ends.p);
-        e = hipGetLastError();
+    BFD_STEP(dtri.alloc((size_t)n * 9));
+    BFD_STEP(recs.alloc((size_t)n));
+    BFD_STEP(ends.alloc((size_t)n));
+    BFD_STEP(cross.alloc((size_t)nWords));
+    BFD_STEP(occ.alloc((size_t)nWords));
+    BFD_STEP(dtable.alloc((size_t)nTable));
+    if (mask) BFD_STEP(dmask.alloc(mb));
+    BFD_STEP(dcount.alloc(1));
+    BFD_STEP(sum.reserve(ends, (size_t)n));
+    BFD_STEP(hipMemcpy(dtri, triangles, (size_t)n * 36, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    BFD_STEP(hipMemsetAsync(cross, 0, (size_t)nWords * 8, 0));
+    BFD_STEP(hipMemsetAsync(dcount, 0, 8, 0));
+    hipLaunchKernelGGL(vox_setup, dim3(blocks_for(n, VX_THREADS, MAX_BLOCKS)), dim3(VX_THREADS), 0, 0, dtri.p, n, g, recs.p, ends.p);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(sum.run(ends, (size_t)n));
+    // the pair count stays on the device: the launch is sized by its bound n gy gz, the kernel reads the count itself
+    const int64_t bound = n > VOX_SWEEP_BLOCKS * VX_THREADS / g.nColumns ? VOX_SWEEP_BLOCKS * VX_THREADS : n * g.nColumns;
+    hipLaunchKernelGGL(vox_crossings, dim3(blocks_for(bound, VX_THREADS, VOX_SWEEP_BLOCKS)), dim3(VX_THREADS), 0, 0, recs.p, ends.p, n, g,
+                       (unsigned long long *)cross.p);
+    hipLaunchKernelGGL(vox_scan, dim3(blocks_for(nWords, VX_THREADS, MAX_BLOCKS)), dim3(VX_THREADS), 0, 0, cross.p, occ.p, g, nWords);
+    hipLaunchKernelGGL(vox_pack, dim3(blocks_for(nTable, VX_THREADS, MAX_BLOCKS)), dim3(VX_THREADS), 0, 0, occ.p, dtable.p, g, nTable, dcount.p);
+    if (mask) hipLaunchKernelGGL(vox_expand, dim3(blocks_for(nTable, VX_THREADS, MAX_BLOCKS)), dim3(VX_THREADS), 0, 0, dtable.p, dmask.p, nTable, g.nVoxels);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    if (table) BFD_STEP(hipMemcpy(table, dtable, tb, hipMemcpyDeviceToHost));
+    if (mask) BFD_STEP(hipMemcpy(mask, dmask, mb, hipMemcpyDeviceToHost));
+    if (count) {
+        BFD_STEP(hipMemcpy(&total, dcount, 8, hipMemcpyDeviceToHost));
+        *count = (int64_t)total;
     }
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, ends.p, ends.p, (size_t)n, rocprim::plus<int64_t>(), (hipStream_t)0);
-    if (e == hipSuccess) {
-        // the pair count stays on the device: the launch is sized by its bound n gy gz, the kernel reads the count itself
-        const int64_t bound = n > VOX_SWEEP_BLOCKS * VX_THREADS / g.nColumns ? VOX_SWEEP_BLOCKS * VX_THREADS : n * g.nColumns;
-        hipLaunchKernelGGL(vox_crossings, dim3(blocks_for(bound, VX_THREADS, VOX_SWEEP_BLOCKS)), dim3(VX_THREADS), 0, 0, recs.p, ends.p, n, g,
-                           (unsigned long long *)cross.p);
-        hipLaunchKernelGGL(vox_scan, dim3(blocks_for(nWords, VX_THREADS)), dim3(VX_THREADS), 0, 0, cross.p, occ.p, g, nWords);
-        hipLaunchKernelGGL(vox_pack, dim3(blocks_for(nTable, VX_THREADS)), dim3(VX_THREADS), 0, 0, occ.p, dtable.p, g, nTable, dcount.p);
-        if (mask) hipLaunchKernelGGL(vox_expand, dim3(blocks_for(nTable, VX_THREADS)), dim3(VX_THREADS), 0, 0, dtable.p, dmask.p, nTable, g.nVoxels);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
-    if (e == hipSuccess && table) e = hipMemcpy(table, dtable, tb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mask) e = hipMemcpy(mask, dmask, mb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count) e = hipMemcpy(&total, dcount, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
-    if (count) *count = (int64_t)total;
     return 0;
 }
 
@@ -327,32 +298,25 @@ extern "C" int bfd_voxel_points(int device, const uint32_t *table, int64_t gx, i
     DevTemp<uint32_t> dtable;
     DevTemp<int64_t> ends;
     DevTemp<float> dpts;
-    DevTemp<char> work;
-    EventPair ev;
-    size_t wbytes = 0;
-    hipError_t e = dtable.alloc((size_t)nTable);
-    if (e == hipSuccess) e = ends.alloc((size_t)nTable);
-    if (e == hipSuccess) e = dpts.alloc((size_t)total * 3);
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)nullptr, wbytes, ends.p, ends.p, (size_t)nTable, rocprim::plus<int64_t>(), (hipStream_t)0);
-    if (e == hipSuccess) e = work.alloc(std::max<size_t>(wbytes, 1));
-    if (e == hipSuccess) e = hipMemcpy(dtable, table, (size_t)nTable * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ev.create();
-    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-    const unsigned tbk = blocks_for(nTable, VX_THREADS);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pts_count, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, nTable, nVoxels);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = rocprim::inclusive_scan((void *)work.p, wbytes, ends.p, ends.p, (size_t)nTable, rocprim::plus<int64_t>(), (hipStream_t)0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pts_write, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, dpts.p, nTable, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
-    if (e == hipSuccess) e = hipMemcpy(points, dpts, (size_t)total * 12, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    InclusiveSum<int64_t> sum;
+    Events ev;
+    BFD_STEP(dtable.alloc((size_t)nTable));
+    BFD_STEP(ends.alloc((size_t)nTable));
+    BFD_STEP(dpts.alloc((size_t)total * 3));
+    BFD_STEP(sum.reserve(ends, (size_t)nTable));
+    BFD_STEP(hipMemcpy(dtable, table, (size_t)nTable * 4, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    const unsigned tbk = blocks_for(nTable, VX_THREADS, MAX_BLOCKS);
+    hipLaunchKernelGGL(pts_count, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, nTable, nVoxels);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(sum.run(ends, (size_t)nTable));
+    hipLaunchKernelGGL(pts_write, dim3(tbk), dim3(VX_THREADS), 0, 0, dtable.p, ends.p, dpts.p, nTable, a);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(hipMemcpy(points, dpts, (size_t)total * 12, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -379,27 +343,24 @@ extern "C" int bfd_map_values3d(int device, const float *hu, const uint8_t *sel,
     for (uint32_t &k : keys) k = map_key(k);
     DevTemp<uint32_t> dhu, duni, dout;
     DevTemp<uint8_t> dsel;
-    EventPair ev;
-    hipError_t e = dhu.alloc(n);
-    if (e == hipSuccess) e = dsel.alloc(n);
-    if (e == hipSuccess) e = duni.alloc((size_t)nU);
-    if (e == hipSuccess) e = dout.alloc(n);
-    if (e == hipSuccess) e = hipMemcpy(dhu, hu, 4 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dsel, sel, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(duni, keys.data(), (size_t)nU * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ev.create();
-    if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
-    if (e == hipSuccess) {
-        // at least one block's worth of lanes for the N % 4 tail; every block stages the table, so no more blocks than keep the device full
-        const unsigned blocks = blocks_for(N / 4, VX_THREADS, 8192);
-        if (nU <= MAP_LDS_ROWS) hipLaunchKernelGGL(map_values<true>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
-        else hipLaunchKernelGGL(map_values<false>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
-    if (e == hipSuccess && kernelMs) e = hipEventElapsedTime(kernelMs, ev.e0, ev.e1);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, 4 * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { bfd_set_error(std::string(who) + ": " + hipGetErrorString(e)); return -10; }
+    Events ev;
+    BFD_STEP(dhu.alloc(n));
+    BFD_STEP(dsel.alloc(n));
+    BFD_STEP(duni.alloc((size_t)nU));
+    BFD_STEP(dout.alloc(n));
+    BFD_STEP(hipMemcpy(dhu, hu, 4 * n, hipMemcpyHostToDevice));
+    BFD_STEP(hipMemcpy(dsel, sel, n, hipMemcpyHostToDevice));
+    BFD_STEP(hipMemcpy(duni, keys.data(), (size_t)nU * 4, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    BFD_STEP(ev.record(0));
+    // at least one block's worth of lanes for the N % 4 tail; every block stages the table, so no more blocks than keep the device full
+    const unsigned blocks = blocks_for(N / 4, VX_THREADS, 8192);
+    if (nU <= MAP_LDS_ROWS) hipLaunchKernelGGL(map_values<true>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
+    else hipLaunchKernelGGL(map_values<false>, dim3(blocks), dim3(VX_THREADS), 0, 0, dhu.p, dsel.p, duni.p, (int)nU, dout.p, N);
+    BFD_STEP(hipGetLastError());
+    BFD_STEP(ev.record(1));
+    BFD_STEP(ev.sync(1));
+    BFD_STEP(ev.elapsed(kernelMs, 0, 1));
+    BFD_STEP(hipMemcpy(out, dout, 4 * n, hipMemcpyDeviceToHost));
     return 0;
 }

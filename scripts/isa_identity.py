@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of the gfx950 machine code of two builds of babelbrain_amd/csrc (refactor check).
 
-    make -C <tree>/babelbrain_amd/csrc -j16 EXTRA=-Rpass-analysis=kernel-resource-usage > <tree>.log 2>&1     (both trees)
+    make -C <tree>/babelbrain_amd/csrc -O -j16 EXTRA=-Rpass-analysis=kernel-resource-usage > <tree>.log 2>&1     (both trees; -O keeps the
+                                                            remarks of one compiler together: without it parallel compilers tear each other's lines)
     scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log [new=old ...]
 
 new=old (optional, e.g. bfd_outputs=bfd_api): kernels and resource records of object `new` of the second build are looked up under object `old`
@@ -20,7 +21,15 @@ import sys
 import tempfile
 
 LLVM = os.environ.get('LLVM_BIN', '/opt/rocm/lib/llvm/bin')
-SRC = ['bfd_api', 'bfd_outputs', 'bfd_placement', 'bfd_group', 'bfd_kernels_v1', 'bfd_kernels_v2', 'bfd_kernels_fused', 'bfd_rayleigh', 'bfd_bhte', 'bfd_median', 'bfd_morphology']
+
+def sources():
+    """the objects of the library: the SRC := line of csrc/Makefile, so that a new source file is compared from the day it is built"""
+    makefile = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'babelbrain_amd', 'csrc', 'Makefile')
+    line = next(l for l in open(makefile) if re.match(r'^SRC\s*:=', l))
+    return [s[:-len('.hip')] for s in line.split(':=', 1)[1].split()]
+
+
+SRC = sources()
 
 
 def kernels(obj, tmp):

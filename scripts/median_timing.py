@@ -38,7 +38,7 @@ def timed(fn, reps):
         fn()
         wall.append((time.perf_counter() - t0) * 1e3)
         ms.append(MF.last_kernel_ms)
-    return float(np.median(ms)), float(np.median(wall))
+    return float(np.median(ms)), float(np.median(wall)), wall
 
 
 def scipy_rate(a, size, edge):
@@ -74,13 +74,14 @@ def main():
 
     def case(name, vol, size, region=None):
         fn = (lambda: MF.MedianFilter(vol, size)) if region is None else (lambda: MF.median_in_region(vol, region, size))
-        ms, wall = timed(fn, a.reps)
+        ms, wall, walls = timed(fn, a.reps)
         rate = scipy_rate(vol, size, a.scipy_edge) if a.scipy_edge > 0 else None
         line = '%-50s kernel %9.3f ms (%6.3f ns/voxel), call %8.1f ms' % (name, ms, ms * 1e6 / vol.size, wall)
         if rate is not None:
             line += '; scipy on this host, %d^3 corner: %.2f us/voxel = %.0f s for the whole volume (extrapolated)' % (a.scipy_edge, rate, rate * vol.size * 1e-6)
         print(line, flush=True)
-        res['cases'].append({'name': name, 'voxels': int(vol.size), 'kernel_ms': ms, 'call_ms': wall, 'scipy_us_per_voxel_extrapolated': rate})
+        res['cases'].append({'name': name, 'voxels': int(vol.size), 'kernel_ms': ms, 'call_ms': wall, 'call_ms_repetitions': walls,
+                             'scipy_us_per_voxel_extrapolated': rate})
 
     shape = tuple(a.mask_shape)
     for name, top in (('uint8 0/1', 2), ('uint8 labels 0-5', 6), ('uint8 full range', 256)):

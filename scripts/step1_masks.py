@@ -1,7 +1,7 @@
 """Timing record of the device mask clean-up of Step 1 (bfd_binary_morphology3d, bfd_label3d) on a Step-1-sized mask: a synthetic skull shell of
 448 x 448 x 384 uint8 voxels at 0.3675 mm. Every case runs in a process of its own under its own time limit, and the first one that fails ends
 the script. Each prints last_kernel_ms (HIP events around the kernels) and the wall time of the whole call (allocation, copies, kernels), both as
-the median of --reps calls after one warm-up:
+the median of --reps calls after one warm-up (the single calls on a line of their own before it):
   - closing with an all-ones structure of 5, 14 and 27 (the box path; 14 is round(5 mm / 0.3675 mm)); the bytes the passes move over the kernel
     time, as a share of the 8 TB/s peak; the ratio of the kernel times at 27 and 5, which a non-separable path would put near (27 / 5)^3 = 157
   - labelling with 26 neighbours of the closed mask, and of a 30 % random fill
@@ -47,6 +47,7 @@ def timed(fn, module, reps):
         fn()
         wall.append((time.perf_counter() - t0) * 1e3)
         ms.append(module.last_kernel_ms)
+    print(json.dumps({'repetitions': {'kernel_ms': ms, 'call_ms': wall}}), flush=True)
     return float(np.median(ms)), float(np.median(wall))
 
 

@@ -42,7 +42,7 @@ def median3(fn):
     for rep in range(4):                                           # rep 0 warms up
         t0 = time.perf_counter(); ms = fn(); rows.append((ms, (time.perf_counter() - t0) * 1e3))
     k = sorted(r[0] for r in rows[1:]); w = sorted(r[1] for r in rows[1:])
-    return {'kernel_ms_min_median_max': [k[0], k[1], k[2]], 'wall_ms_median': w[1]}
+    return {'kernel_ms_min_median_max': [k[0], k[1], k[2]], 'wall_ms_median': w[1], 'wall_ms_min_max': [w[0], w[2]]}
 
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'counts':
