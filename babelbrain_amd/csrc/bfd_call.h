@@ -1,8 +1,8 @@
-// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip and bfd_voxelize.hip (and by no other
+// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip and bfd_distance.hip (and by no other
 // source: the solver's translation units do not see this file). Host code only.
 //
-// The contract of the eight entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
-// bfd_voxelize_mesh, bfd_voxel_points, bfd_map_values3d). Every entry takes these steps in this order:
+// The contract of the ten entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
+// bfd_voxelize_mesh, bfd_voxel_points, bfd_map_values3d, bfd_distance_transform_edt3d, bfd_gaussian_filter3d). Every entry takes these steps in this order:
 //    1. argument errors: -1 and a text, each before a device is looked for, in the entry's own order
 //    2. pick_device: -3 where no device is visible or the ordinal is out of range
 //    3. kernelMs zeroed (after the device pick)

@@ -570,6 +570,40 @@ int bfd_voxel_points(int device, const uint32_t *table, int64_t gx, int64_t gy, 
 int bfd_map_values3d(int device, const float *hu, const uint8_t *sel, const float *unique, int64_t nU, uint32_t *out, int64_t N,
                      float *kernelMs /*may be NULL*/);
 
+/* ---- exact Euclidean distance transform and Gaussian filter: the scipy.ndimage calls of the bone-rim correction, BabelDatasetPreps.py:936-1017 ----
+ * (:967 ndimage.distance_transform_edt(inv_interior); :984, :986 ndimage.gaussian_filter(volume, sigma=sigma_local) on float32 volumes; the erosion
+ * of :953 is bfd_binary_morphology3d with an all-ones structure.)
+ * Conventions of bfd_median_filter3d: HOST pointers to [N1][N2][N3] volumes in numpy C order (k fastest), fewer than 2^31 voxels; the input is never
+ * written and no output may overlap it; returns 0; -1 bad argument (reported before a device is looked for), -3 no such device, -10 device error;
+ * text in bfd_last_error; kernelMs (may be NULL): device time of the kernels alone, HIP events; on a refusal (-1, -3) the outputs and kernelMs are
+ * untouched; device memory lives for the call and is freed on every path; an empty volume returns 0 after the device pick; no CPU fallback.
+ *
+ * bfd_distance_transform_edt3d: a voxel is BACKGROUND where in == 0, with bit 0 of flags ("invert") where in != 0 (other bits of flags: -1).
+ * dist2[v] (int32, may be NULL) = the smallest squared Euclidean distance, in voxels, from v to a background voxel, as an exact integer (0 at a
+ * background voxel); dist[v] (float64, may be NULL) = its square root, taken on the device: correctly rounded, so dist equals
+ * scipy.ndimage.distance_transform_edt(in) element for element (scipy forms the same integer in float64 and takes one square root). At least one
+ * output must be asked for. Every dimension is at most 16384, so that 3 (N - 1)^2 stays within int32; a volume without any background voxel is
+ * refused (scipy's result there is not a distance): both -1, the second after a host pass over the input. The scheme is separable and works in
+ * integers throughout: nearest background voxel per row from the bit-packed mask, then the lower envelope of parabolas along j and along i with
+ * intersections by integer division. The same bits from run to run. Device memory during the call: the mask (1 B per voxel), its bits (rows padded to 64
+ * voxels), 4 B per voxel for the squared distances and 8 B per voxel of scratch (the stacks of the envelope passes, then the roots). */
+int bfd_distance_transform_edt3d(int device, const uint8_t *in, int flags /*bit 0: invert*/, int32_t *dist2 /*may be NULL*/, double *dist /*may be NULL*/,
+                                 int64_t N1, int64_t N2, int64_t N3, float *kernelMs /*may be NULL*/);
+
+/* bfd_gaussian_filter3d: scipy.ndimage.gaussian_filter(in, sigma, order=0, mode=..., cval=..., truncate=...) with out of in's dtype: 1 float32,
+ * 3 float64 (the codes of bfd_affine_transform3d). sigma: three float64, one per axis. Per axis the host forms scipy's weights in float64: radius
+ * r = int(truncate sigma + 0.5), w(x) = exp(-0.5 / sigma^2 * x^2) for x = -r .. r over their sum (numpy's pairwise sum; exp as numpy takes it on the CPU at hand, so that the
+ * weights are those of scipy on the same machine bit for bit: bfd_distance_core.h, gauss_exp). An axis with sigma <= 1e-15 is
+ * skipped, as scipy skips it; with all three skipped out is a copy of in. r <= 127 per axis; sigma and truncate finite and not negative: otherwise
+ * -1. mode 0 reflect (d c b a | a b c d | d c b a, scipy's default), 1 constant (cval, as float64), 2 nearest, 3 mirror (d c b | a b c d | c b a),
+ * each for any ratio of radius to axis length (an axis of length 1 under radius 12 takes as many reflections as it needs). The axes are filtered in the
+ * order 0, 1, 2; every sum is float64, formed in scipy's order for a symmetric kernel (the centre term, then (x[p - d] + x[p + d]) w[d] from d = r
+ * down to 1) without contraction, and rounded to dtype once per axis, as scipy rounds when it writes its intermediate into the output array.
+ * Device memory during the call: two volumes. */
+int bfd_gaussian_filter3d(int device, int dtype /*1 f32, 3 f64*/, const void *in, void *out, int64_t N1, int64_t N2, int64_t N3,
+                          const double *sigma /*[3]*/, double truncate, int mode /*0 reflect, 1 constant, 2 nearest, 3 mirror*/, double cval,
+                          float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
