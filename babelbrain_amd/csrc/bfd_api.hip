@@ -521,8 +521,9 @@ int bfd_create(const bfd_config *cfg, bfd_sim **out)
     const int P = cfg->NDelta + 1;
     if (cfg->N1 < 2 * P + 4 || cfg->N2 < 2 * P + 4 || cfg->N3 < 2 * P + 4)
         BFD_FAIL(-2, "bfd_create: every dimension must be at least 2*(NDelta+1)+4 voxels");
-    if (cfg->k0 < 0 || cfg->nk < 2 || cfg->k0 + cfg->nk > cfg->N3)
-        BFD_FAIL(-2, "bfd_create: slab [k0,k0+nk) outside the domain or thinner than 2 planes");
+    if (cfg->k0 < 0 || cfg->nk < 0 || cfg->k0 + cfg->nk > cfg->N3) BFD_FAIL(-2, "bfd_create: slab [k0,k0+nk) outside the domain");
+    // the rule of both splitters (slab.partition, partition() in bfd_group.hip): a slab owns the 2 + 2 planes its neighbours read
+    if (cfg->nk < 4) BFD_FAIL(-2, "bfd_create: every slab needs at least 4 planes");
     if (cfg->nMat <= 0 || cfg->nMat > (int)BFD_MAT_MASK) BFD_FAIL(-2, "bfd_create: nMat must be in 1..32767");
     if (cfg->sensorSub <= 0 || cfg->sensorStart < 0 || cfg->nt < 0) BFD_FAIL(-2, "bfd_create: bad sensor sampling / nt");
     if (cfg->typeSource < 0 || cfg->typeSource > 3) BFD_FAIL(-2, "bfd_create: TypeSource must be 0..3");

@@ -264,14 +264,24 @@ class SlabRunner:
 
 
 def create_hip_slab(args, kwargs, rank, world, device, kernelVariant=0, local=None, host_staging=False, rmsFirstStep=0,
-                    placement_search_bytes=None):
+                    placement_search_bytes=None, bounds=None):
     """Build the engine for this rank's slab from the same arguments the reference passes to
     StaggeredFDTD_3D_with_relaxation (BASE:2338-2365). Returns (HipSlab, info).
     local=(N3, k0, nk, gl, gh): the volumes in `args` are already this rank's slab (MaterialMap with
-    gl/gh ghost planes, Ox/Oy/Oz size-1) -- every rank built only its own share."""
+    gl/gh ghost planes, Ox/Oy/Oz size-1) -- every rank built only its own share.
+    bounds=(k0, nk): this rank's slab is planes k0 .. k0+nk-1 of the whole-domain volumes in `args` instead of its share of
+    the balanced partition (an uneven split; every rank's bounds must tile the domain in rank order). Not with local=."""
     MaterialMap, MaterialList, Frequency, SourceMap, PulseSource, SpatialStep, Duration, SensorMap = args
     N1, N2 = MaterialMap.shape[:2]
-    if local is None:
+    if bounds is not None:
+        if local is not None:
+            raise ValueError('bounds= cuts whole-domain volumes; local= volumes follow the balanced partition')
+        N3 = MaterialMap.shape[2]
+        k0, nk = int(bounds[0]), int(bounds[1])
+        if k0 < 0 or k0 + nk > N3 or nk < MIN_PLANES or (rank == 0) != (k0 == 0) or (rank == world - 1) != (k0 + nk == N3):
+            raise ValueError('bounds (%d, %d): rank %d of %d needs a slab of at least %d planes inside the %d planes, the first '
+                             'from plane 0, the last to the end' % (k0, nk, rank, world, MIN_PLANES, N3))
+    elif local is None:
         N3 = MaterialMap.shape[2]
         k0, nk = partition(N3, world)[rank]
     else:

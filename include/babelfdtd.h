@@ -22,7 +22,8 @@
  *  - One bfd_sim owns the Z-slab [k0, k0+nk) of the global N1 x N2 x N3 domain (single GPU:
  *    k0=0, nk=N3). Slabs are advanced half-step by half-step; the two ghost planes on each side
  *    are exchanged by the caller between half-steps (bfd_halo_region gives device pointers), or
- *    are zero at the ends of the domain.
+ *    are zero at the ends of the domain. A slab has at least 4 planes, the 2 + 2 its neighbours
+ *    read: bfd_create refuses a thinner one, as bfd_group_create refuses a split that gives one.
  *  - Selectable maps are a bitmask of BFD_MAP_* (names follow the reference's SelMapsRMSPeakList /
  *    SelMapsSensorsList strings, BabelIntegrationBASE.py:1413-1417, 2355-2356).
  */

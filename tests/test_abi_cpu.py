@@ -61,6 +61,29 @@ def test_engine_refuses_without_gpu(lib):
         _engine.Engine(64, 64, 64, 1, 1e-3, 1e-7, 5e5, 10)
 
 
+@pytest.mark.parametrize('k0,nk', [(0, 3), (30, 2), (61, 3), (20, 0)])
+def test_engine_refuses_a_slab_thinner_than_the_splitters_allow(lib, k0, nk):
+    """One rule in three places: slab.partition, partition() of bfd_group.hip and bfd_create all want 4 planes in a slab. The
+    arguments are checked before a device is looked for, so this holds with and without a GPU."""
+    import ctypes as C
+    from babelbrain_amd import slab
+    assert slab.MIN_PLANES == 4
+
+    def create(k0, nk):
+        cfg = _engine.Config(N1=64, N2=64, N3=64, k0=k0, nk=nk, nMat=1, NDelta=12, typeSource=0, sensorSub=1, sensorStart=0, nt=10,
+                             selRMSorPeak=1, selMapsRMS=_engine.mask_of(['Pressure']), selMapsSensors=_engine.mask_of(['Pressure']),
+                             qfactorCorrection=1, device=0, kernelVariant=0, rmsFirstStep=0, sensorMode=0, h=1e-3, dt=1e-7, freq=5e5,
+                             reflectionLimit=1e-5)
+        handle = C.c_void_p()
+        rc = lib.bfd_create(C.byref(cfg), C.byref(handle))
+        assert not handle
+        return rc, lib.bfd_last_error().decode()
+
+    assert create(k0, nk) == (-2, 'bfd_create: every slab needs at least 4 planes')
+    rc, msg = create(62, 4)
+    assert rc == -2 and 'outside the domain' in msg
+
+
 def test_backend_entry_points_of_the_reference_exist(lib):
     """The names BabelBrain imports from the solver package's tools (BabelBrain.py:429-439, SelFiles.py:245-263)."""
     import babelbrain_amd

@@ -7,20 +7,24 @@ import numpy as np
 import pytest
 
 from babelbrain_amd import PropagationModel, _engine, harness as H
-from tests.util import oracle_dt
+from tests.util import assert_same, compare_runs, geometry_of, oracle_dt
 
 pytestmark = pytest.mark.gpu
 
 
-def _same(out, ref):
+def _same(out, ref, a, k):
+    """every return value of the group call equals the reference's element by element; a failure names the plane, the layer and the material"""
+    geo = geometry_of(a, k)
     assert len(out) == len(ref)
     assert np.array_equal(out[-1]['IndexSensorMap'], ref[-1]['IndexSensorMap'])
     assert np.array_equal(out[0]['time'], ref[0]['time'])
+    sensors = (ref[-1]['IndexSensorMap'], geo[0])
     for q in range(len(ref) - 1):
         assert set(out[q].keys()) == set(ref[q].keys())
         for n in ref[q]:
             assert out[q][n].shape == ref[q][n].shape and out[q][n].dtype == ref[q][n].dtype, (q, n)
-            assert np.array_equal(out[q][n], ref[q][n]), (q, n)
+            if n != 'time':
+                assert_same(out[q][n], ref[q][n], '%s[%s]' % (('sensor', 'last', 'rms', 'peak')[q], n), geo, sensors if q == 0 else None)
 
 
 def _problem(config, N, steps, **kw):
@@ -39,7 +43,7 @@ def test_group_call_equals_single_device_call(config, nslabs, overlap, monkeypat
     ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     pm = PropagationModel(devices=[0] * nslabs)
     out = pm.StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
     assert out[-1]['devices'] == [0] * nslabs and len(out[-1]['slabs']) == nslabs
     assert pm.last_timing['overlapped'] == (overlap == '1') and pm.last_timing['halo_bytes_per_step'] > 0
     # the wave did reach the last slab
@@ -57,12 +61,12 @@ def test_group_through_the_reference_keyword_and_environment(monkeypatch):
     ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, ReturnSensorDFT=True, ReturnSensorSeries=False, **k)
     out = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, DefaultGPUDeviceNumber=[0, 0], ReturnSensorDFT=True,
                                                                ReturnSensorSeries=False, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
     for n in ref[-1]['SensorDFT']:
         assert np.array_equal(out[-1]['SensorDFT'][n], ref[-1]['SensorDFT'][n]) and np.array_equal(out[-1]['SensorPeak'][n], ref[-1]['SensorPeak'][n])
     monkeypatch.setenv('BABELFDTD_DEVICES', '0,0,0')
     out = PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, ReturnSensorDFT=True, ReturnSensorSeries=False, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
     assert len(out[-1]['slabs']) == 3
 
 
@@ -73,7 +77,7 @@ def test_group_on_random_media(seed):
     a, k = random_case(seed)
     ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out = PropagationModel(devices=[0, 0, 0]).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
 
 
 def test_group_c_abi_with_x_fastest_views_and_reset():
@@ -116,7 +120,7 @@ def test_group_halo_planes_through_the_peer_copy_call(monkeypatch):
         monkeypatch.setenv('BFD_GROUP_OVERLAP', overlap)
         monkeypatch.setenv('BFD_GROUP_THREADS', threads)
         out = PropagationModel(devices=[0, 0, 0]).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-        _same(out, ref)
+        _same(out, ref, a, k)
     assert ref[2]['Pressure'][:, :, 64:].max() > 0
 
 
@@ -128,7 +132,7 @@ def test_group_over_distinct_devices():
     a, k, info = _problem('C2', (64, 56, 64 * len(devs)), 250 + 480 * (len(devs) - 1))
     ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out = PropagationModel(devices=devs).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
     assert ref[2]['Pressure'][:, :, out[-1]['slabs'][-1][0]:].max() > 0
     # every interface must have gone device to device: a missing peer path (staged through the host) fails nothing but the curve
     peer = out[-1]['timing']['peer']
@@ -153,5 +157,73 @@ def test_group_slabs_prepared_side_by_side(monkeypatch):
     a, k, info = _problem('C2', (64, 56, 128), 300)
     ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
     out = PropagationModel(devices=[0, 0, 0, 0]).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
-    _same(out, ref)
+    _same(out, ref, a, k)
     assert len(out[-1]['placement']) == 4 and ref[2]['Pressure'].max() > 0
+
+
+# ---- the group at its limits: slabs of 4 to 16 planes, more slabs than the balanced split has been tested with ----------------------------------------
+THIN = {'C2 30 planes over 7': ('C2', (40, 36, 30), 120, 7),        # 5, 5, 4, 4, 4, 4, 4
+        'C2 70 planes over 8': ('C2', (40, 36, 70), 260, 8),
+        'C2 64 planes over 4': ('C2', (64, 56, 64), 260, 4),        # 16-plane slabs: 128^3 over eight devices, scaled down
+        'C3 70 planes over 8': ('C3', (40, 36, 70), 260, 8)}
+_thin = {}
+
+
+def _thin_case(name):
+    """(args, kwargs, slabs, single-device call, oracle) of a case: built and computed once, never modified"""
+    if name not in _thin:
+        from babelbrain_amd import slab
+        from oracle import oracle as O
+        from tests import slab_cuts as SC
+        config, N, steps, n = THIN[name]
+        a, k, _ = H.make_problem(config, N=N, steps=steps, stable_dt_fn=oracle_dt)
+        parts = slab.partition(N[2], n)
+        a, k = SC.tune(a, k, [k0 for k0, _ in parts] + [N[2]])       # every map, three sensor quantities, a reflector box across a cut
+        ref = PropagationModel(device=0).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
+        orc = O.StaggeredFDTD_3D_with_relaxation(*a, **k)
+        assert np.abs(orc[1]['Pressure'][:, :, -1]).max() > 0                # the wave reaches the last plane
+        _thin[name] = (a, k, parts, ref, orc)
+    return _thin[name]
+
+
+def _thin_call(name, monkeypatch, overlap, threads, peer_copy=False):
+    a, k, parts, ref, orc = _thin_case(name)
+    for var, val in (('BFD_GROUP_OVERLAP', overlap), ('BFD_GROUP_THREADS', threads), ('BFD_GROUP_FORCE_PEER_COPY', '1' if peer_copy else None)):
+        if val is None:
+            monkeypatch.delenv(var, raising=False)
+        else:
+            monkeypatch.setenv(var, val)
+    pm = PropagationModel(devices=[0] * len(parts))
+    out = pm.StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
+    assert [tuple(s[:2]) for s in out[-1]['slabs']] == parts
+    # thin slabs take the blocking order unless the overlapped one is forced
+    assert pm.last_timing['overlapped'] == (overlap == '1') and pm.last_timing['halo_bytes_per_step'] > 0
+    _same(out, ref, a, k)
+    compare_runs(out, orc, both=True, geometry=geometry_of(a, k))
+
+
+@pytest.mark.parametrize('threads', ['0', '1'])
+@pytest.mark.parametrize('overlap', [None, '1'])
+@pytest.mark.parametrize('name', sorted(THIN))
+def test_group_of_thin_slabs(name, overlap, threads, monkeypatch):
+    """the drop-in call over slabs of 4 to 16 planes against the single-device call and the oracle: default order and the overlapped one,
+    queued from one host thread and from one per slab"""
+    _thin_call(name, monkeypatch, overlap, threads)
+
+
+@pytest.mark.parametrize('name', sorted(THIN))
+def test_group_of_thin_slabs_through_the_peer_copy_call(name, monkeypatch):
+    _thin_call(name, monkeypatch, '1', '1', peer_copy=True)
+
+
+def test_one_slab_too_many_is_refused_and_the_next_call_works(monkeypatch):
+    """30 planes over 8 slabs: bfd_group_create refuses before anything runs (the drop-in call never asks: it takes N3 // 4 devices at most);
+    the group of 7 then works in the same process"""
+    a, k, parts, ref, orc = _thin_case('C2 30 planes over 7')
+    MaterialMap, ml, f = a[0], a[1], a[2]
+    nt = ref[-1]['nt']
+    with pytest.raises(_engine.EngineError, match='every slab needs at least 4 planes'):
+        _engine.Group([0] * 8, *MaterialMap.shape, len(ml), a[5], k['DT'], f, nt)
+    out = PropagationModel(devices=[0] * 8).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k)
+    assert [tuple(s[:2]) for s in out[-1]['slabs']] == parts and len(parts) == 7
+    _same(out, ref, a, k)

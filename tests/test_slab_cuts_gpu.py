@@ -1,0 +1,150 @@
+"""HIP slab engines at the edges of the Z-split: thin slabs, uneven cuts, cuts inside the absorbing layer (tests/slab_cuts.py has
+the cases; tests/test_slab_cuts_host.py holds the oracle in the same cuts to the oracle). Several slab engines share device 0,
+built by slab.create_hip_slab(bounds=...) and stepped with their halo planes moved by device copies, in SlabRunner's blocking
+and overlapped orders. Every output -- all ten maps as last / RMS / peak, three sensor quantities, IndexSensorMap -- must
+equal the oracle and a single-domain engine element by element.
+
+What the cuts reach in the engine (choose_tile_grid in bfd_api.hip, which the design notes call make_grid): with nk planes in
+a slab, lowPlanes = min(SUB, nk) and hiStart = max(((nk - 2) / SUB) * SUB, lowPlanes) delimit the boundary sub-tiles, which
+form part 1 of a split half-step, take the sources and listed shear cells below srcLowEnd / from srcHighBeg and never go
+quiet. For nk <= SUB low and high boundary are one sub-tile and part 2 is empty; quiet runs exist from nk = 3 SUB."""
+import numpy as np
+import pytest
+
+from tests import slab_cuts as SC
+from tests.util import geometry_of
+
+pytestmark = pytest.mark.gpu
+
+SUB = 8          # depth of a sub-tile in planes: bfd_tile_subz() in choose_tile_grid (bfd_api.hip); held to the library in the quiet-run test
+
+_oracle, _single = {}, {}
+
+
+def _oracle_ref(key, a, k):
+    """the single-domain oracle of a case, computed once and left unchanged"""
+    if key not in _oracle:
+        from oracle import oracle as O
+        _oracle[key] = SC.as_merged(O.StaggeredFDTD_3D_with_relaxation(*a, **k), k)
+    return _oracle[key]
+
+
+def _single_ref(key, a, k, variant=0):
+    """one engine for the whole domain through the drop-in call, once per case and kernel variant"""
+    if (key, variant) not in _single:
+        from babelbrain_amd import PropagationModel
+        _single[(key, variant)] = SC.as_merged(PropagationModel(kernelVariant=variant).StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k), k)
+    return _single[(key, variant)]
+
+
+def _hold(got, key, a, k, what, variant=0):
+    geo = geometry_of(a, k)
+    SC.assert_merged_same(got, _oracle_ref(key, a, k), geo, what + ' against the oracle')
+    SC.assert_merged_same(got, _single_ref(key, a, k, variant), geo, what + ' against one engine')
+
+
+@pytest.mark.parametrize('split', [False, True])
+@pytest.mark.parametrize('medium,cutset', SC.CASES)
+def test_slabs_at_the_cuts(medium, cutset, split):
+    """kernel variant 0, both step orders"""
+    a, k, cuts = SC.problem(medium, cutset)
+    what = '%s cuts %s %s' % (medium, cutset, 'split' if split else 'blocking')
+    ref = _oracle_ref((medium, cutset), a, k)
+    SC.assert_cuts_are_live(ref, a, cuts, what)
+    assert np.abs(ref['LastMap']['Pressure'][:, :, -1]).max() > 0
+    if (medium, cutset) in (('C2', 'A'), ('C2wide', 'A')):
+        assert len(SC.cuts_across_solid(a, cuts)) >= 3
+    got, _ = SC.run_hip_cuts(a, k, cuts, split=split)
+    _hold(got, (medium, cutset), a, k, what)
+
+
+@pytest.mark.parametrize('variant', [1, 2, 3])
+@pytest.mark.parametrize('medium,cutset', [('C2', 'A'), ('C2wide', 'A'), ('C3', 'C3'), ('C1', 'A')])
+def test_other_kernel_variants_at_the_thinnest_cuts(medium, cutset, variant):
+    """the simple (1, which has no parts), dense (2) and class-specialised two-buffer (3) variants in the blocking order"""
+    a, k, cuts = SC.problem(medium, cutset)
+    got, _ = SC.run_hip_cuts(a, k, cuts, variant=variant)
+    _hold(got, (medium, cutset), a, k, '%s cuts %s variant %d' % (medium, cutset, variant), variant)
+
+
+@pytest.mark.parametrize('split', [False, True])
+@pytest.mark.parametrize('seed', sorted(SC.RANDOM_CUTS))
+def test_random_media_in_thin_slabs(seed, split):
+    """solid specks and reflector pockets inside the layer, slabs of 4 to 9 planes"""
+    a, k, cuts = SC.problem('random', seed)
+    got, _ = SC.run_hip_cuts(a, k, cuts, split=split)
+    _hold(got, ('random', seed), a, k, 'random medium %d %s' % (seed, 'split' if split else 'blocking'))
+    assert SC.solid_of(a).any() and np.abs(got['LastMap']['Pressure']).max() > 0
+
+
+@pytest.mark.parametrize('type_source', [0, 1, 2, 3])
+def test_sources_and_sensors_on_cut_planes(type_source):
+    """A source voxel in the last plane of a 4-plane slab (low and high boundary coincide: [srcHighBeg, srcLowEnd) is not empty) and one in
+    the first plane of the next slab, in the split order: a source injected twice, or in neither part, shows at the sensors beside it."""
+    a, k, cuts = SC.cut_plane_problem(type_source)
+    got, _ = SC.run_hip_cuts(a, k, cuts, split=True)
+    _hold(got, ('cut planes', type_source), a, k, 'TypeSource %d' % type_source)
+    z = (got['IndexSensorMap'].astype(np.int64) - 1) // (a[0].shape[0] * a[0].shape[1])
+    for p in (15, 16, 17, 18):
+        assert np.abs(got['Sensor']['Pressure'][z == p]).max() > 0
+
+
+@pytest.mark.parametrize('split', [False, True])
+@pytest.mark.parametrize('medium,cutset', [('C2', 'C'), ('C2q78', 'Q26')])
+def test_quiet_runs_either_side_of_three_sub_tiles(medium, cutset, split, monkeypatch):
+    """Default settings (rmsFirstStep 0, BFD_SKIP_ZERO unset) against one engine in which every run works: slabs of 3 SUB planes and
+    more keep an activity map, thinner ones do not; in a 26-plane slab the last sub-tile holds only the two boundary planes."""
+    from babelbrain_amd import PropagationModel
+    a, k, cuts = SC.problem(medium, cutset)
+    monkeypatch.delenv('BFD_SKIP_ZERO', raising=False)
+    got, act = SC.run_hip_cuts(a, k, cuts, split=split, probe=lambda slabs: [s.eng.activity_counts() for s in slabs])
+    monkeypatch.setenv('BFD_SKIP_ZERO', '0')
+    ref = SC.as_merged(PropagationModel().StaggeredFDTD_3D_with_relaxation(*a, SILENT=True, **k), k)
+    SC.assert_merged_same(got, ref, geometry_of(a, k), '%s cuts %s against one engine without quiet runs' % (medium, cutset))
+    N1, N2 = a[0].shape[:2]
+    solid_planes = SC.solid_of(a).any(axis=(0, 1))
+    for (k0, nk), (active, total) in zip(SC.bounds_of(cuts), act):
+        # quiet_runs_wanted (bfd_api.hip) also wants the solid state compact, which takes a solid cell among the slab's own planes: a slab that
+        # sees bone only in a ghost plane (the last one of the 78-plane grid: bone ends in plane 50, the slab begins at 52) has solid runs, an
+        # empty cell list and no map
+        ghosts_only = not solid_planes[k0:k0 + nk].any() and solid_planes[max(k0 - 2, 0):k0 + nk + 2].any()
+        if ghosts_only:
+            assert (medium, k0) == ('C2q78', 52)           # that one slab only; whether it keeps a map is the library's choice
+        elif nk >= 3 * SUB:
+            assert total == -(-N1 // 64) * -(-N2 // 8) * -(-nk // SUB) and 0 < active <= total, (k0, nk, active, total)
+        else:
+            assert (active, total) == (0, 0), (k0, nk, active, total)
+    assert [nk >= 3 * SUB for _, nk in SC.bounds_of(cuts)] == ([False, True, False] if cutset == 'C' else [True] * 3)
+
+
+VZ_GRID = (264, 56, 100)         # tests/test_vz_advance_gpu.py's grid: x- and y-tiles outside the absorbing layer
+
+
+@pytest.mark.parametrize('cuts,advancing', [([0, 29, 58, 100], [True, True, True]), ([0, 20, 27, 100], [True, True, True]),
+                                            ([0, 19, 26, 100], [False, True, True])])
+def test_advanced_vz_in_uneven_slabs(cuts, advancing, monkeypatch):
+    """Advanced Vz (stress_fluid stores Vz of a run's inner planes kbeg+1 .. kend-3: n - 3 planes of a run of n >= 4, none of a shorter
+    one) in slabs whose runs are shorter than a whole domain's: a run of 5 planes at the end of a 29-plane slab; a 7-plane slab, one run
+    with four inner planes; a 20-plane slab whose only run outside the layer has 4 planes, one of them inner; and a 19-plane slab where
+    that run has 3 planes and the slab falls back to the two-pass update. Engines as bench.py builds them (rmsFirstStep 1: quiet runs
+    keep the two-pass update), against one engine under BFD_ADV_VZ=0; the byte tables show where the advance ran."""
+    from babelbrain_amd import harness as H
+    from tests.util import oracle_dt
+    a, k, _ = H.make_problem('C3', N=VZ_GRID, steps=200, stable_dt_fn=oracle_dt, full_sensors=False)
+    a, k = SC.tune(a, k, cuts)
+    probe = lambda slabs: [s.eng.algorithmic_bytes(False) for s in slabs]
+    monkeypatch.setenv('BFD_ADV_VZ', '0')
+    ref, _ = SC.run_hip_cuts(a, k, [0, VZ_GRID[2]], rms_first_step=1)
+    _, bytes_ref = SC.run_hip_cuts(a, k, cuts, rms_first_step=1, probe=probe)
+    monkeypatch.delenv('BFD_ADV_VZ')
+    for split in (False, True):
+        got, bytes_out = SC.run_hip_cuts(a, k, cuts, split=split, rms_first_step=1, probe=probe)
+        SC.assert_merged_same(got, ref, geometry_of(a, k), 'cuts %s %s' % (cuts, 'split' if split else 'blocking'))
+        for (k0, nk), adv, bo, br in zip(SC.bounds_of(cuts), advancing, bytes_out, bytes_ref):
+            less = br['velocity_fluid'] - bo['velocity_fluid']
+            more = bo['stress_fluid'] - br['stress_fluid']
+            print('slab (%d, %d): velocity_fluid moves %d bytes less, stress_fluid %d more' % (k0, nk, less, more))
+            assert less == 2 * more and (less > 0) == adv, (k0, nk, less, more)
+            assert all(bo[c] == br[c] for c in br if c not in ('velocity_fluid', 'stress_fluid'))
+    vz = ref['LastMap']['Vz']
+    assert all(np.abs(vz[:, :, c - 1:c + 1]).max() > 0 for c in cuts[1:-1])

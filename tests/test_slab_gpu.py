@@ -7,7 +7,7 @@ import pytest
 from babelbrain_amd import harness as H
 from babelbrain_amd import slab
 from babelbrain_amd._engine import HALO_STRESS, HALO_VELOCITY
-from tests.util import oracle_dt
+from tests.util import assert_same, geometry_of, oracle_dt
 
 pytestmark = pytest.mark.gpu
 
@@ -59,12 +59,13 @@ def test_slabs_on_one_gpu_match_single_domain(config, variant, world, split):
     merged = slab.merge_slab_outputs([slab.collect_slab_outputs(s.eng, k, i) for s, i in zip(slabs, infos)])
     Sensor, Last, RMS, Peak, Inp = ref
     assert np.array_equal(merged['IndexSensorMap'], Inp['IndexSensorMap'])
+    geo = geometry_of(a, k)
     for n in ('Pressure', 'Sigmayy'):
-        assert np.array_equal(merged['Sensor'][n], Sensor[n]), n
+        assert_same(merged['Sensor'][n], Sensor[n], 'sensor[%s]' % n, geo, (Inp['IndexSensorMap'], geo[0]))
     for n in RMS:
-        assert np.array_equal(merged['RMS'][n], RMS[n]), n
-        assert np.array_equal(merged['Peak'][n], Peak[n]), n
-        assert np.array_equal(merged['LastMap'][n], Last[n]), n
+        assert_same(merged['RMS'][n], RMS[n], 'rms[%s]' % n, geo)
+        assert_same(merged['Peak'][n], Peak[n], 'peak[%s]' % n, geo)
+        assert_same(merged['LastMap'][n], Last[n], 'last[%s]' % n, geo)
     assert RMS['Pressure'].max() > 0
     for s in slabs:
         s.eng.close()
@@ -93,7 +94,10 @@ def test_collapsed_all_fluid_slabs_with_reduced_halo():
             s.half_step_velocity(2)
     torch.cuda.synchronize()
     merged = slab.merge_slab_outputs([slab.collect_slab_outputs(s.eng, k, i) for s, i in zip(slabs, infos)])
-    assert np.array_equal(merged['Sensor']['Pressure'], ref[0]['Pressure'])
-    assert np.array_equal(merged['RMS']['Pressure'], ref[2]['Pressure']) and ref[2]['Pressure'].max() > 0
+    geo = geometry_of(a, k)
+    assert np.array_equal(merged['IndexSensorMap'], ref[-1]['IndexSensorMap'])
+    assert_same(merged['Sensor']['Pressure'], ref[0]['Pressure'], 'sensor[Pressure]', geo, (ref[-1]['IndexSensorMap'], geo[0]))
+    assert_same(merged['RMS']['Pressure'], ref[2]['Pressure'], 'rms[Pressure]', geo)
+    assert ref[2]['Pressure'].max() > 0
     for s in slabs:
         s.eng.close()
