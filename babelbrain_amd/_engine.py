@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     'bfd_group_get_sensor_index', 'bfd_group_get_sensors', 'bfd_group_get_sensor_dft', 'bfd_group_get_map', 'bfd_group_device_bytes',
     'bfd_group_peer_status', 'bfd_placement_cache_release', 'bfd_median_filter3d', 'bfd_binary_morphology3d', 'bfd_label3d',
     'bfd_affine_transform3d', 'bfd_spline_filter3d', 'bfd_voxelize_mesh', 'bfd_voxel_points', 'bfd_map_values3d',
-    'bfd_distance_transform_edt3d', 'bfd_gaussian_filter3d',
+    'bfd_distance_transform_edt3d', 'bfd_gaussian_filter3d', 'bfd_voxel_scatter3d', 'bfd_voxelize_scatter3d',
 ]
 
 
@@ -208,6 +208,10 @@ def load_library():
                                       C.POINTER(C.c_int64), C.POINTER(C.c_float)]
     lib.bfd_voxel_points.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    lib.bfd_voxel_scatter3d.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_voxelize_scatter3d.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_map_values3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
     lib.bfd_distance_transform_edt3d.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_float)]
     lib.bfd_gaussian_filter3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int,

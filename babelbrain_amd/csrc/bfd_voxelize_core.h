@@ -3,6 +3,8 @@
 //
 // The definition (include/babelfdtd.h, bfd_voxelize_mesh) is evaluated in float64, ONE OPERATION PER ROUNDING, in exactly the order written here:
 // the library is built with -ffp-contract=off, and tests/voxelize_oracle.py performs the same operations in numpy. Do not reassociate.
+// The conformal-mask scatter (bfd_voxel_scatter3d) is float32 under the same rule; its pieces are further down (conf_*), restated in
+// tests/conformal_oracle.py.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -171,6 +173,72 @@ BFD_HD uint32_t vox_table_valid(int64_t o, int64_t nVoxels)
 
 // coordinate of voxel index idx along one axis: float64, rounded once to float32
 BFD_HD float vox_centre(double min, double unit, int64_t idx) { return (float)(min + ((double)idx + 0.5) * unit); }
+
+// Conformal masks (include/babelfdtd.h, bfd_voxel_scatter3d): a point through a float32 [3][4] matrix to a voxel index. Every product and every
+// sum is rounded to float32 on its own, in the order written; tests/conformal_oracle.py performs the same operations in numpy. On the device the
+// intrinsics keep the statement independent of -ffp-contract; a host build needs -ffp-contract=off (x86-64 without -mfma contracts nothing anyway).
+// This build flushes float32 denormals: a flushed operand changes a t by less than 2^-126 and cannot move it across a half-integer.
+BFD_HD float conf_mul(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+BFD_HD float conf_add(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+
+// t = ((m0 x + py) + pz) + m3 of one matrix row m, with py = conf_mul(m1, y) and pz = conf_mul(m2, z) formed by the caller: they are the same for
+// every point of a source row, and a product rounded on its own is the same wherever it is formed
+BFD_HD float conf_row(const float *m, float x, float py, float pz) { return conf_add(conf_add(conf_add(conf_mul(m[0], x), py), pz), m[3]); }
+
+// n = rint(t), half to even (np.round), saturated to the int32 range: t >= 2^31 and +inf give INT32_MAX, t <= -2^31, -inf and NaN give INT32_MIN
+BFD_HD int32_t conf_round(float t)
+{
+    if (!(t > -2147483648.f)) return INT32_MIN;
+    if (t >= 2147483648.f) return INT32_MAX;
+    return (int32_t)rintf(t);
+}
+
+// the index of the three coordinates of a point, in one call
+BFD_HD void conf_point(const float m[3][4], float x, float y, float z, int32_t n[3])
+{
+    for (int a = 0; a < 3; a++) n[a] = conf_round(conf_row(m[a], x, conf_mul(m[a][1], y), conf_mul(m[a][2], z)));
+}
+
+// What becomes of a point with index n in an output volume [M0][M1][M2], numpy's index rules behind the reference's filter of the upper side: the
+// value is the slot of counts[] the point is counted in beside counts[0] (0: none).
+enum { CONF_INSIDE = 0, CONF_ABOVE = 1, CONF_WRAPPED = 2, CONF_BELOW = 3 };
+//   CONF_ABOVE    some n_a >= M_a: dropped (the filter comes first: such a point is dropped whatever its other indices are)
+//   CONF_BELOW    otherwise, some n_a < -M_a: dropped (numpy raises IndexError here)
+//   CONF_WRAPPED  otherwise, some n_a in [-M_a, 0): that index wraps by +M_a
+// *at receives the voxel (i0 M1 + i1) M2 + i2 of a point that is not dropped; the saturated indices of conf_round are dropped on their side for
+// every 1 <= M_a < 2^31.
+BFD_HD int conf_target(const int32_t n[3], const int64_t M[3], int64_t *at)
+{
+    bool above = false, below = false, wrapped = false;
+    for (int a = 0; a < 3; a++) {
+        above |= n[a] >= M[a];
+        below |= n[a] < -M[a];
+        wrapped |= n[a] < 0;
+    }
+    if (above) return CONF_ABOVE;
+    if (below) return CONF_BELOW;
+    int64_t v = 0;
+    for (int a = 0; a < 3; a++) v = v * M[a] + (n[a] < 0 ? n[a] + M[a] : n[a]);
+    *at = v;
+    return wrapped ? CONF_WRAPPED : CONF_INSIDE;
+}
+
+// bit of voxel index idx in a table in bfd_voxelize_mesh's packing
+BFD_HD bool vox_table_bit(const uint32_t *table, int64_t idx) { return (table[idx >> 5] >> (31 - (int)(idx & 31))) & 1u; }
 
 // CT value mapping. Values are compared as order-preserving integer keys of their float32 bits, never as floats: this build flushes float32
 // denormals, and a float comparison might take a denormal for 0. The key keeps float order and float equality: -0.0 gets the key of +0.0.

@@ -563,6 +563,46 @@ int bfd_voxelize_mesh(int device, const float *triangles, int64_t nTriangles, co
 int bfd_voxel_points(int device, const uint32_t *table, int64_t gx, int64_t gy, int64_t gz, const double *min /*[3]*/, const double *unit /*[3]*/,
                      float *points /*may be NULL when capacity is 0*/, int64_t capacity, int64_t *count /*may be NULL*/, float *kernelMs /*may be NULL*/);
 
+/* ---- conformal masks: the scatter of the voxel centres through the rotated affine, BabelDatasetPreps.py:710-759 ----
+ * (per mesh: hstack, np.round(np.dot(InVAffineRot, XYZ)).astype(np.int64), the filter of the upper side :740-743, the fancy-index store.)
+ * Same conventions as bfd_voxelize_mesh. The points never exist on the host: only the mask (1 B per voxel of the simulation grid), the index bounds
+ * and four counts come back.
+ *
+ * Points. The points of a table are those of bfd_voxel_points: one per set voxel, index = i + gx (j + gy k), padding bits ignored; coordinate a of
+ * a point is (float)(min_a + (idx_a + 0.5) unit_a), formed in float64 and rounded once.
+ * Transform. matrix: float32 [3][4], the first three rows of InVAffineRot. Row a of a point (x, y, z) is
+ *     t_a = ((m_a0 x + m_a1 y) + m_a2 z) + m_a3
+ * with every product and every sum rounded to float32 on its own, in exactly this order, no fused multiply-add; n_a = rint(t_a), half to even, as
+ * np.round has it. The build flushes float32 denormals: a flushed operand changes a t_a by less than 2^-126 and cannot move it across a
+ * half-integer. A t_a that is not finite or is at least 2^31 in magnitude saturates: n_a = INT32_MAX for t_a >= 2^31, INT32_MIN for t_a <= -2^31 and
+ * for NaN.
+ * Output. out: uint8 [M1][M2][M3], last axis fastest, written whole with 0 or 1. A point sets voxel (n_0, n_1, n_2) with numpy's index rules behind
+ * the reference's filter:
+ *     a point with any n_a >= M_a is dropped ("above"; the filter comes first, whatever the point's other indices are);
+ *     otherwise a point with any n_a < -M_a is dropped ("below": numpy raises IndexError there; a saturated index is always on its side);
+ *     otherwise an index in [-M_a, 0) wraps by +M_a ("wrapped": the reference filters only the upper side).
+ *   counts  int64 [4] = {points, above, wrapped, below}, each point counted once beside `points`
+ *   lo, hi  int64 [3] each: the minimum and maximum of n_a over all points before any dropping, saturated to the int32 range as above; left
+ *           alone when the table has no point. They come together.
+ * With out == NULL the call is the bounds pass: M1..M3 are ignored and counts[1..3] are 0. At least one of out, lo/hi, counts must be asked for.
+ * An empty table is not an error: out all zero, counts all zero, lo and hi untouched. The result is a set: the same bytes in every run.
+ * tests/conformal_oracle.py restates all of this in numpy with elementwise float32 operations; the device equals it voxel for voxel and number
+ * for number.
+ * -1, in this order: the grid errors of bfd_voxel_points (min and unit finite); a non-finite matrix; M_a < 1 where out is given; an out of 2^31 voxels
+ * or more; an out that overlaps an input; lo without hi; no output asked for. kernelMs brackets the memset of out and the kernel, never a copy.
+ * Device memory: the table, out. */
+int bfd_voxel_scatter3d(int device, const uint32_t *table, int64_t gx, int64_t gy, int64_t gz, const double *min /*[3]*/, const double *unit /*[3]*/,
+                        const float *matrix /*[12]*/, int64_t M1, int64_t M2, int64_t M3, uint8_t *out /*may be NULL*/, int64_t *lo /*may be NULL*/,
+                        int64_t *hi /*may be NULL*/, int64_t *counts /*may be NULL*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_voxelize_scatter3d: bfd_voxelize_mesh's table of the mesh, made on the device and scattered there (unit_a = (max_a - min_a) / g_a): what
+ * bfd_voxelize_mesh -> bfd_voxel_scatter3d gives, without the table or any point leaving the device. -1: the triangle, grid, box and vertex errors
+ * of bfd_voxelize_mesh, then the errors above from the matrix on. kernelMs brackets the voxelisation too. */
+int bfd_voxelize_scatter3d(int device, const float *triangles, int64_t nTriangles, const double *min /*[3]*/, const double *max /*[3]*/,
+                           int64_t gx, int64_t gy, int64_t gz, const float *matrix /*[12]*/, int64_t M1, int64_t M2, int64_t M3,
+                           uint8_t *out /*may be NULL*/, int64_t *lo /*may be NULL*/, int64_t *hi /*may be NULL*/, int64_t *counts /*may be NULL*/,
+                           float *kernelMs /*may be NULL*/);
+
 /* ---- CT value mapping: GPUFunctions.GPUMapping.MappingFilter.MapFilter (BabelDatasetPreps.py:1039; host loop :1034-1037) ----
  * Same conventions. out[v] (uint32) = the row m with unique[m] == hu[v] where sel[v] != 0 and such a row exists, 0 everywhere else -- what the
  * reference's kernel leaves in its zero-initialised output. == is float32 equality: -0.0 matches +0.0, a NaN in hu matches nothing. unique: float32
