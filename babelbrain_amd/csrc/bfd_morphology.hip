@@ -4,6 +4,7 @@
 //     BinaryClosingFilter(fct, structure=np.ones(sf2, int))          BabelDatasetPreps.py:881-883 (scipy.ndimage.binary_closing; sf2 = 14 at 0.3675 mm)
 //     binary_dilation(mask, iterations=6), binary_erosion(mask, iterations=n)     :901, :953, :1106
 //     LabelImage(nfct), regionprops, the largest region              :888-894, :910-929, :1055-1058, :1078-1081
+//     the same with np.isin(label_img, AllLabels) and a masked store :909-929, :1055-1061, :1077-1097 (bfd_paint_components3d: the labels stay here)
 //
 // Morphology. The mask is packed to one bit per voxel along k (__ballot: 64 voxels per wave-wide word; layout in bfd_morph_core.h) and every pass
 // works on whole words, one thread per word:
@@ -17,6 +18,9 @@
 //   3. flatten: every voxel points at its root
 //   4. roots (parent == self) flagged, inclusive prefix sum in raster order (rocPRIM): label of a component = rank of its root, scipy's numbering
 //   5. sizes by one histogram pass (one atomic per wave and distinct label), the largest by a reduction, its mask
+//   Steps 1-5 up to the sizes are `Labelling`, which bfd_label3d and bfd_paint_components3d both run.
+// Painting. A flag per label from the sizes and the largest (paint_flags: all but the largest, the ones below a tenth of it, or the largest alone),
+//   then out = in with the voxels of flagged labels set to the fill value (paint_write): 6 B per voxel, and the int32 labels never reach the host.
 // No kernel waits for another workgroup; every loop is bounded, see the comment at each.
 #include <string.h>
 #include "bfd_internal.h"
@@ -110,8 +114,8 @@ static __device__ __forceinline__ void uf_union(int *L, int a, int b)
 
 struct label_dims { int N1, N2, N3, nTj, nTk; long nTiles; int conn; };
 
-// 1. local union-find of one tile in LDS
-__global__ __launch_bounds__(MB_THREADS) void label_local(const uint8_t *__restrict__ in, int *__restrict__ L, const label_dims g)
+// 1. local union-find of one tile in LDS. The foreground is in != 0, or in == value where value >= 0 (bfd_paint_components3d)
+__global__ __launch_bounds__(MB_THREADS) void label_local(const uint8_t *__restrict__ in, int *__restrict__ L, const label_dims g, const int value)
 {
     __shared__ int lab[LT_VOX];                       // 16 KiB
     for (long t = blockIdx.x; t < g.nTiles; t += gridDim.x) {          // grid-stride over tiles, block-uniform: ends
@@ -122,7 +126,11 @@ __global__ __launch_bounds__(MB_THREADS) void label_local(const uint8_t *__restr
         __syncthreads();                              // the tile before this one has been written out
         for (int v = threadIdx.x; v < LT_VOX; v += MB_THREADS) {
             const int i = i0 + v / (LT_J * LT_K), j = j0 + (v / LT_K) % LT_J, k = k0 + v % LT_K;
-            const bool on = i < g.N1 && j < g.N2 && k < g.N3 && in[((long)i * g.N2 + j) * g.N3 + k] != 0;
+            bool on = i < g.N1 && j < g.N2 && k < g.N3;
+            if (on) {
+                const int x = in[((long)i * g.N2 + j) * g.N3 + k];
+                on = value < 0 ? x != 0 : x == value;
+            }
             lab[v] = on ? v : -1;
         }
         __syncthreads();
@@ -245,6 +253,102 @@ __global__ __launch_bounds__(MB_THREADS) void label_select(const int *__restrict
         out[v] = (b > 0 && labels[v] == b) ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- painting by size ----------------------------------------------------------------
+
+// acc[0] = size of the largest component, acc[1] = components painted, acc[2] = voxels painted. flag[q] = 1 where label q + 1 is painted:
+// select 0: all but the largest; 1: those of the others whose size a has (double)a < 0.1 * (double)L, the product formed once in float64 as Python
+// forms 0.1*regions[-1].area; 2: the largest alone. `best` is label_largest's: among equal sizes the highest label is the largest.
+__global__ __launch_bounds__(MB_THREADS) void paint_flags(const unsigned long long *__restrict__ sizes, int n, const int *__restrict__ best, int select,
+                                                          uint8_t *__restrict__ flag, unsigned long long *__restrict__ acc)
+{
+    const int b = best[0];
+    const unsigned long long big = b > 0 ? sizes[b - 1] : 0;
+    const double limit = 0.1 * (double)big;
+    unsigned long long comps = 0, vox = 0;
+    for (long q = (long)blockIdx.x * MB_THREADS + threadIdx.x; q < n; q += (long)gridDim.x * MB_THREADS) {         // grid-stride: ends
+        const unsigned long long a = sizes[q];
+        const bool largest = (int)q + 1 == b;
+        const bool on = select == 2 ? largest : (!largest && (select == 0 || (double)a < limit));
+        flag[q] = on ? 1 : 0;
+        if (on) { comps++; vox += a; }
+    }
+    for (int d = 32; d >= 1; d >>= 1) { comps += __shfl_xor(comps, d); vox += __shfl_xor(vox, d); }               // whole waves arrive here
+    if ((threadIdx.x & 63) == 0 && comps) { atomicAdd(acc + 1, comps); atomicAdd(acc + 2, vox); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) acc[0] = big;
+}
+
+// out = in with the voxels of the flagged labels set to fill
+__global__ __launch_bounds__(MB_THREADS) void paint_write(const uint8_t *__restrict__ in, const int *__restrict__ labels, const uint8_t *__restrict__ flag,
+                                                          uint8_t *__restrict__ out, int fill, long nVox)
+{
+    for (long v = (long)blockIdx.x * MB_THREADS + threadIdx.x; v < nVox; v += (long)gridDim.x * MB_THREADS) {      // grid-stride: ends
+        const int lab = labels[v];
+        out[v] = (lab > 0 && flag[lab - 1]) ? (uint8_t)fill : in[v];
+    }
+}
+
+// ---------------------------------------------------------------- the labelling, shared ----------------------------------------------------------------
+
+// Steps 1-5a for bfd_label3d and bfd_paint_components3d: reserve() before the host-to-device copies, run() after them. run() leaves the labels in L,
+// their number in nl, the voxel counts in dsz (wantSizes and nl > 0) and the milliseconds of its two timed sections in ms; its events are ev's.
+struct Labelling {
+    DevTemp<int> L, rank;
+    InclusiveSum<int> sum;
+    DevTemp<unsigned long long> dsz;
+    int nl = 0;
+    float ms = 0.f;
+
+    int reserve(const char *who, size_t n)
+    {
+        BFD_STEP(L.alloc(n));
+        BFD_STEP(rank.alloc(n));
+        BFD_STEP(sum.reserve(rank, n));
+        return 0;
+    }
+
+    // vol: the volume on the device; value < 0: the foreground is vol != 0
+    int run(const char *who, const uint8_t *vol, int value, const label_dims &g, size_t n, bool wantSizes, Events &ev)
+    {
+        const long nv = (long)n;
+        float ms1 = 0.f, ms2 = 0.f;
+        BFD_STEP(ev.record(0));
+        const unsigned vb = blocks_for(nv, MB_THREADS, MAX_BLOCKS);
+        hipLaunchKernelGGL(label_local, dim3(blocks_for(g.nTiles, 1, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, vol, L.p, g, value);
+        hipLaunchKernelGGL(label_merge, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, g, nv);
+        hipLaunchKernelGGL(label_flatten, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+        BFD_STEP(hipGetLastError());
+        BFD_STEP(sum.run(rank, n));
+        hipLaunchKernelGGL(label_assign, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
+        BFD_STEP(hipGetLastError());
+        BFD_STEP(ev.record(1));
+        BFD_STEP(ev.sync(1));
+        BFD_STEP(ev.elapsed(&ms1, 0, 1));
+        // the number of components sizes the histogram: the one value the host needs between the kernels
+        BFD_STEP(hipMemcpy(&nl, rank.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost));
+        if (wantSizes && nl > 0) {
+            BFD_STEP(dsz.alloc((size_t)nl));
+            BFD_STEP(hipMemset(dsz, 0, (size_t)nl * sizeof(unsigned long long)));
+            BFD_STEP(ev.record(0));
+            hipLaunchKernelGGL(label_sizes, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, dsz.p, nv);
+            BFD_STEP(hipGetLastError());
+            BFD_STEP(ev.record(1));
+            BFD_STEP(ev.sync(1));
+            BFD_STEP(ev.elapsed(&ms2, 0, 1));
+        }
+        ms = ms1 + ms2;
+        return 0;
+    }
+};
+
+static label_dims make_label_dims(int64_t N1, int64_t N2, int64_t N3, int connectivity)
+{
+    label_dims g;
+    g.N1 = (int)N1; g.N2 = (int)N2; g.N3 = (int)N3; g.conn = connectivity;
+    g.nTj = (int)((N2 + LT_J - 1) / LT_J); g.nTk = (int)((N3 + LT_K - 1) / LT_K);
+    g.nTiles = (long)g.nTk * g.nTj * ((N1 + LT_I - 1) / LT_I);
+    return g;
+}
+
 }  // namespace
 
 extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3,
@@ -342,61 +446,96 @@ extern "C" int bfd_label3d(int device, const uint8_t *in, int32_t *labels, int64
     if (numLabels) *numLabels = 0;
     if (n == 0) return 0;
 
-    label_dims g;
-    g.N1 = (int)N1; g.N2 = (int)N2; g.N3 = (int)N3; g.conn = connectivity;
-    g.nTj = (int)((N2 + LT_J - 1) / LT_J); g.nTk = (int)((N3 + LT_K - 1) / LT_K);
-    g.nTiles = (long)g.nTk * g.nTj * ((N1 + LT_I - 1) / LT_I);
+    const label_dims g = make_label_dims(N1, N2, N3, connectivity);
     const long nv = (long)n;
     const bool wantSizes = sizes || largest;
 
     DevTemp<uint8_t> vol;                             // the input; afterwards the mask of the largest component
-    DevTemp<int> L, rank, best;
-    InclusiveSum<int> sum;
-    DevTemp<unsigned long long> dsz;
+    DevTemp<int> best;
+    Labelling lab;
     Events ev;
-    int nl = 0;
-    float ms = 0.f, ms2 = 0.f;
+    float ms2 = 0.f;
     BFD_STEP(vol.alloc(n));
-    BFD_STEP(L.alloc(n));
-    BFD_STEP(rank.alloc(n));
+    if (int rc = lab.reserve(who, n)) return rc;
     BFD_STEP(best.alloc(1));
-    BFD_STEP(sum.reserve(rank, n));
     BFD_STEP(hipMemcpy(vol, in, n, hipMemcpyHostToDevice));
     BFD_STEP(ev.create());
-    BFD_STEP(ev.record(0));
-    const unsigned vb = blocks_for(nv, MB_THREADS, MAX_BLOCKS);
-    hipLaunchKernelGGL(label_local, dim3(blocks_for(g.nTiles, 1, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, vol.p, L.p, g);
-    hipLaunchKernelGGL(label_merge, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, g, nv);
-    hipLaunchKernelGGL(label_flatten, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
-    BFD_STEP(hipGetLastError());
-    BFD_STEP(sum.run(rank, n));
-    hipLaunchKernelGGL(label_assign, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, rank.p, nv);
-    BFD_STEP(hipGetLastError());
-    BFD_STEP(ev.record(1));
-    BFD_STEP(ev.sync(1));
-    BFD_STEP(ev.elapsed(&ms, 0, 1));
-    // the number of components sizes the histogram: the one value the host needs between the kernels
-    BFD_STEP(hipMemcpy(&nl, rank.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost));
+    if (int rc = lab.run(who, vol, -1, g, n, wantSizes, ev)) return rc;
+    const int nl = lab.nl;
     if (wantSizes && nl > 0) {
-        BFD_STEP(dsz.alloc((size_t)nl));
-        BFD_STEP(hipMemset(dsz, 0, (size_t)nl * sizeof(unsigned long long)));
-        BFD_STEP(ev.record(0));
-        hipLaunchKernelGGL(label_sizes, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, dsz.p, nv);
         if (largest) {
-            hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, dsz.p, nl, best.p);
-            hipLaunchKernelGGL(label_select, dim3(vb), dim3(MB_THREADS), 0, 0, L.p, best.p, vol.p, nv);
+            BFD_STEP(ev.record(0));
+            hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, lab.dsz.p, nl, best.p);
+            hipLaunchKernelGGL(label_select, dim3(blocks_for(nv, MB_THREADS, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, lab.L.p, best.p, vol.p, nv);
+            BFD_STEP(hipGetLastError());
+            BFD_STEP(ev.record(1));
+            BFD_STEP(ev.sync(1));
+            BFD_STEP(ev.elapsed(&ms2, 0, 1));
         }
-        BFD_STEP(hipGetLastError());
-        BFD_STEP(ev.record(1));
-        BFD_STEP(ev.sync(1));
-        BFD_STEP(ev.elapsed(&ms2, 0, 1));
-        if (sizes && sizesCapacity >= nl) BFD_STEP(hipMemcpy(sizes, dsz, (size_t)nl * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (sizes && sizesCapacity >= nl) BFD_STEP(hipMemcpy(sizes, lab.dsz, (size_t)nl * sizeof(int64_t), hipMemcpyDeviceToHost));
         if (largest) BFD_STEP(hipMemcpy(largest, vol, n, hipMemcpyDeviceToHost));
     } else if (largest) {
         memset(largest, 0, n);                        // no component: an all-zero mask
     }
-    if (labels) BFD_STEP(hipMemcpy(labels, L, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (labels) BFD_STEP(hipMemcpy(labels, lab.L, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (numLabels) *numLabels = nl;
-    if (kernelMs) *kernelMs = ms + ms2;
+    if (kernelMs) *kernelMs = lab.ms + ms2;
+    return 0;
+}
+
+extern "C" int bfd_paint_components3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int value, int connectivity,
+                                      int select, int fill, int64_t *counts, float *kernelMs)
+{
+    static const char *who = "bfd_paint_components3d";
+    if (!in || !out || !counts) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (value < 0 || value > 255 || fill < 0 || fill > 255) BFD_FAIL(-1, std::string(who) + ": value and fill must be uint8 values (0 .. 255)");
+    if (connectivity < 1 || connectivity > 3) BFD_FAIL(-1, std::string(who) + ": connectivity must be 1, 2 or 3");
+    if (select < 0 || select > 2) BFD_FAIL(-1, std::string(who) + ": select must be 0 (all but the largest), 1 (the small ones) or 2 (the largest)");
+    const size_t n = (size_t)(N1 * N2 * N3);
+    if (n && overlap(in, n, out, n)) BFD_FAIL(-1, std::string(who) + ": out may not alias in");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (n == 0) { for (int q = 0; q < 4; q++) counts[q] = 0; return 0; }
+
+    const label_dims g = make_label_dims(N1, N2, N3, connectivity);
+    const long nv = (long)n;
+    DevTemp<uint8_t> vol, dout;
+    DevTemp<int> best;
+    DevTemp<unsigned long long> acc;
+    Labelling lab;
+    Events ev;
+    float ms2 = 0.f;
+    unsigned long long r[3] = {0, 0, 0};
+    BFD_STEP(vol.alloc(n));
+    if (int rc = lab.reserve(who, n)) return rc;
+    BFD_STEP(best.alloc(1));
+    BFD_STEP(acc.alloc(3));
+    BFD_STEP(hipMemcpy(vol, in, n, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    if (int rc = lab.run(who, vol, value, g, n, true, ev)) return rc;
+    const int nl = lab.nl;
+    if (nl > 0) {
+        // the flags take the place of the root flags in `rank` (nl <= n bytes of 4 n), the result the place of nothing: out is a volume of its own
+        uint8_t *flag = (uint8_t *)lab.rank.p;
+        BFD_STEP(dout.alloc(n));
+        BFD_STEP(hipMemset(acc, 0, 3 * sizeof(unsigned long long)));
+        BFD_STEP(ev.record(0));
+        hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, lab.dsz.p, nl, best.p);
+        hipLaunchKernelGGL(paint_flags, dim3(blocks_for(nl, MB_THREADS, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, lab.dsz.p, nl, best.p, select, flag, acc.p);
+        hipLaunchKernelGGL(paint_write, dim3(blocks_for(nv, MB_THREADS, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, vol.p, lab.L.p, flag, dout.p, fill, nv);
+        BFD_STEP(hipGetLastError());
+        BFD_STEP(ev.record(1));
+        BFD_STEP(ev.sync(1));
+        BFD_STEP(ev.elapsed(&ms2, 0, 1));
+        BFD_STEP(hipMemcpy(r, acc, sizeof r, hipMemcpyDeviceToHost));
+        BFD_STEP(hipMemcpy(out, dout, n, hipMemcpyDeviceToHost));
+    } else {
+        memcpy(out, in, n);                           // no foreground: nothing to paint
+    }
+    counts[0] = nl; counts[1] = (int64_t)r[0]; counts[2] = (int64_t)r[1]; counts[3] = (int64_t)r[2];
+    if (kernelMs) *kernelMs = lab.ms + ms2;
     return 0;
 }

@@ -645,6 +645,63 @@ int bfd_gaussian_filter3d(int device, int dtype /*1 f32, 3 f64*/, const void *in
                           const double *sigma /*[3]*/, double truncate, int mode /*0 reflect, 1 constant, 2 nearest, 3 mirror*/, double cval,
                           float *kernelMs /*may be NULL*/);
 
+/* ---- the final tissue mask: the whole-volume stages of BabelDatasetPreps.py between the conformal masks and the file Step 2 reads ----
+ * Conventions of bfd_median_filter3d and of the section above: HOST pointers, numpy C order, fewer than 2^31 voxels, inputs never written, 0 / -1 (before
+ * a device is looked for) / -3 / -10, text in bfd_last_error, kernelMs the kernels alone, outputs untouched on an argument refusal, nothing held
+ * on the device after the call.
+ *
+ * bfd_paint_components3d: the components of the foreground in == value, chosen by size, set to `fill`; the labels never leave the device.
+ * Replaces label -> regionprops -> sorted(key=area) -> np.isin -> masked store (:909-929, :1077-1097; :1055-1061 for select 2).
+ * Components and their labels are bfd_label3d's (raster order of the first voxel; connectivity 1, 2, 3). The LARGEST component has the most voxels,
+ * among equals the HIGHEST label: what sorted(regionprops(...), key=area)[-1] selects, Python's sort being stable and regionprops listing by label.
+ *   select 0  every component except the largest                                                    (:922-924)
+ *   select 1  every component except the largest whose size a satisfies (double)a < 0.1 * (double)L, L the size of the largest; the product is
+ *             formed once in float64, as Python forms 0.1*regions[-1].area                          (:926, bApplyBOXFOV)
+ *   select 2  the largest alone                                                                     (:1061)
+ * out = in with the selected voxels set to fill; every other voxel is copied, whatever its value. counts int64 [4] = {components, size of the
+ * largest, components painted, voxels painted}. Without foreground out = in and the counts are 0 (the reference raises at regions[-1]). An empty
+ * volume returns 0 after the device pick with the counts zeroed.
+ * -1, in this order: a null pointer (in, out, counts); a negative dimension; 2^31 voxels or more; value or fill outside 0 .. 255; connectivity outside
+ * 1 .. 3; select outside 0 .. 2; out overlapping in. kernelMs is the sum of the timed sections (labelling, sizes, flags and painting).
+ * Device memory: bfd_label3d's 9 B per voxel and 8 B per component, and 1 B per voxel for out. */
+int bfd_paint_components3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int value, int connectivity,
+                           int select /*0 all but the largest, 1 the small ones, 2 the largest*/, int fill, int64_t *counts /*[4]*/,
+                           float *kernelMs /*may be NULL*/);
+
+/* bfd_quantize_values3d: min and max of `values` under the mask, the quantisation to 2^bits levels, the table of distinct quantised values and the
+ * index map, :1019-1027 and :1039 in one call. All float32, one rounding per operation, no fused multiply-add:
+ *     mn, mx = min, max of values where mask != 0          A = mx - mn          M = 2^bits - 1
+ *     s = fl32(M / A)        r = fl32(A / M)
+ *     level(x) = rint(fl32(s * fl32(x - mn)))              half to even, as np.round
+ *     v(l)     = fl32(fl32(r * l) + mn)
+ *   quantized  float32 [N1][N2][N3], may be NULL: v(level(x)) under the mask, values elsewhere
+ *   table      float32, room for 2^bits: the distinct v(l) of the levels that occur, ascending (np.unique(ndataCT[nfct]) after :1026). v is
+ *              non-decreasing in l; levels whose values are equal share a row
+ *   numValues  the number of rows written
+ *   map        uint32 [N1][N2][N3], may be NULL: the row of v(level(x)) under the mask, 0 elsewhere (what MapFilter returns at :1039)
+ *   range      float32 [2] = {mn, mx}
+ * This equals the reference's expression under numpy 1.x (float64 scalars A/M, M/A demoted against the float32 array) and 2.x (float32 divisions): a
+ * float64 quotient of two float32 values rounded to float32 is the correctly rounded float32 quotient. The build flushes float32 denormals and numpy
+ * does not: the definition covers inputs whose intermediates are normal or zero. tests/tissue_oracle.py restates it in numpy.
+ * -1 before a device is looked for, in this order: a null pointer (values, mask, table, numValues, range); a negative dimension; 2^31 voxels or
+ * more; bits outside 1 .. 16; an output overlapping an input or the other output. -1 AFTER the device pick and the min / max reduction, before any
+ * output is written, in this order: an empty mask (an empty volume included); a value under the mask that is not finite; A not finite in float32;
+ * A == 0 (a denormal A is zero to the device); r < 2^-126. The text of each of these, and of no other error, reads "bfd_quantize_values3d: refused data: ...".
+ * kernelMs is zero after such a refusal, the other outputs are untouched.
+ * Device memory: 5 B per voxel, 4 B per voxel for each of quantized and map, 6 B per level. */
+int bfd_quantize_values3d(int device, const float *values, const uint8_t *mask, int64_t N1, int64_t N2, int64_t N3, int bits /*1 .. 16*/,
+                          float *quantized /*may be NULL*/, uint32_t *map /*may be NULL*/, float *table /*2^bits floats*/, int64_t *numValues,
+                          float *range /*[2]*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_clear_beyond_bone3d: the pre-focal cleanup, :1122-1133 without the two flips. Per line (i, j): let kb be the largest k > kFocal with
+ * in[i][j][k] equal to boneA or boneB; if there is one, every k > kb with in == from becomes `to`. Everything else is copied: a line without such
+ * bone, any bone at k <= kFocal, `from` voxels at or below kb. counts int64 [2] = {lines with such bone, voxels changed}. An empty volume (with
+ * N3 > kFocal) returns 0 after the device pick with the counts zeroed.
+ * -1, in this order: a null pointer (in, out, counts); a negative dimension; 2^31 voxels or more; kFocal outside 0 .. N3 - 1; boneA, boneB, from or
+ * to outside 0 .. 255; out overlapping in. Device memory: two volumes. */
+int bfd_clear_beyond_bone3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int64_t kFocal, int boneA, int boneB,
+                            int from, int to, int64_t *counts /*[2]*/, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
