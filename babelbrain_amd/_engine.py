@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     'bfd_affine_transform3d', 'bfd_spline_filter3d', 'bfd_voxelize_mesh', 'bfd_voxel_points', 'bfd_map_values3d',
     'bfd_distance_transform_edt3d', 'bfd_gaussian_filter3d', 'bfd_voxel_scatter3d', 'bfd_voxelize_scatter3d',
     'bfd_paint_components3d', 'bfd_quantize_values3d', 'bfd_clear_beyond_bone3d',
+    'bfd_label_survey3d', 'bfd_assemble_material_map3d', 'bfd_sdr_rays3d',
 ]
 
 
@@ -223,6 +224,13 @@ def load_library():
                                           C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_clear_beyond_bone3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_label_survey3d.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_float)]
+    lib.bfd_assemble_material_map3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_sdr_rays3d.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64,
+                                   C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

@@ -1,9 +1,10 @@
-// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip and bfd_tissue.hip (and by no other
+// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip and bfd_domain.hip (and by no other
 // source: the solver's translation units do not see this file). Host code only.
 //
-// The contract of the fifteen entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
+// The contract of the eighteen entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
 // bfd_voxelize_mesh, bfd_voxel_points, bfd_map_values3d, bfd_distance_transform_edt3d, bfd_gaussian_filter3d, bfd_voxel_scatter3d,
-// bfd_voxelize_scatter3d, bfd_paint_components3d, bfd_quantize_values3d, bfd_clear_beyond_bone3d). Every entry takes these steps in this order:
+// bfd_voxelize_scatter3d, bfd_paint_components3d, bfd_quantize_values3d, bfd_clear_beyond_bone3d,
+// bfd_label_survey3d, bfd_assemble_material_map3d, bfd_sdr_rays3d). Every entry takes these steps in this order:
 //    1. argument errors: -1 and a text, each before a device is looked for, in the entry's own order
 //    2. pick_device: -3 where no device is visible or the ordinal is out of range
 //    3. kernelMs zeroed (after the device pick)

@@ -702,6 +702,69 @@ int bfd_quantize_values3d(int device, const float *values, const uint8_t *mask, 
 int bfd_clear_beyond_bone3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int64_t kFocal, int boneA, int boneB,
                             int from, int to, int64_t *counts /*[2]*/, float *kernelMs /*may be NULL*/);
 
+/* ---- the domain setup of Step 2: what TranscranialModeling/BabelIntegrationBASE.py does between the mask file and the solver call ----
+ * Conventions of the section above: HOST pointers, numpy C order (k fastest), fewer than 2^31 voxels per volume, inputs never written, 0 / -1 (before
+ * a device is looked for) / -3 / -10, text in bfd_last_error, kernelMs the kernels alone, outputs untouched on a refusal, nothing held on the
+ * device after the call. The driver flips axis 2 of every volume it loads (:1161, :1176, :1179, :1844). With flipK = 1 the entries read the stored
+ * volume at M3 - 1 - k, and every index they take or report is in the driver's (flipped) coordinates; the flipped copy never exists.
+ * tests/domain_oracle.py restates the three definitions in numpy.
+ *
+ * bfd_label_survey3d: what the driver asks of the label volume (:1163, :1903-1908, :2162), in one pass. The box lo, hi is half-open, in driver
+ * coordinates.
+ *   hist    int64 [256]: the number of voxels of each label inside the box
+ *   bounds  int64 [6] = {min i, max i, min j, max j, min k, max k} of the voxels inside the box with label > 0, relative to lo; all -1 where none.
+ *           bounds[4] is FirstVoxelTissueZ - ZLOffset of :1903-1904 for the crop the box stands for
+ *   focal   int64 [2] = {voxels equal to 5 in the WHOLE volume, the smallest C-order linear index of one in driver coordinates or -1}
+ * An empty volume returns 0 after the device pick with hist zeroed, bounds -1 and focal {0, -1}.
+ * -1, in this order: a null pointer (labels, lo, hi, hist, bounds, focal); a negative dimension; 2^31 voxels or more; a box that is not
+ * 0 <= lo <= hi <= M on every axis; flipK outside 0 .. 1. Device memory: one volume. */
+int bfd_label_survey3d(int device, const uint8_t *labels, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo /*[3]*/, const int64_t *hi /*[3]*/,
+                       int flipK, int64_t *hist /*[256]*/, int64_t *bounds /*[6]*/, int64_t *focal /*[2]*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_assemble_material_map3d: :2111-2201 (the path that is neither water only nor a test hook). The source box lo, size of the volumes [M1][M2][M3]
+ * (driver coordinates) lands at padLo in outputs of N = size + padLo + padHi per axis; outside it every output is 0. With raw the label at a voxel:
+ *   mapNoCT  uint32 [N], may be NULL: raw (:2166, before the relabelling and before the water layer)
+ *   airOut   uint32 [N], may be NULL: air at the voxel, 0 where air is NULL (:2183-2190; no water layer)
+ *   map      uint32 [N]: lut[raw] where bit 31 of lut[raw] is clear, ct + ctOffset (uint32 arithmetic) where it is set; then 0 on the planes
+ *            k <= zWater (:2201; -1: none). The sequential relabels of :2169-2173 and :2196-2198 are functions of raw: the caller runs them on
+ *            0 .. 255 and hands the result as lut. ct is the index map as stored (uint16 or uint32 by ctBytes), ctOffset 3 or 6 (:1241-1244)
+ *   stats    int64 [8] = {voxels taken from ct (bone); the min and the max of ct + ctOffset over them, before the water layer, as the asserts of
+ *            :2191-2192 see them, -1 without bone; voxels with map > 0; the max of map; the smallest k with map > 0, -1 if none; the same on the
+ *            column focalIJ (what CalculateDomainZReference reads, :2609-2614; the reference aliases _MaterialMap and _MaterialMapRef at :2161, so
+ *            that method sees the final map); voxels with map >= nMaterials}
+ * An empty map (a zero in N) returns 0 after the device pick with stats {0, -1, -1, 0, 0, -1, -1, 0}.
+ * -1, in this order: a null pointer (labels, lo, size, padLo, padHi, lut, focalIJ, map, stats); a negative dimension; 2^31 voxels or more in the
+ * source; ctBytes outside {0, 2, 4} or not 0 exactly where ct is NULL; a box that is not 0 <= lo, 0 <= size, lo + size <= M; a padding outside
+ * 0 .. 2^31 - 1; a map of 2^31 voxels or more; flipK outside 0 .. 1; a lut entry with bit 31 while ct is NULL; zWater < -1; nMaterials outside
+ * 0 .. 2^32 - 1; focalIJ outside the map (a non-empty map only); an output overlapping an input or another output.
+ * Device memory: the inputs handed, and 4 B per voxel of N for each output. */
+int bfd_assemble_material_map3d(int device, const uint8_t *labels, const void *ct /*may be NULL*/, int ctBytes /*0, 2, 4*/, const uint8_t *air /*may be NULL*/,
+                                int64_t M1, int64_t M2, int64_t M3, const int64_t *lo /*[3]*/, const int64_t *size /*[3]*/, const int64_t *padLo /*[3]*/,
+                                const int64_t *padHi /*[3]*/, int flipK, const uint32_t *lut /*[256]*/, uint32_t ctOffset, int64_t zWater, int64_t nMaterials,
+                                const int64_t *focalIJ /*[2]*/, uint32_t *map, uint32_t *mapNoCT /*may be NULL*/, uint32_t *airOut /*may be NULL*/,
+                                int64_t *stats /*[8]*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_sdr_rays3d: compute_sdr_from_rays, :816-854, on the box lo, size of the CT index volume (uint16 or uint32 by ctBytes, as stored, WITHOUT the
+ * offset of :1241-1244), with HU = hu[index] and skull = index > 0 as :1385-1392 form them. hu is float32 or float64 (huBytes 4 or 8) and `value` has
+ * its type. One ray per (r, c) of the lattice ceil(size[0] / stepI) x ceil(size[1] / stepJ), r outer and c inner, along k at
+ * (lo[0] + r stepI, lo[1] + c stepJ). With n the skull voxels of the ray (count) and p(q) the position of the one of rank q:
+ *   state 4  an index >= nHU on the ray (numpy raises IndexError at :1389; only the rays of the lattice are looked at)
+ *   state 0  n < minSkullVoxels
+ *   else     mid = n // 2, l_half = n centerRegion, beg = max(0, rint(mid - l_half / 2)), end = min(n - 1, 1 + rint(mid + l_half / 2)), in float64,
+ *            one rounding per operation, rint half to even as np.round (dm_segment of csrc/bfd_domain_core.h)
+ *   state 3  beg >= end: the centre slice is empty (numpy's .min() raises ValueError)
+ *   state 2  the maximum of hu over the skull voxels is <= 0
+ *   state 1  value = min(hu[index] for every voxel p(beg) <= p < p(end), skull or not: a voxel of index 0 contributes hu[0]) / that maximum, one
+ *            division in the table's type
+ * value is 0 unless the state is 1. A lattice without rays returns 0 after the device pick and writes nothing.
+ * -1, in this order: a null pointer (ct, lo, size, hu, value, count, state); a negative dimension; 2^31 voxels or more; ctBytes outside {2, 4}; a box
+ * that is not 0 <= lo, 0 <= size, lo + size <= M; flipK outside 0 .. 1; huBytes outside {4, 8}; nHU outside 1 .. 2^31 - 1; a hu that is not
+ * finite; stepI or stepJ outside 1 .. 2^31 - 1; minSkullVoxels outside 1 .. 2^31 - 1; centerRegion negative or not finite.
+ * Device memory: the index volume, the table and 5 B + huBytes per ray. */
+int bfd_sdr_rays3d(int device, const void *ct, int ctBytes /*2, 4*/, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo /*[3]*/, const int64_t *size /*[3]*/,
+                   int flipK, const void *hu, int huBytes /*4, 8*/, int64_t nHU, int64_t stepI, int64_t stepJ, int64_t minSkullVoxels, double centerRegion,
+                   void *value, int32_t *count, uint8_t *state, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
