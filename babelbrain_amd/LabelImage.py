@@ -4,6 +4,7 @@ hand LabelImage to BabelDatasetPreps.InitLabelImageGPUCallback):
     InitLabel(DeviceName, GPUBackend)                                 CalculateMaskProcess.py:79
     LabelImage(nfct, GPUBackend=...)                                  BabelDatasetPreps.py:891, :913, :1058, :1081 (skimage.measure.label of a bool volume)
     largest_component(nfct)                                           :888-894 in one call: label, regionprops, sort by area, == the last label
+    largest_component(arr, ties='first')                              CTZTEProcessing.py:599-606: sorted(..., reverse=True)[0] (bfd_select_component3d)
     component_sizes(mask)                                             the areas regionprops would report, labels 1..n
 
 The labelling runs on the MI355X through the C ABI (bfd_label3d, csrc/bfd_morphology.hip); there is no CPU fallback. Labels equal
@@ -18,6 +19,7 @@ from . import _engine, _step1
 
 _device = 0
 last_kernel_ms = None
+last_component = None              # largest_component(ties='first'): (components, voxels of the chosen one)
 
 
 def InitLabel(DeviceName=None, GPUBackend=None):
@@ -77,8 +79,24 @@ def component_sizes(image, connectivity=None):
     return _run(*_checked(image, None, connectivity), want_sizes=True)[2]
 
 
-def largest_component(image, connectivity=None):
+def largest_component(image, connectivity=None, ties='last'):
     """bool mask of the component with the most voxels; among equals the one with the highest label, which is what
         label_img = label(image); regions = sorted(regionprops(label_img), key=lambda d: d.area); mask = label_img == regions[-1].label
-    selects (BabelDatasetPreps.py:888-894). All false for an image without foreground. The int32 labels never leave the device."""
-    return _run(*_checked(image, None, connectivity), want_largest=True)[3]
+    selects (BabelDatasetPreps.py:888-894). All false for an image without foreground. The int32 labels never leave the device.
+    ties='first' keeps the lowest label among equals instead (bfd_select_component3d): what
+        props = sorted(regionprops(label_img, ...), key=itemgetter('pixelcount'), reverse=True); mask = label_img == props[0].label
+    selects (CTZTEProcessing.py:599-606), Python's sort being stable under reverse too."""
+    global last_kernel_ms, last_component
+    if ties not in ('last', 'first'):
+        raise ValueError("ties must be 'last' or 'first', not %r" % (ties,))
+    if ties == 'last':
+        return _run(*_checked(image, None, connectivity), want_largest=True)[3]
+    a, c = _checked(image, None, connectivity)
+    out = np.empty(a.shape, np.uint8)
+    info = np.zeros(2, np.int64)
+    ms = C.c_float()
+    _step1.call('bfd_select_component3d', _device, _engine._ptr(a), _engine._ptr(out), a.shape[0], a.shape[1], a.shape[2], c, 1, _engine._ptr(info),
+                C.byref(ms))
+    last_kernel_ms = ms.value
+    last_component = (int(info[0]), int(info[1]))
+    return out.view(np.bool_)

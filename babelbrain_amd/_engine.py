@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     'bfd_distance_transform_edt3d', 'bfd_gaussian_filter3d', 'bfd_voxel_scatter3d', 'bfd_voxelize_scatter3d',
     'bfd_paint_components3d', 'bfd_quantize_values3d', 'bfd_clear_beyond_bone3d',
     'bfd_label_survey3d', 'bfd_assemble_material_map3d', 'bfd_sdr_rays3d',
+    'bfd_integer_histogram3d', 'bfd_order_statistics3d', 'bfd_uniform_histogram3d', 'bfd_pseudo_ct_candidates3d', 'bfd_pseudo_ct_convert3d',
+    'bfd_select_component3d',
 ]
 
 
@@ -231,6 +233,17 @@ def load_library():
                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_sdr_rays3d.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64,
                                    C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_integer_histogram3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_order_statistics3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_double, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_uniform_histogram3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    lib.bfd_pseudo_ct_candidates3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                               C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    lib.bfd_pseudo_ct_convert3d.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_select_component3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

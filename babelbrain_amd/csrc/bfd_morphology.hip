@@ -246,6 +246,29 @@ __global__ __launch_bounds__(1024) void label_largest(const unsigned long long *
     if (threadIdx.x == 0) best[0] = id[0];
 }
 
+// 5b with the other tie rule: among equals the lowest label, what sorted(props, key=pixelcount, reverse=True)[0] selects (CTZTEProcessing.py:604-606)
+__global__ __launch_bounds__(1024) void label_largest_lowest(const unsigned long long *__restrict__ sizes, int n, int *__restrict__ best)
+{
+    __shared__ unsigned long long sz[1024];
+    __shared__ int id[1024];
+    unsigned long long s = 0;
+    int b = 0;
+    for (int q = threadIdx.x; q < n; q += 1024)       // ascending labels: > lets the earlier of two equals stay
+        if (sizes[q] > s) { s = sizes[q]; b = q + 1; }
+    sz[threadIdx.x] = s; id[threadIdx.x] = b;
+    __syncthreads();
+    for (int h = 512; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            const unsigned long long s2 = sz[threadIdx.x + h];
+            const int b2 = id[threadIdx.x + h];
+            // b2 == 0 is a thread without a component (s2 == 0): it never wins, a component has a voxel
+            if (s2 > sz[threadIdx.x] || (s2 == sz[threadIdx.x] && b2 > 0 && b2 < id[threadIdx.x])) { sz[threadIdx.x] = s2; id[threadIdx.x] = b2; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) best[0] = id[0];
+}
+
 __global__ __launch_bounds__(MB_THREADS) void label_select(const int *__restrict__ labels, const int *__restrict__ best, uint8_t *__restrict__ out, long nVox)
 {
     const int b = best[0];
@@ -536,6 +559,59 @@ extern "C" int bfd_paint_components3d(int device, const uint8_t *in, uint8_t *ou
         memcpy(out, in, n);                           // no foreground: nothing to paint
     }
     counts[0] = nl; counts[1] = (int64_t)r[0]; counts[2] = (int64_t)r[1]; counts[3] = (int64_t)r[2];
+    if (kernelMs) *kernelMs = lab.ms + ms2;
+    return 0;
+}
+
+extern "C" int bfd_select_component3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int connectivity, int tie,
+                                      int64_t *info, float *kernelMs)
+{
+    static const char *who = "bfd_select_component3d";
+    if (!in || !out || !info) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (N1 < 0 || N2 < 0 || N3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
+    if (!volume_fits(N1, N2, N3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (connectivity < 1 || connectivity > 3) BFD_FAIL(-1, std::string(who) + ": connectivity must be 1, 2 or 3");
+    if (tie != 0 && tie != 1) BFD_FAIL(-1, std::string(who) + ": tie must be 0 (the highest label among equals) or 1 (the lowest)");
+    const size_t n = (size_t)(N1 * N2 * N3);
+    if (n && overlap(in, n, out, n)) BFD_FAIL(-1, std::string(who) + ": out may not alias in");
+
+    if (int rc = pick_device(who, device)) return rc;
+    if (kernelMs) *kernelMs = 0.f;
+    if (n == 0) { info[0] = info[1] = 0; return 0; }
+
+    const label_dims g = make_label_dims(N1, N2, N3, connectivity);
+    const long nv = (long)n;
+    DevTemp<uint8_t> vol;                             // the input; afterwards the mask of the chosen component
+    DevTemp<int> best;
+    Labelling lab;
+    Events ev;
+    float ms2 = 0.f;
+    int chosen = 0;
+    unsigned long long size = 0;
+    BFD_STEP(vol.alloc(n));
+    if (int rc = lab.reserve(who, n)) return rc;
+    BFD_STEP(best.alloc(1));
+    BFD_STEP(hipMemcpy(vol, in, n, hipMemcpyHostToDevice));
+    BFD_STEP(ev.create());
+    if (int rc = lab.run(who, vol, -1, g, n, true, ev)) return rc;
+    const int nl = lab.nl;
+    if (nl > 0) {
+        BFD_STEP(ev.record(0));
+        if (tie) hipLaunchKernelGGL(label_largest_lowest, dim3(1), dim3(1024), 0, 0, lab.dsz.p, nl, best.p);
+        else hipLaunchKernelGGL(label_largest, dim3(1), dim3(1024), 0, 0, lab.dsz.p, nl, best.p);
+        hipLaunchKernelGGL(label_select, dim3(blocks_for(nv, MB_THREADS, MAX_BLOCKS)), dim3(MB_THREADS), 0, 0, lab.L.p, best.p, vol.p, nv);
+        BFD_STEP(hipGetLastError());
+        BFD_STEP(ev.record(1));
+        BFD_STEP(ev.sync(1));
+        BFD_STEP(ev.elapsed(&ms2, 0, 1));
+        BFD_STEP(hipMemcpy(&chosen, best, sizeof chosen, hipMemcpyDeviceToHost));
+        if (chosen < 1 || chosen > nl) BFD_FAIL(-10, std::string(who) + ": the reduction returned a label outside 1 .. components");
+        BFD_STEP(hipMemcpy(&size, lab.dsz.p + (chosen - 1), sizeof size, hipMemcpyDeviceToHost));
+        BFD_STEP(hipMemcpy(out, vol, n, hipMemcpyDeviceToHost));
+    } else {
+        memset(out, 0, n);                            // no component: an all-zero mask
+    }
+    info[0] = nl; info[1] = (int64_t)size;
     if (kernelMs) *kernelMs = lab.ms + ms2;
     return 0;
 }

@@ -765,6 +765,89 @@ int bfd_sdr_rays3d(int device, const void *ct, int ctBytes /*2, 4*/, int64_t M1,
                    int flipK, const void *hu, int huBytes /*4, 8*/, int64_t nHU, int64_t stepI, int64_t stepJ, int64_t minSkullVoxels, double centerRegion,
                    void *value, int32_t *count, uint8_t *state, float *kernelMs /*may be NULL*/);
 
+/* ---- the pseudo-CT from ZTE / PETRA: the whole-volume steps of BabelBrain/CTZTEProcessing.py, ConvertZTE_PETRA_pCT (:501-628) ----
+ * Conventions of the sections above: HOST pointers, numpy C order (k fastest), fewer than 2^31 voxels, inputs never written, 0 / -1 (before a device
+ * is looked for) / -3 / -10, text in bfd_last_error, kernelMs the kernels alone (the sum of the timed sections where the host reads a few words
+ * between them), outputs untouched on a refusal, nothing held on the device after the call. `values` is float32 or float64 by dtype (1 or 3, the
+ * codes of bfd_gaussian_filter3d). All arithmetic is float64, one rounding per operation; a float32 voxel is widened exactly first, denormals
+ * included, as nibabel's get_fdata hands the reference float64. Byte masks are read as != 0. Four of the entries refuse DATA as well: -1 AFTER the
+ * device pick and their first reduction, with kernelMs zeroed and nothing else written; the text of each of these, and of no other error, reads
+ * "<entry>: refused data: ...". tests/pseudoct_oracle.py restates the definitions in numpy and scipy.
+ *
+ * bfd_integer_histogram3d: :559-562. range = {min, max} of the volume; first = (int64)min and last = (int64)max, truncated toward zero as
+ * astype(int) truncates; numBins = last - first + 1 (at most 65536); counts[b] = the voxels v with (int64)v == first + b, so the bin of 0 collects
+ * (-1, 1). counts has room for 65536; only numBins are written. Counts are integers: every run gives the same.
+ * -1, in this order: dtype outside {1, 3}; values null; a negative dimension; 2^31 voxels or more; a null pointer (counts, first, numBins, range);
+ * counts overlapping values. Refused data, in this order: an empty volume; a value that is not finite; max - min > 65535 ("The range of values in
+ * the ZTE file exceeds 2^16", the reference's text); a value beyond +-2^62.
+ * Device memory: the volume and 256 KiB. */
+int bfd_integer_histogram3d(int device, int dtype /*1 f32, 3 f64*/, const void *values, int64_t N1, int64_t N2, int64_t N3, int64_t *counts /*[65536]*/,
+                            int64_t *first, int64_t *numBins, double *range /*[2]*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_order_statistics3d: exact order statistics of the SELECTED voxels: mask != 0 (mask NULL: all) and v > above (v >= above with inclusive; a NaN
+ * is never selected; above = -inf with inclusive selects every voxel that is not a NaN). count = their number n. With ranks (R of them, 1 .. 4, each
+ * 0 .. n - 1): statistics[r] = the value at rank ranks[r] of the ascending order. Without (ranks NULL; R is not looked at): the two ranks
+ * np.percentile(x, quantile) reads, lo = floor((n - 1) * (quantile / 100)) and min(lo + 1, n - 1), in float64; statistics[0 .. 1] their values.
+ * ranksUsed (may be NULL) receives the ranks. The values are found by a radix select on order-preserving integer keys of the voxels' own format (32
+ * bits for float32, 64 for float64; -0.0 orders below +0.0), 8 bits a pass: no sort and no approximation; the host reads 256 counts per rank
+ * between the passes. np.percentile's interpolation between the two is the caller's (pc_lerp of csrc/bfd_pseudoct_core.h restates it).
+ * -1, in this order: dtype outside {1, 3}; values null; a negative dimension; 2^31 voxels or more; a null pointer (count, statistics); above a NaN;
+ * inclusive outside 0 .. 1; R outside 1 .. 4 where ranks are given; quantile outside 0 .. 100 where they are not. Refused data, in this order:
+ * nothing selected (an empty volume included); a rank outside 0 .. n - 1.
+ * Device memory: the volume, 1 B per voxel with a mask, 4 KiB. */
+int bfd_order_statistics3d(int device, int dtype /*1 f32, 3 f64*/, const void *values, const uint8_t *mask /*may be NULL*/, int64_t N1, int64_t N2, int64_t N3,
+                           double above, int inclusive, const int64_t *ranks /*[R], may be NULL*/, int R, double quantile, int64_t *count,
+                           int64_t *ranksUsed /*[R] or [2], may be NULL*/, double *statistics /*[R] or [2]*/, float *kernelMs /*may be NULL*/);
+
+/* bfd_uniform_histogram3d: np.histogram(x[x > above], bins) in two calls (x >= above with inclusive; :476-477 and BabelDatasetPreps.py:828).
+ *   edges NULL   range = {min, max} and count of the selected voxels (0, 0 and 0 where there are none). bins and counts are not looked at. The caller
+ *                forms edges = np.linspace(min, max, bins + 1), min - 0.5 .. max + 0.5 where they are equal
+ *   edges given  float64 [bins + 1], finite, ascending, edges[0] < edges[bins]; bins 1 .. 1024. counts[b] = the selected voxels in bin b by numpy's
+ *                rule for equal bins: i = (int)(((a - first) / (last - first)) * bins), first = edges[0], last = edges[bins]; i == bins goes down by
+ *                one; i -= 1 where a < edges[i]; then i += 1 where a >= edges[i + 1] and i != bins - 1. A selected voxel outside first .. last is
+ *                not counted. range and count are not looked at
+ * An empty volume returns 0 after the device pick with the outputs of the form zeroed.
+ * -1, in this order: dtype outside {1, 3}; values null; a negative dimension; 2^31 voxels or more; a null pointer (counts with edges; range, count
+ * without); above a NaN; inclusive outside 0 .. 1; bins outside 1 .. 1024; edges not finite or not ascending. Refused data (first form): a selected
+ * value that is not finite.
+ * Device memory: the volume and 12 KiB. */
+int bfd_uniform_histogram3d(int device, int dtype /*1 f32, 3 f64*/, const void *values, int64_t N1, int64_t N2, int64_t N3, double above, int inclusive,
+                            int bins, const double *edges /*[bins + 1] or NULL*/, int64_t *counts /*[bins]*/, double *range /*[2]*/, int64_t *count,
+                            float *kernelMs /*may be NULL*/);
+
+/* bfd_pseudo_ct_candidates3d: :577 / :592-597. q = values / divisor, one float64 division per voxel; with a head, q = -0.5 where head == 0 (ZTE;
+ * PETRA hands NULL). maximum = max q over all voxels. g = q where eroded != 0, maximum elsewhere (eroded: the head after binary_erosion,
+ * iterations 3). mask = 1 where lo <= g <= hi, else 0; count = the voxels of the mask. Two passes: the maximum, then the mask from the same quotients.
+ * -1, in this order: dtype outside {1, 3}; values null; a negative dimension; 2^31 voxels or more; a null pointer (eroded, mask, maximum, count); a
+ * divisor that is zero or not finite; lo or hi a NaN; mask overlapping an input. Refused data, in this order: an empty volume; a quotient that is not
+ * finite. Device memory: the volume and 1 B per voxel for each mask. */
+int bfd_pseudo_ct_candidates3d(int device, int dtype /*1 f32, 3 f64*/, const void *values, int64_t N1, int64_t N2, int64_t N3, double divisor,
+                               const uint8_t *head /*may be NULL*/, const uint8_t *eroded, double lo, double hi, uint8_t *mask, double *maximum,
+                               int64_t *count, float *kernelMs /*may be NULL*/);
+
+/* bfd_pseudo_ct_convert3d: :608-621 for every voxel, in the reference's order of statements (pc_hu of csrc/bfd_pseudoct_core.h):
+ *     ct = skin != 0 ? 42 : -1000
+ *     bone != 0:  ct = fl(fl(slope * q) + offset)          q as in bfd_pseudo_ct_candidates3d; no fused multiply-add
+ *     ct < -1000: ct = -1000          ct > 3300: ct = -1000          cavities != 0: ct = -1000
+ * out is float64 (outDtype 3) or that value rounded once to float32 (1). A NaN under the bone region stays a NaN, as in numpy. An empty volume
+ * returns 0 after the device pick. This entry refuses no data.
+ * -1, in this order: dtype outside {1, 3}; values null; a negative dimension; 2^31 voxels or more; a null pointer (bone, skin, cavities, out);
+ * outDtype outside {1, 3}; a divisor that is zero or not finite; slope or offset a NaN; out overlapping an input.
+ * Device memory: the two volumes and 1 B per voxel for each mask. */
+int bfd_pseudo_ct_convert3d(int device, int dtype /*1 f32, 3 f64*/, const void *values, int64_t N1, int64_t N2, int64_t N3, double divisor,
+                            const uint8_t *head /*may be NULL*/, const uint8_t *bone, const uint8_t *skin, const uint8_t *cavities, double slope,
+                            double offset, int outDtype /*1 f32, 3 f64*/, void *out, float *kernelMs /*may be NULL*/);
+
+/* bfd_select_component3d (csrc/bfd_morphology.hip): the component of in != 0 with the most voxels, as a 0 / 1 mask; components and labels are
+ * bfd_label3d's. Among components of equal size, tie 0 keeps the HIGHEST label (bfd_label3d's `largest`, sorted(regionprops, key=area)[-1]) and
+ * tie 1 the LOWEST: sorted(props, key=pixelcount, reverse=True)[0] of :604-606, Python's sort being stable. info int64 [2] = {components, voxels
+ * of the chosen one}. Without foreground out is all 0 and info is 0 (the reference raises at props[0]). An empty volume returns 0 after the
+ * device pick with info zeroed.
+ * -1, in this order: a null pointer (in, out, info); a negative dimension; 2^31 voxels or more; connectivity outside 1 .. 3; tie outside 0 .. 1; out
+ * overlapping in. kernelMs is the sum of the timed sections (labelling, sizes, reduction and mask). Device memory: bfd_label3d's. */
+int bfd_select_component3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int connectivity, int tie /*0 highest, 1 lowest*/,
+                           int64_t *info /*[2]*/, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
