@@ -29,6 +29,7 @@
 #include "bfd_internal.h"
 #include "bfd_call.h"
 #include "bfd_distance_core.h"
+#include "bfd_step1_stages.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -198,6 +199,38 @@ void launch_gauss_axis(const T *in, T *out, gauss_args &p)
 
 }  // namespace
 
+hipError_t bfd_stage_edt_squared(const uint64_t *background, int32_t *dist2, void *stack, int64_t N1, int64_t N2, int64_t N3)
+{
+    const int64_t n = N1 * N2 * N3, W = edt_row_words(N3);
+    edt_site *st = (edt_site *)stack;
+    hipLaunchKernelGGL(edt_rows, dim3(blocks_for(n, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, background, dist2, n, N3, W);
+    hipLaunchKernelGGL(edt_lines, dim3(blocks_for(N1 * N3, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, dist2, st, N1 * N3, N3, N2 * N3, N3, (int)N2);
+    hipLaunchKernelGGL(edt_lines, dim3(blocks_for(N2 * N3, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, dist2, st, N2 * N3, N3, N3, N2 * N3, (int)N1);
+    return hipGetLastError();
+}
+
+hipError_t bfd_stage_gaussian3d(int dtype, void *a, void *b, int64_t N1, int64_t N2, int64_t N3, const double *sigma, const int *radius, int mode,
+                                double cval, void **result)
+{
+    const int64_t N[3] = {N1, N2, N3};
+    void *src = a, *dst = b;
+    for (int ax = 0; ax < 3; ax++) {
+        if (!(sigma[ax] > 1e-15)) continue;           // scipy skips the axis
+        gauss_args p;
+        p.outer = ax == 0 ? 1 : (ax == 1 ? N1 : N1 * N2);
+        p.m = N[ax];
+        p.inner = ax == 0 ? N2 * N3 : (ax == 1 ? N3 : 1);
+        p.r = radius[ax]; p.mode = mode; p.T = 0; p.cval = cval;
+        memset(p.w, 0, sizeof p.w);
+        gauss_weights(sigma[ax], p.r, p.w);
+        if (dtype == 1) launch_gauss_axis<float>((const float *)src, (float *)dst, p);
+        else launch_gauss_axis<double>((const double *)src, (double *)dst, p);
+        std::swap(src, dst);
+    }
+    *result = src;
+    return hipGetLastError();
+}
+
 extern "C" int bfd_distance_transform_edt3d(int device, const uint8_t *in, int flags, int32_t *dist2, double *dist, int64_t N1, int64_t N2, int64_t N3,
                                             float *kernelMs)
 {
@@ -240,11 +273,8 @@ extern "C" int bfd_distance_transform_edt3d(int device, const uint8_t *in, int f
     BFD_STEP(ev.create());
     BFD_STEP(ev.record(0));
     hipLaunchKernelGGL(edt_pack, dim3(blocks_for(rows * W, THREADS / 64, MAX_BLOCKS)), dim3(THREADS), 0, 0, din.p, dbits.p, rows, N3, W, invert);
-    const unsigned blocksN = blocks_for((int64_t)n, THREADS, MAX_BLOCKS);
-    hipLaunchKernelGGL(edt_rows, dim3(blocksN), dim3(THREADS), 0, 0, dbits.p, df.p, (int64_t)n, N3, W);
-    hipLaunchKernelGGL(edt_lines, dim3(blocks_for(N1 * N3, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, df.p, dscratch.p, N1 * N3, N3, N2 * N3, N3, (int)N2);
-    hipLaunchKernelGGL(edt_lines, dim3(blocks_for(N2 * N3, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, df.p, dscratch.p, N2 * N3, N3, N3, N2 * N3, (int)N1);
-    if (dist) hipLaunchKernelGGL(edt_root, dim3(blocksN), dim3(THREADS), 0, 0, df.p, (double *)dscratch.p, (int64_t)n);
+    BFD_STEP(bfd_stage_edt_squared(dbits.p, df.p, dscratch.p, N1, N2, N3));
+    if (dist) hipLaunchKernelGGL(edt_root, dim3(blocks_for((int64_t)n, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, 0, df.p, (double *)dscratch.p, (int64_t)n);
     BFD_STEP(hipGetLastError());
     BFD_STEP(ev.record(1));
     BFD_STEP(ev.sync(1));
@@ -280,7 +310,6 @@ extern "C" int bfd_gaussian_filter3d(int device, int dtype, const void *in, void
     if (kernelMs) *kernelMs = 0.f;
     if (n == 0) return 0;
 
-    const int64_t N[3] = {N1, N2, N3};
     DevTemp<char> da, db;
     Events ev;
     BFD_STEP(da.alloc(n * esz));
@@ -288,21 +317,8 @@ extern "C" int bfd_gaussian_filter3d(int device, int dtype, const void *in, void
     BFD_STEP(hipMemcpy(da, in, n * esz, hipMemcpyHostToDevice));
     BFD_STEP(ev.create());
     BFD_STEP(ev.record(0));
-    char *src = da, *dst = db;
-    for (int a = 0; a < 3; a++) {
-        if (!(sigma[a] > 1e-15)) continue;            // scipy skips the axis
-        gauss_args p;
-        p.outer = a == 0 ? 1 : (a == 1 ? N1 : N1 * N2);
-        p.m = N[a];
-        p.inner = a == 0 ? N2 * N3 : (a == 1 ? N3 : 1);
-        p.r = radius[a]; p.mode = mode; p.T = 0; p.cval = cval;
-        memset(p.w, 0, sizeof p.w);
-        gauss_weights(sigma[a], p.r, p.w);
-        if (dtype == 1) launch_gauss_axis<float>((const float *)src, (float *)dst, p);
-        else launch_gauss_axis<double>((const double *)src, (double *)dst, p);
-        std::swap(src, dst);
-    }
-    BFD_STEP(hipGetLastError());
+    void *src = da.p;
+    BFD_STEP(bfd_stage_gaussian3d(dtype, da.p, db.p, N1, N2, N3, sigma, radius, mode, cval, &src));
     BFD_STEP(ev.record(1));
     BFD_STEP(ev.sync(1));
     BFD_STEP(ev.elapsed(kernelMs, 0, 1));

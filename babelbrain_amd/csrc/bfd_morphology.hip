@@ -27,6 +27,7 @@
 #include "bfd_call.h"
 #include "bfd_scan.h"
 #include "bfd_morph_core.h"
+#include "bfd_step1_stages.h"
 
 namespace {
 
@@ -374,6 +375,24 @@ static label_dims make_label_dims(int64_t N1, int64_t N2, int64_t N3, int connec
 
 }  // namespace
 
+hipError_t bfd_stage_box_morphology(uint64_t *a, uint64_t *b, int N1, int N2, int N3, const int *s, int dilate, int borderValue, uint64_t **result)
+{
+    const morph_dims g = morph_make_dims(N1, N2, N3);
+    const long nWords = (long)N1 * N2 * g.nW;
+    const unsigned wb = blocks_for(nWords, MB_THREADS, MAX_BLOCKS);
+    const uint64_t fill = borderValue ? ~(uint64_t)0 : 0;
+    uint64_t *src = a, *dst = b;
+    for (int axis = 2; axis >= 0; axis--) {
+        if (s[axis] == 1) continue;
+        int lo, hi;
+        morph_box_taps(s[axis], dilate != 0, &lo, &hi);
+        hipLaunchKernelGGL(morph_box_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, axis, lo, hi, dilate, fill);
+        std::swap(src, dst);
+    }
+    *result = src;
+    return hipGetLastError();
+}
+
 extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3,
                                        const uint8_t *structure, int s1, int s2, int s3, int iterations, int borderValue, float *kernelMs)
 {
@@ -428,13 +447,9 @@ extern "C" int bfd_binary_morphology3d(int device, int op, const uint8_t *in, ui
         const uint64_t fill = borderValue ? ~(uint64_t)0 : 0;
         for (int it = 0; it < iterations; it++) {
             if (box) {
-                for (int axis = 2; axis >= 0; axis--) {
-                    if (s[axis] == 1) continue;
-                    int lo, hi;
-                    morph_box_taps(s[axis], dilate != 0, &lo, &hi);
-                    hipLaunchKernelGGL(morph_box_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, axis, lo, hi, dilate, fill);
-                    std::swap(src, dst);
-                }
+                uint64_t *res = src;
+                BFD_STEP(bfd_stage_box_morphology(src, dst, (int)N1, (int)N2, (int)N3, s, dilate, borderValue, &res));
+                if (res != src) std::swap(src, dst);
             } else {
                 hipLaunchKernelGGL(morph_general_pass, dim3(wb), dim3(MB_THREADS), 0, 0, src, dst, g, nWords, taps[dilate], dilate, fill);
                 std::swap(src, dst);

@@ -848,6 +848,43 @@ int bfd_pseudo_ct_convert3d(int device, int dtype /*1 f32, 3 f64*/, const void *
 int bfd_select_component3d(int device, const uint8_t *in, uint8_t *out, int64_t N1, int64_t N2, int64_t N3, int connectivity, int tie /*0 highest, 1 lowest*/,
                            int64_t *info /*[2]*/, float *kernelMs /*may be NULL*/);
 
+/* ---- the bone-rim partial-volume correction of the CT: BabelBrain/BabelDatasetPreps.py, bMaximizeBoneRim (:935-1017), as one call ----
+ * Conventions of the sections above: HOST pointers, numpy C order (k fastest), fewer than 2^31 voxels, inputs never written (out may be ct itself),
+ * 0 / -1 / -3 / -10, text in bfd_last_error, kernelMs the sum of the timed sections, outputs untouched on a refusal, nothing held on the device
+ * after the call. tests/bonerim_oracle.py restates the definition in numpy and scipy.
+ *
+ * bfd_bone_rim_correct3d (csrc/bfd_bonerim.hip). ct float32, bone read as != 0, box = RatioCTVoxels already made odd and at least 3 (:942-946):
+ *     floor given:  ct = floor where bone and ct < floor                                   (:931-933; out carries these values too)
+ *     dense    = ct >= interiorThreshold                                                   (:951)
+ *     interior = binary_erosion(bone, ones(box)), border value 0, one iteration            (:953)
+ *     gmean    = the given mean, or the exact mean of ct over dense (below)                (:957)
+ *     d2       = the exact squared Euclidean distance to the nearest interior voxel        (:964-967)
+ *     edge     = bone and not interior                                                     (:970)
+ *     w        = exp(-sqrt(d2) / distanceScale), float64, exp as numpy takes it on the CPU at hand: a table over d2 formed on the host (:974-976)
+ *     bi, bm   = gaussian_filter(ct * dense), gaussian_filter(float32(dense)), float32, sigma on the three axes, reflect, truncate 4 (:980-986)
+ *     lm       = bm > float32(1e-6) ? bi / bm : gmean, float32                             (:988)
+ *     at edge voxels: c = o + w * (lm - o), the subtraction float32, the rest float64; delta = min(c - o, maxBoost); out = float32(o + delta),
+ *     rounded to nearest even (:994-1010). Every other voxel keeps its bits.
+ *   globalMean   float32, in and out. globalMeanGiven 1: the value is used as it is (numpy's own .mean() gives the reference's bits). 0: the
+ *                entry computes gmean = float32(double(S) / (16384.0 * count)), S = the sum of ct * 2^14 over dense as 64-bit integers, which is
+ *                exact and the same in every run, and writes it back. numpy's pairwise float32 sum may differ from it by an ulp or so; it reaches
+ *                the edge voxels with bm <= 1e-6 alone, which stats counts
+ *   stats        int64 [8] = {bone, interior, dense, edge voxels; edge voxels that took gmean; edge voxels whose delta the clip lowered; voxels
+ *                whose stored bits the blend changed; the largest d2 over edge voxels}
+ *   interior (uint8), d2 (int32), bi, bm (float32): [N1][N2][N3], each may be NULL: the fields, for tests
+ * -1 before a device is looked for, in this order: a null pointer (ct, bone, out, box, globalMean, stats); a negative dimension; a dimension above
+ * 16384; 2^31 voxels or more; a box size that is even or outside 3 .. 31; interiorThreshold not finite or below 512 (every float32 from 512 up is a
+ * multiple of 2^-14: the exact sum rests on it); maxBoost a NaN; distanceScale not finite or not positive; sigma not finite or not positive; the
+ * radius int(4 sigma + 0.5) above 127; a floor that is not finite; globalMeanGiven outside 0 .. 1; a given mean that is not finite; an output
+ * overlapping an input or another output (out == ct is no overlap). -1 AFTER the device pick, the preparation pass and the erosion, with kernelMs
+ * zeroed and nothing else written, in this order: an empty volume; a CT value that is not finite; a dense value at or above 2^17; no dense voxel
+ * (unless a mean is given); an erosion that leaves no interior voxel. The text of each of these, and of no other error, reads
+ * "bfd_bone_rim_correct3d: refused data: ...". Device memory: 25 B per voxel, 3 bits per voxel of packed masks, 1 B per voxel with interior, the table. */
+int bfd_bone_rim_correct3d(int device, const float *ct, const uint8_t *bone, float *out, int64_t N1, int64_t N2, int64_t N3, const int32_t *box /*[3]*/,
+                           float interiorThreshold, double maxBoost, double distanceScale, double sigma, const float *floorValue /*may be NULL*/,
+                           float *globalMean, int globalMeanGiven, int64_t *stats /*[8]*/, uint8_t *interior /*may be NULL*/, int32_t *d2 /*may be NULL*/,
+                           float *bi /*may be NULL*/, float *bm /*may be NULL*/, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

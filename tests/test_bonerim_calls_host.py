@@ -1,0 +1,73 @@
+"""The call contract of bfd_bone_rim_correct3d without a device: every argument error of include/babelfdtd.h in the header's order, with nothing
+written, and -3 where no device is visible (where one is, tests/test_bonerim_gpu.py holds a bad ordinal to -3 and the data refusals to their
+texts)."""
+import os
+
+import numpy as np
+import pytest
+
+from babelbrain_amd import BoneRim as BR, _engine
+from tests import bonerim_calls as TC
+
+
+@pytest.fixture(scope='module')
+def lib():
+    if not os.path.exists(_engine.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _engine.load_library()
+
+
+def test_abi_symbol_and_version(lib):
+    assert lib.bfd_abi_version() == 7
+    assert TC.ENTRY in _engine.ABI_SYMBOLS and hasattr(lib, TC.ENTRY)
+
+
+def test_abi_refuses_before_a_device_in_the_header_s_order(lib):
+    """-1 with the text of the first fault the header lists, whether or not a device exists, with every output and kernelMs untouched."""
+    words = {n: w for n, w, _ in TC.FAULTS}
+    for names, first in TC.ordered_plants():
+        c = TC.planted(names)
+        assert c.run(lib) == -1, names
+        text = lib.bfd_last_error().decode()
+        assert text.startswith(TC.ENTRY) and words[first] in text and BR.DATA_REFUSED not in text, (names, first, text)
+        assert c.untouched(), names
+    for name in TC.REQUIRED:
+        c = TC.Case(**{'want_' + name: False})
+        assert c.run(lib) == -1 and 'null' in lib.bfd_last_error().decode() and c.untouched(), name
+    for kw in TC.MORE:
+        c = TC.Case(**kw)
+        assert c.run(lib) == -1 and c.untouched(), (kw, lib.bfd_last_error().decode())
+    # out overlapping ct in part, out on the bone mask's bytes, a field on the CT's bytes
+    c = TC.Case()
+    both = np.zeros(c.ct.size + 4, np.float32)
+    both[:c.ct.size] = c.ct.ravel()
+    c.ct = both[:c.ct.size].reshape(c.N)
+    c.outputs['out'] = both[4:].reshape(c.N)
+    c.pristine = c.snapshot()
+    assert c.run(lib) == -1 and 'overlap' in lib.bfd_last_error().decode() and c.untouched()
+    c = TC.Case()
+    c.outputs['interior'] = c.bone
+    c.pristine = c.snapshot()
+    assert c.run(lib) == -1 and 'overlap' in lib.bfd_last_error().decode() and c.untouched()
+    c = TC.Case()
+    c.outputs['d2'] = c.ct.view(np.int32)
+    c.pristine = c.snapshot()
+    assert c.run(lib) == -1 and 'overlap' in lib.bfd_last_error().decode() and c.untouched()
+
+
+def test_without_a_device_the_call_returns_minus_3(lib):
+    if lib.bfd_device_count() > 0:
+        c = TC.Case()
+        assert c.run(lib, device=lib.bfd_device_count()) == -3 and c.untouched()
+        return
+    for kw in ({}, dict(floor=300.0), dict(given=1, mean=np.float32(1500.0)), dict(want_interior=False, want_d2=False, want_bi=False, want_bm=False),
+               dict(box=np.array([31, 3, 5], np.int32), sigma=31.0, distanceScale=15.5)):
+        c = TC.Case(**kw)
+        assert c.run(lib) == -3 and c.untouched(), kw
+    c = TC.Case()
+    c.outputs['out'] = c.ct                                         # in place: no overlap
+    c.pristine = c.snapshot()
+    assert c.run(lib) == -3 and c.untouched()
+    c = TC.Case(N=(0, 6, 9))                                        # the empty volume is refused after the device pick
+    assert c.run(lib) == -3 and c.untouched()
