@@ -341,7 +341,17 @@ def _bhte_inputs(fields, MaterialMap, MaterialList, dx, dt, blood_rho, blood_ct,
         dose = np.empty((N1, N2, N3), np.float32)
     initT = np.ascontiguousarray(MaterialList['InitTemperature'], np.float32)
     idx = None
-    if MonitoringPointsMap is not None:
+    if hasattr(MonitoringPointsMap, 'ids') and hasattr(MonitoringPointsMap, 'indices'):
+        # the sparse form (ThermalAnalysis.MonitoringPoints): the same rows as its dense map gives below, without a pass over the volume
+        if tuple(MonitoringPointsMap.shape) != (N1, N2, N3):
+            raise ValueError('MonitoringPointsMap must have the shape of the pressure field')
+        ids, lin = np.asarray(MonitoringPointsMap.ids), np.asarray(MonitoringPointsMap.indices, np.int64)
+        if ids.shape != lin.shape or ids.ndim != 1 or np.unique(lin).size != lin.size:
+            raise ValueError('MonitoringPointsMap needs one id for each of its distinct linear indices')
+        if lin.size and (lin.min() < 0 or lin.max() >= N1 * N2 * N3 or ids.min() == 0):
+            raise ValueError('MonitoringPointsMap holds an index outside the volume or the id 0')
+        idx = np.ascontiguousarray(lin[np.lexsort((lin, ids))], np.uint32)          # by id, then by linear index: flatnonzero, then the stable sort
+    elif MonitoringPointsMap is not None:
         mp = np.asarray(MonitoringPointsMap)
         if mp.shape != (N1, N2, N3):
             raise ValueError('MonitoringPointsMap must have the shape of the pressure field')

@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     'bfd_paint_components3d', 'bfd_quantize_values3d', 'bfd_clear_beyond_bone3d',
     'bfd_label_survey3d', 'bfd_assemble_material_map3d', 'bfd_sdr_rays3d',
     'bfd_integer_histogram3d', 'bfd_order_statistics3d', 'bfd_uniform_histogram3d', 'bfd_pseudo_ct_candidates3d', 'bfd_pseudo_ct_convert3d',
-    'bfd_select_component3d', 'bfd_bone_rim_correct3d',
+    'bfd_select_component3d', 'bfd_bone_rim_correct3d', 'bfd_class_extrema3d', 'bfd_loss_survey3d',
 ]
 
 
@@ -247,6 +247,11 @@ def load_library():
     lib.bfd_bone_rim_correct3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_double,
                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_float)]
+    lib.bfd_class_extrema3d.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_loss_survey3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

@@ -1,5 +1,5 @@
 """What the eleven Step-1 drop-ins (MedianFilter, BinaryClosing, LabelImage, Resample, Voxelize, MappingFilter, DistanceTransform, GaussianFilter, ConformalMask,
-TissueMask, PseudoCT) and Domain, the domain setup of Step 2, share on the way to the C ABI: the
+TissueMask, PseudoCT), Domain, the domain setup of Step 2, and ThermalAnalysis, the exposure analysis of Step 3, share on the way to the C ABI: the
 device pick of their Init* functions, the bool -> uint8 normalisation and the call itself. Each module keeps its own `_device` and `last_kernel_ms`."""
 import numpy as np
 

@@ -1,11 +1,12 @@
-// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip and bfd_bonerim.hip (and by no other
+// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip, bfd_bonerim.hip and bfd_thermal.hip (and by no other
 // source: the solver's translation units do not see this file). Host code only.
 //
-// The contract of the twenty-five entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
+// The contract of the twenty-seven entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
 // bfd_voxelize_mesh, bfd_voxel_points, bfd_map_values3d, bfd_distance_transform_edt3d, bfd_gaussian_filter3d, bfd_voxel_scatter3d,
 // bfd_voxelize_scatter3d, bfd_paint_components3d, bfd_quantize_values3d, bfd_clear_beyond_bone3d,
 // bfd_label_survey3d, bfd_assemble_material_map3d, bfd_sdr_rays3d, bfd_integer_histogram3d, bfd_order_statistics3d, bfd_uniform_histogram3d,
-// bfd_pseudo_ct_candidates3d, bfd_pseudo_ct_convert3d, bfd_select_component3d, bfd_bone_rim_correct3d). Every entry takes these steps in this order:
+// bfd_pseudo_ct_candidates3d, bfd_pseudo_ct_convert3d, bfd_select_component3d, bfd_bone_rim_correct3d,
+// bfd_class_extrema3d, bfd_loss_survey3d). Every entry takes these steps in this order:
 //    1. argument errors: -1 and a text, each before a device is looked for, in the entry's own order
 //    2. pick_device: -3 where no device is visible or the ordinal is out of range
 //    3. kernelMs zeroed (after the device pick)
@@ -25,7 +26,9 @@
 // first reduction, with kernelMs zeroed and nothing else written. So do bfd_integer_histogram3d (an empty volume, a value that is not finite, a
 // range over 65535), bfd_order_statistics3d (nothing selected, a rank beyond the count), bfd_uniform_histogram3d (a selected value that is not
 // finite), bfd_pseudo_ct_candidates3d (an empty volume, a quotient that is not finite) and bfd_bone_rim_correct3d (an empty volume, a value that is not
-// finite, a dense value at or above 2^17, no dense voxel, no interior voxel); include/babelfdtd.h lists each in its order.
+// finite, a dense value at or above 2^17, no dense voxel, no interior voxel), and bfd_class_extrema3d and bfd_loss_survey3d (an id that is not below
+// nMat, a value that is not finite; their kernelMs is the sum over the launches, one for every 4 volumes or for every field); include/babelfdtd.h lists
+// each in its order.
 // On any other refusal (-1, -3) the outputs and kernelMs are untouched. Everything a call holds on the device, events included, is released on every way
 // out: the next call of the process starts from nothing.
 #pragma once

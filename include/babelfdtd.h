@@ -885,6 +885,61 @@ int bfd_bone_rim_correct3d(int device, const float *ct, const uint8_t *bone, flo
                            float *globalMean, int globalMeanGiven, int64_t *stats /*[8]*/, uint8_t *interior /*may be NULL*/, int32_t *d2 /*may be NULL*/,
                            float *bi /*may be NULL*/, float *bm /*may be NULL*/, float *kernelMs /*may be NULL*/);
 
+/* ---- the Step-3 exposure analysis: ThermalModeling/CalculateTemperatureEffects.py, AnalyzeLosses (:94-256) and the extrema lines (:996-1001,
+ * :1126-1144) ----
+ * Conventions of the sections above: HOST pointers, numpy C order (k fastest, as bfd_bhte_run_volumes takes its volumes), fewer than 2^31 voxels,
+ * inputs never written (waterOut may be pw itself), 0 / -1 / -3 / -10, text in bfd_last_error, kernelMs the sum of the timed sections, outputs
+ * untouched on a refusal, nothing held on the device after the call. tests/thermal_oracle.py restates both definitions in numpy.
+ *   map       material ids of idBytes 1, 2 or 4 (uint8, uint16, uint32), [N1][N2][N3]
+ *   classOf   uint8 [nMat], 1 <= nMat <= 65536: bit c set = the id belongs to class c, 8 classes. Every selection of :864-906 and :165-179
+ *             (isin, ==, !=, >, ranges, complements) is such a table
+ * Results are the same bytes in every run: maxima travel as (value, index) words through integer atomics, sums are added in one fixed order; no
+ * floating-point atomics. Values are compared as IEEE does, -0 == +0; float32 denormals are values like any other.
+ * Refused data (-1 AFTER the device pick and the pass over the volumes, kernelMs zeroed, nothing else written), in this order: an id that is not
+ * below nMat; a value of any volume that is not finite. The text of each, and of no other error, reads "<entry>: refused data: ...".
+ *
+ * bfd_class_extrema3d (csrc/bfd_thermal.hip): nVol float32 volumes (volumes[v] -> [N1][N2][N3]) over one map in one pass.
+ *   count  [8]        voxels of class c
+ *   maxIn  [nVol][8]  the maximum of x over the class, argIn the lowest linear index that attains it: X[Sel].max() of :1126-1138 and
+ *                     p_map[SelBrain].argmax() with the value read (:1142-1144). An empty class: maxIn 0, argIn -1
+ *   maxKey [nVol][8]  the maximum over ALL voxels of key = in ? x : x * 0.0f, argKey the lowest linear index whose key equals it: exactly
+ *                     np.argmax(X * Sel.astype(np.float32)) of :996-1001. A class of negative values loses to the first +-0 outside it; an
+ *                     all-zero product gives index 0. maxKey is +0 where the key is a zero of either sign
+ * More than 4 volumes take one pass over the map for every 4. An empty volume returns 0 after the device pick: count 0, maxima 0, indices -1.
+ * -1, in this order: a null pointer (volumes, count, maxIn, argIn, maxKey, argKey, map, classOf); a negative dimension; 2^31 voxels or more;
+ * idBytes outside {1, 2, 4}; nMat outside 1 .. 65536; nVol below 1; a null volume; an output overlapping an input or another output.
+ * Device memory: the volumes and the map. */
+int bfd_class_extrema3d(int device, const float *const *volumes /*[nVol]*/, int nVol, const void *map, int idBytes, int64_t N1, int64_t N2, int64_t N3,
+                        const uint8_t *classOf /*[nMat]*/, int nMat, int64_t *count /*[8]*/, float *maxIn, int64_t *argIn, float *maxKey,
+                        int64_t *argKey, float *kernelMs /*may be NULL*/);
+
+/* bfd_loss_survey3d (csrc/bfd_thermal.hip): the volume work of AnalyzeLosses for nFields focal spots. p, pw float32 [nFields][N1][N2][N3]: the
+ * pressure amplitude in tissue and in water. Class bit 0 = brain (SelBrain), bit 1 = selregion (:165-179); brainMask, uint8 [N1][N2][N3] read as
+ * != 0, replaces bit 0 where given. rho, c float64 [nMat] (Density, SoS); rhoWater, cWater = row 0 of the reference's tables; dx2 = (xf[1] - xf[0])^2.
+ * Per field f:
+ *   maxTissue, argTissue   the maximum of p with everything outside the brain set to 0.0f, and the first linear index that attains it (:189-195)
+ *   maxWater, argWater     the same for pw with selregion set to 0.0f (:181-185)
+ *   eWaterRaw [f][N3]      for every k, the sum over (i, j) of the terms of pw BEFORE the zeroing (:162-163 read plane 2 before :181)
+ *   eWater    [f][N3]      of the terms of the zeroed water field (:203-204, :211-212)
+ *   eTissue   [f][N3]      of the terms of the brain-masked p (:152, :207-208, :215-216)
+ * A term is (((double)(float)((x * x) / 2.0f) / R) / C) * dx2: the square and the halving in float32 (denormals kept), then three float64
+ * operations, each rounded once; (R, C) = (rhoWater, cWater) for water and (rho[id], c[id]) for tissue. These are the reference's types under
+ * NumPy >= 2 promotion (under numpy 1.x its water energies are float32 sums). A plane's terms are added in a fixed order: rows (i, j) in ascending
+ * order inside chunks of 128 rows, the chunks by a tree of 32 to a node, every node in ascending order; within (n - 1) u / (1 - (n - 1) u) of the
+ * exact sum, n = N1 N2, u = 2^-53.
+ * All N3 planes come from the one pass; the caller picks planes 2, cz, czw and czr.
+ *   waterOut  may be NULL, or [nFields][N1][N2][N3]: the zeroed water field (the in-place store of :181); it may equal pw exactly
+ * An empty volume returns 0 after the device pick: maxima 0, indices -1, sums 0.
+ * -1, in this order: a null pointer (p, pw, rho, c, the four maxima and indices, the three sums, map, classOf); a negative dimension; 2^31 voxels or
+ * more; idBytes outside {1, 2, 4}; nMat outside 1 .. 65536; nFields below 1; rhoWater or cWater not finite or not positive; a rho or c not finite or
+ * not positive (a voxel set to 0.0f then has the term +0 and is left out of the sum); dx2 not finite or negative; nFields volumes of 2^40 voxels or
+ * more; an output overlapping an input or another output other than waterOut == pw.
+ * Device memory: one tissue field, one water field (nFields of them with waterOut), the map, the mask, 24 B per 128 rows and k of partial sums. */
+int bfd_loss_survey3d(int device, const float *p, const float *pw, int nFields, const void *map, int idBytes, int64_t N1, int64_t N2, int64_t N3,
+                      const uint8_t *classOf /*[nMat]*/, int nMat, const uint8_t *brainMask /*may be NULL*/, const double *rho, const double *c,
+                      double rhoWater, double cWater, double dx2, float *maxTissue, int64_t *argTissue, float *maxWater, int64_t *argWater,
+                      double *eWaterRaw, double *eWater, double *eTissue, float *waterOut /*may be NULL*/, float *kernelMs /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
