@@ -110,7 +110,7 @@ static __device__ __forceinline__ long css_index(const bfd_dev &d, long c)
 // 32 planes); run = (bx + tilesX*by, kbeg | kend<<16, flags: bit0 solid, bit1 lossy, bit2 UNI, bit3 PML, bit4 LEAN, material
 // id of UNI runs). n* counters after nSolidB are in 64x8x8 sub-tiles, for reporting.
 // BFD_RUN_ADV_VZ in the flags of a run: stress_fluid stores the new Vz of the run's planes kbeg+1 .. kend-3 and velocity_fluid leaves Vz alone there
-// (bfd_api.hip, "advanced Vz"); both kernels read the same record. bfd_tiles::advVz = some run of the current lists carries it.
+// (bfd_lists.hip, "advanced Vz"); both kernels read the same record. bfd_tiles::advVz = some run of the current lists carries it.
 #define BFD_RUN_ADV_VZ 512
 // kernel classes of the per-kernel timing / byte accounting (bfd_timing_kernels, bfd_algorithmic_bytes)
 enum { BFD_K_STRESS_FLUID = 0, BFD_K_STRESS_SOLID = 1, BFD_K_STRESS_SHEAR = 2, BFD_K_VELOCITY_FLUID = 3, BFD_K_VELOCITY_SOLID = 4,
@@ -122,95 +122,112 @@ void bfd_kmark(bfd_sim *sim, int cls, int end, hipStream_t st);
 // maps of bfd_tiles::xmap: fluid stress / fluid velocity / solid stress / solid velocity (plain runs) by part 0, 1, 2; the two pieces of solid
 // runs in the absorbing layer; the fused runs
 enum { BFD_XM_SF = 0, BFD_XM_VF = 3, BFD_XM_SS = 6, BFD_XM_VS = 9, BFD_XM_VSP_LO = 12, BFD_XM_VSP_HI = 13, BFD_XM_FUSED = 14, BFD_XMAP_COUNT = 15 };
-struct bfd_tiles { bfd_sim *ktimer; int nMat; int4 *runs;
-                   unsigned *shearCells; float *shearCoef; long nShear, shearLowEnd, shearHighBeg;   /* sparse shear list */
-                   unsigned *shearCodes; float *shearTab; long nShearExplicit;   /* per listed cell a byte per edge: 0 inactive, 1 + m = one material around the edge (coefficients from shearTab[8 m], [8 m + 1]; the cell's own AP, BP, AS2, BS2 at [8 m + 4 ..]), 255 = explicit coefficients in shearCoef; number of explicit edges */
-                   int4 *runsAll; int nAll, nAllB;   /* compact solid state: every run, fluid and solid, in list order [boundary | interior] -- the stress half-step's one launch of the fluid kernel */
+struct bfd_tiles { bfd_sim *ktimer = nullptr; int nMat = 0; int4 *runs = nullptr;
+                   unsigned *shearCells = nullptr; float *shearCoef = nullptr; long nShear = 0, shearLowEnd = 0, shearHighBeg = 0;   /* sparse shear list */
+                   unsigned *shearCodes = nullptr; float *shearTab = nullptr; long nShearExplicit = 0;   /* per listed cell a byte per edge: 0 inactive, 1 + m = one material around the edge (coefficients from shearTab[8 m], [8 m + 1]; the cell's own AP, BP, AS2, BS2 at [8 m + 4 ..]), 255 = explicit coefficients in shearCoef; number of explicit edges */
+                   int4 *runsAll = nullptr; int nAll = 0, nAllB = 0;   /* compact solid state: every run, fluid and solid, in list order [boundary | interior] -- the stress half-step's one launch of the fluid kernel */
                    /* compact solid state (bfd_dev::cssRow): the row table and where the ten compact arrays (Sxx Syy Sxy Sxz Syz Rxx Ryy Rxy Rxz Ryz, list order) live:
                       cssHosted = inside the full-volume buffers of their own fields (unused otherwise in this mode; the placement has spread those over the memory
                       regions, which the sparse kernel's ten streams need as much as the marching kernels' do: 0.253 against 0.266-0.29 ms), from allocation plane 4 on
                       (the planes a Z-neighbour exchanges stay free); else css = one block [10][cssCap] (solid cells too many for that) */
-                   unsigned *cssRow; float *css; long cssCap; bool cssHosted;
-                   float *shearR;   /* full-volume solid state (BFD_COMPACT_SOLID=0) only: memory variables Rxy, Rxz, Ryz of the listed cells, [3][nShear] in list order, beside the list (dense, coalesced); the full-volume arrays are filled from here on demand (bfd_get_field). Null when the state is compact */
-                   int nFluid, nFluidB, nSolid, nSolidB, nSolidBP /* leading boundary runs that touch the absorbing layer */, nSolidIP /* trailing interior ones */, nFused /* runs of the fused kernel, after the solid runs */;
-                   int nLossless, nLossy, nSolidSub, nUni, nPml, nLean, nFusedSub;
-                   bool advVz;
+                   unsigned *cssRow = nullptr; float *css = nullptr; long cssCap = 0; bool cssHosted = false;
+                   float *shearR = nullptr;   /* full-volume solid state (BFD_COMPACT_SOLID=0) only: memory variables Rxy, Rxz, Ryz of the listed cells, [3][nShear] in list order, beside the list (dense, coalesced); the full-volume arrays are filled from here on demand (bfd_get_field). Null when the state is compact */
+                   int nFluid = 0, nFluidB = 0, nSolid = 0, nSolidB = 0, nSolidBP = 0 /* leading boundary runs that touch the absorbing layer */, nSolidIP = 0 /* trailing interior ones */, nFused = 0 /* runs of the fused kernel, after the solid runs */;
+                   int nLossless = 0, nLossy = 0, nSolidSub = 0, nUni = 0, nPml = 0, nLean = 0, nFusedSub = 0;
+                   bool advVz = false;
                    /* cost-balanced block -> run maps (round 4): block b of a launch runs on XCD slot b & 7 and takes run seg[slot] + (b >> 3) of
                       the launched range if that is below seg[slot + 1]; the launch has 8 x maxcnt blocks. One map of 10 ints (seg[0..8], maxcnt)
                       per launched range and kernel class, on the device in xmap, on the host in xmapH. */
-                   int *xmap; int xmapH[BFD_XMAP_COUNT][10]; };
+                   int *xmap = nullptr; int xmapH[BFD_XMAP_COUNT][10] = {}; };
 
+// Streamed source table (large PulseSource; bfd_sources.hip): the caller's float64 table stays on the host, time tiles of
+// tileSteps steps are converted to float32 [step][source] by a packer job and uploaded double-buffered. pulseHost = null: no table is streamed.
+struct bfd_source_tiles {
+    const double *pulseHost = nullptr; int tileSteps = 0, nTiles = 0;
+    float *tileDev[2] = {}, *tilePinned[2] = {}; int tileLoaded[2] = {-1, -1}, tilePacked[2] = {-1, -1};
+    hipEvent_t evTile[2] = {}; bool evTileUsed[2] = {};
+    hipEvent_t evRead[2][2] = {}; bool evReadUsed[2][2] = {};      // [buffer][0 = engine stream, 1 = a side stream]: behind the last kernels that read the tile the buffer holds
+    std::future<void> packJob[2];
+    // The two ends of what the table holds (device tiles, pinned buffers, packer jobs, events). release: back to "no table streamed"; the
+    // events stay, the next table reuses them. destroy: release, and the events too (the engine is going away).
+    void release(bfd_sim *s);
+    void destroy(bfd_sim *s);
+};
+
+// Every member starts from its initialiser here; bfd_create sets what depends on the configuration or the environment. bfd_dev has none (it is passed
+// to kernels by value and stays a plain aggregate): bfd_create clears it.
 struct bfd_sim {
-    bfd_config cfg;
+    bfd_config cfg = {};
     bfd_dev d;
-    hipStream_t stream;
-    bool ownStream;
-    int step;
-    size_t nloc, nalloc;            // owned voxels, allocated voxels per state array
-    float *stateBase[15];           // allocation bases
-    uint16_t *matBase;
-    uint8_t *clsBase; bool classesReady;
-    bool placementDone, haloHandedOut;   // bfd_prepare: the per-voxel arrays may be moved until a halo pointer has been given out
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    int step = 0;
+    size_t nloc = 0, nalloc = 0;    // owned voxels, allocated voxels per state array
+    float *stateBase[15] = {};      // allocation bases
+    uint16_t *matBase = nullptr;
+    uint8_t *clsBase = nullptr; bool classesReady = false;
+    bool placementDone = false, haloHandedOut = false;   // bfd_prepare: the per-voxel arrays may be moved until a halo pointer has been given out
     std::string placementNote;           // what bfd_choose_placement found and did (bfd_placement_note; bfd_placement.hip)
     std::vector<void *> searched;        // state buffers that a search found in another memory region: kept for the next engine of this process when this one is destroyed
-    int placementMode; int64_t placementLimit;   // bfd_set_placement: 0 = off; bytes the search may hold at a time (-1 = default rule)
-    float *tables;                  // 7*nMat
-    float *profiles;                // 4*(N1+N2+N3)
+    int placementMode = 1; int64_t placementLimit = -1;   // bfd_set_placement: 0 = off; bytes the search may hold at a time (-1 = default rule)
+    float *tables = nullptr;        // 7*nMat
+    float *profiles = nullptr;      // 4*(N1+N2+N3)
     std::vector<void *> allocs;     // everything to free
-    int64_t devBytes;
-    bool haveMaterials, haveMap;
-    bfd_tiles tiles; bool tilesReady;   // variants 2, 3, 4
-    bool pingpong;                      // variant 4 on a whole domain: second copies of V, Szz, Rzz (ppBase), swapped every step
-    float *ppBase[5];
-    int zchunk;                         // planes of the longest z-run (8, 16 or 32), chosen per grid
-    double cmax;
-    // sources
-    int64_t nSrcVox, srcLowEnd, srcHighBeg;   // sources sorted by voxel: [0,lowEnd) first z-chunk, [highBeg,n) last z-chunk
-    uint32_t *srcLin, *srcRow; float *srcW[3]; float *pulseT; int nSources, lengthSource;
-    // streamed source table (large PulseSource): the caller's float64 table stays on the host, time tiles of
-    // tileSteps steps are converted to float32 [step][source] by a packer job and uploaded double-buffered
-    const double *pulseHost; int tileSteps, nTiles;
-    float *tileDev[2], *tilePinned[2]; int tileLoaded[2], tilePacked[2];
-    hipEvent_t evTile[2]; bool evTileUsed[2];
-    hipEvent_t evRead[2][2]; bool evReadUsed[2][2];      // [buffer][0 = engine stream, 1 = a side stream]: behind the last kernels that read the tile the buffer holds
-    std::future<void> packJob[2];
+    int64_t devBytes = 0;
+    bool haveMaterials = false, haveMap = false;
+    bfd_tiles tiles; bool tilesReady = false;   // variants 2, 3, 4
+    bool pingpong = false;              // variant 4 on a whole domain: second copies of V, Szz, Rzz (ppBase), swapped every step
+    float *ppBase[5] = {};
+    int zchunk = 0;                     // planes of the longest z-run (8, 16 or 32), chosen per grid
+    double cmax = 0;
+    // sources (bfd_sources.hip)
+    int64_t nSrcVox = 0, srcLowEnd = 0, srcHighBeg = 0;   // sources sorted by voxel: [0,lowEnd) first z-chunk, [highBeg,n) last z-chunk
+    uint32_t *srcLin = nullptr, *srcRow = nullptr; float *srcW[3] = {}; float *pulseT = nullptr; int nSources = 0, lengthSource = 0;
+    bfd_source_tiles srcTiles;      // the dense table streamed from the host instead of resident in pulseT
     // separable source (bfd_set_sources_separable; srcK = 0: the dense table above): row r at step n is
     // sum_k srcWeights[r*K + k] * srcSignals[n*K + k], in that order, in float32
-    int srcK; float *srcWeights, *srcSignals;
+    int srcK = 0; float *srcWeights = nullptr, *srcSignals = nullptr;
     // sensors
-    unsigned char *actBase; size_t actBytes; bool actReady;   // storage of bfd_dev::act; actReady = the map matches the state (cleared by setters and bfd_reset)
-    bool sensIsBox; int sensBox[5];    // the sensor set is a dense box of voxels: extents in x, y and its first voxel (i0, j0, local k0); captures then need no index list
-    int *sensEnt; bool sensEntValid;   // compact solid state: list entry of every sensor voxel (-1 = none), valid for the current list
-    int64_t nSensors; uint32_t *sensLin; float *sensOut; int nTs; int nSelS; int selS[BFD_MAP_COUNT];
-    double *dftAcc; float *dftPk; int dftBin;      // sensorMode 1: [nSelS][nSensors][2] running DFT sums, [nSelS][nSensors] running peaks
+    unsigned char *actBase = nullptr; size_t actBytes = 0; bool actReady = false;   // storage of bfd_dev::act; actReady = the map matches the state (cleared by setters and bfd_reset)
+    bool sensIsBox = false; int sensBox[5] = {};    // the sensor set is a dense box of voxels: extents in x, y and its first voxel (i0, j0, local k0); captures then need no index list
+    int *sensEnt = nullptr; bool sensEntValid = false;   // compact solid state: list entry of every sensor voxel (-1 = none), valid for the current list
+    int64_t nSensors = 0; uint32_t *sensLin = nullptr; float *sensOut = nullptr; int nTs = 0; int nSelS = 0; int selS[BFD_MAP_COUNT] = {};
+    double *dftAcc = nullptr; float *dftPk = nullptr; int dftBin = 0;      // sensorMode 1: [nSelS][nSensors][2] running DFT sums, [nSelS][nSensors] running peaks
     // accumulators
-    int nSelR; int selR[BFD_MAP_COUNT]; float *acc, *pk;
-    int accStart;
+    int nSelR = 0; int selR[BFD_MAP_COUNT] = {}; float *acc = nullptr, *pk = nullptr;
+    int accStart = 0;
     // Paired Pressure accumulation (bfd_api.hip, "paired accumulation"): pairEnv = BFD_PAIR_ACC is not 0; pendingAcc = the Pressure of the current Szz
     // has not been added to the maps at the cells of the fluid runs yet (the next stress half-step adds it together with its own, or a flush does);
     // pairDone = the stress half-step of the current step took the pairing flavour (the maps hold this step already; cleared where the step counter
     // advances); pairedLaunches counts the launches of the pairing stress flavour (bfd_paired_launches)
-    bool pairEnv, pendingAcc, pairDone; int64_t pairedLaunches;
-    // Advanced Vz (bfd_api.hip, "advanced Vz"): advEnv = BFD_ADV_VZ is not 0; midStep = a stress half-step of the current step has been queued and its
+    bool pairEnv = true, pendingAcc = false, pairDone = false; int64_t pairedLaunches = 0;
+    // Advanced Vz (bfd_lists.hip, "advanced Vz"): advEnv = BFD_ADV_VZ is not 0; midStep = a stress half-step of the current step has been queued and its
     // velocity half-step has not ended (cleared where the step counter advances and in bfd_reset): Vz is then of mixed time level in the runs that
     // carry BFD_RUN_ADV_VZ, and the run lists must stay as they are
-    bool advEnv, midStep;
+    bool advEnv = true, midStep = false;
     // timing
-    bool timing, perKernel;
-    hipEvent_t evBegin, evEnd;
+    bool timing = false, perKernel = false;
+    hipEvent_t evBegin = nullptr, evEnd = nullptr;
     std::vector<hipEvent_t> evStress, evVelocity;  // pairs
     std::vector<hipEvent_t> evK[BFD_K_COUNT];      // pairs per kernel class (perKernel == 2)
-    double algBytes[2][BFD_K_COUNT];               // algorithmic bytes per launch and class: [0] no accumulation, [1] Pressure RMS accumulated
+    double algBytes[2][BFD_K_COUNT] = {};          // algorithmic bytes per launch and class: [0] no accumulation, [1] Pressure RMS accumulated
     std::vector<hipEvent_t> evPool;
     // optional hipGraph replay of "plain" time steps (no accumulation, no sensor sample, no per-kernel timing) in
     // bfd_run, BFD_USE_GRAPH=1; measured slower than direct launches on ROCm 7.2, so off by default (see bfd_run)
-    int *stepDev;                   // device copy of the step counter (sources index their pulse with it inside a graph)
-    hipGraphExec_t stepGraph;       // BFD_GRAPH_STEPS time steps
-    hipStream_t captureStream;
-    int graphState;                 // 0 not tried, 1 ready, -1 unavailable (direct launches are used)
-    bool stepDevValid;
+    int *stepDev = nullptr;         // device copy of the step counter (sources index their pulse with it inside a graph)
+    hipGraphExec_t stepGraph = nullptr;       // BFD_GRAPH_STEPS time steps
+    hipStream_t captureStream = nullptr;
+    int graphState = 0;             // 0 not tried, 1 ready, -1 unavailable (direct launches are used)
+    bool stepDevValid = false;
 };
 #define BFD_GRAPH_STEPS 8
+// The class-specialised kernels (variants 0 / 3) updating the fields in place (no second copies of variant 4): the clause the three mode
+// predicates share -- advanced Vz and quiet runs (bfd_lists.hip), paired accumulation (pair_engine, bfd_api.hip)
+inline bool class_kernels_in_place(const bfd_sim *s) { return (s->cfg.kernelVariant == 0 || s->cfg.kernelVariant == 3) && !s->pingpong; }
+// Advanced Vz: between the stress and the velocity half-step of a time step the runs that carry BFD_RUN_ADV_VZ hold the new Vz at their inner planes
+// and the old one elsewhere; only the velocity half-step over the SAME lists completes it. What would rebuild the lists waits for the step to end.
+inline bool lists_held_mid_step(const bfd_sim *s) { return s->midStep && s->tilesReady && s->tiles.advVz; }
+#define BFD_REFUSE_MID_STEP(who) do { if (lists_held_mid_step(s)) BFD_FAIL(-6, who ": a stress half-step is outstanding: finish the time step first"); } while (0)
 
 void bfd_set_error(const std::string &s);
 #define BFD_HIP(call)                                                                              \
@@ -281,6 +298,31 @@ void bfd_launch_gather_flags(const bfd_sim *s, const uint32_t *in, long s1, long
 // ascending indices of the set flags among n, on the device: sel[0 .. *dcount). Queued on st; work = the select's scratch block, which the caller keeps
 // until it has synchronised (bfd_api.hip)
 hipError_t select_flagged(uint8_t *flags, uint32_t *sel, int *dcount, int n, hipStream_t st, DevTemp<char> &work);
+
+// inputs changed (bfd_api.hip): a recorded step graph holds stale pointers; the run lists, the activity map and a recorded step graph are out of
+// date, and (classes: materials, map, reflector) the cell classes
+void drop_step_graph(bfd_sim *s);
+void invalidate_lists(bfd_sim *s, bool classes = true);
+// the accumulating steps of this engine pair (bfd_api.hip, "paired accumulation"); quiet = quiet runs are or will be in use, nFluid = the fluid run count
+bool pair_engine(const bfd_sim *s, bool quiet, int nFluid);
+// what feeds source values to a time step (bfd_sources.hip):
+// the injection kernels of one part of a half-step (0 all, 1 = first + last z-chunk, 2 = the chunks between) at step s->step into the fields of `view`, on st
+int bfd_inject_part(bfd_sim *s, int part, const bfd_dev &view, hipStream_t st);
+// the injection node of a recorded plain step (hipGraph capture on cs): every source voxel, the step taken from the device's counter s->stepDev
+void bfd_record_injection(bfd_sim *s, hipStream_t cs);
+// everything the source path holds is released and the engine is back to "no sources"; final = the engine is being destroyed (the events go too)
+void bfd_release_sources(bfd_sim *s, bool final);
+// bfd_reset: the streamed table starts over (waits for the packer jobs; tiles are uploaded again on demand)
+void bfd_rewind_sources(bfd_sim *s);
+// the planner of the class-specialised path (bfd_lists.hip):
+// builds the run lists, the sparse shear list and the compact solid state from the cell classes (rebuilt mid-run: the solid state is carried over)
+int build_tile_lists(bfd_sim *s);
+// quiet runs: sets up (or switches off) the activity map for the current lists and step
+int setup_activity_map(bfd_sim *s);
+// points the ten compact views of bfd_dev at where the compact arrays live; again whenever the state buffers change hands (after the placement)
+void bind_compact_views(bfd_sim *s);
+// this engine lets the runs ahead of the wave front return at entry (needs the run lists built)
+bool quiet_runs_wanted(const bfd_sim *s);
 
 // an event from the engine's pool or a new one; null when none can be made (bfd_api.hip)
 hipEvent_t bfd_get_event(bfd_sim *s);

@@ -20,7 +20,7 @@
 // barriers per plane separate its writes from its reads).
 // The old fields must survive the step for the neighbours' recomputation: this variant keeps two copies of V, Szz, Rzz
 // (kernels read d.X, write d.XW; swapped after the step).
-// Eligible runs (bfd_api.hip, build_tile_lists): FLUID sub-tiles (no solid cell within 2 cells), no absorbing-layer cell
+// Eligible runs (bfd_lists.hip, build_tile_lists): FLUID sub-tiles (no solid cell within 2 cells), no absorbing-layer cell
 // within 2 cells, not the first / last sub-tile of the slab, velocity-type sources. Then every recomputed cell follows the
 // same arithmetic as its owner computes for it and every index stays inside the domain. UNI: one material, no reflector
 // in the grown region (coefficients are scalars); otherwise ids are loaded per region cell (runs with a reflector voxel in the

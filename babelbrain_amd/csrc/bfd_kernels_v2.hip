@@ -524,7 +524,7 @@ __device__ __forceinline__ unsigned fbits(float v) { return __float_as_uint(v); 
 // sources never touch Szz) and the new one that of this step, so ONE read-modify-write of the running sum here, in every second accumulating step, adds
 // both squares in the order the velocity kernel adds them, (acc + p_old^2) + p_new^2, and velocity_fluid leaves the sum alone (bfd_api.hip, "paired
 // accumulation"). The sum runs one plane ahead like the other streams; the peak is read where it is used, as in velocity_fluid_body.
-// advVz (runs that carry BFD_RUN_ADV_VZ: plain fluid runs outside the absorbing layer, not QUIET; bfd_api.hip, "advanced Vz"): the Vz update of
+// advVz (runs that carry BFD_RUN_ADV_VZ: plain fluid runs outside the absorbing layer, not QUIET; bfd_lists.hip, "advanced Vz"): the Vz update of
 // velocity_fluid_body needs nothing from the x/y neighbours, only the column's NEW Szz of planes p-1 .. p+2, and this kernel holds the column's Vz in
 // its z-queue. So it keeps its last three new Szz (and two ids) and stores the new Vz of plane p = kl-2 at iteration kl, after dzVz has used the old
 // one: the very expression of velocity_fluid_body, which then neither loads nor stores Vz at those planes.

@@ -4,7 +4,7 @@ built by slab.create_hip_slab(bounds=...) and stepped with their halo planes mov
 and overlapped orders. Every output -- all ten maps as last / RMS / peak, three sensor quantities, IndexSensorMap -- must
 equal the oracle and a single-domain engine element by element.
 
-What the cuts reach in the engine (choose_tile_grid in bfd_api.hip, which the design notes call make_grid): with nk planes in
+What the cuts reach in the engine (choose_tile_grid in bfd_lists.hip, which the design notes call make_grid): with nk planes in
 a slab, lowPlanes = min(SUB, nk) and hiStart = max(((nk - 2) / SUB) * SUB, lowPlanes) delimit the boundary sub-tiles, which
 form part 1 of a split half-step, take the sources and listed shear cells below srcLowEnd / from srcHighBeg and never go
 quiet. For nk <= SUB low and high boundary are one sub-tile and part 2 is empty; quiet runs exist from nk = 3 SUB."""
@@ -16,7 +16,7 @@ from tests.util import geometry_of
 
 pytestmark = pytest.mark.gpu
 
-SUB = 8          # depth of a sub-tile in planes: bfd_tile_subz() in choose_tile_grid (bfd_api.hip); held to the library in the quiet-run test
+SUB = 8          # depth of a sub-tile in planes: bfd_tile_subz() in choose_tile_grid (bfd_lists.hip); held to the library in the quiet-run test
 
 _oracle, _single = {}, {}
 
@@ -104,7 +104,7 @@ def test_quiet_runs_either_side_of_three_sub_tiles(medium, cutset, split, monkey
     N1, N2 = a[0].shape[:2]
     solid_planes = SC.solid_of(a).any(axis=(0, 1))
     for (k0, nk), (active, total) in zip(SC.bounds_of(cuts), act):
-        # quiet_runs_wanted (bfd_api.hip) also wants the solid state compact, which takes a solid cell among the slab's own planes: a slab that
+        # quiet_runs_wanted (bfd_lists.hip) also wants the solid state compact, which takes a solid cell among the slab's own planes: a slab that
         # sees bone only in a ghost plane (the last one of the 78-plane grid: bone ends in plane 50, the slab begins at 52) has solid runs, an
         # empty cell list and no map
         ghosts_only = not solid_planes[k0:k0 + nk].any() and solid_planes[max(k0 - 2, 0):k0 + nk + 2].any()

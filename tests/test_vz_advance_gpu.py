@@ -1,4 +1,4 @@
-"""Advanced Vz (bfd_api.hip, "advanced Vz"): in the plain fluid runs outside the absorbing layer stress_fluid stores the new Vz of a run's inner
+"""Advanced Vz (bfd_lists.hip, "advanced Vz"): in the plain fluid runs outside the absorbing layer stress_fluid stores the new Vz of a run's inner
 planes (kbeg+1 .. kend-3) and velocity_fluid leaves Vz alone there. Every result must equal, bit for bit, what updating Vz of every plane in
 velocity_fluid gives (BFD_ADV_VZ=0, the path of the parent commit), in a fresh engine each: every state array, the RMS / peak / last maps of
 Pressure and Vz and the sensor series of both.
