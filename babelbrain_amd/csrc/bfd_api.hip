@@ -605,7 +605,7 @@ static int stress_part(bfd_sim *s, int part, hipStream_t st)
             // still takes the pairing flavour for its own cells)
             s->pendingAcc = false; s->pairDone = true;
         }
-        bfd_launch_stress_v2(s->d, st, &s->tiles, part, accP, pkP);
+        bfd_launch_stress_tiled(s->d, st, &s->tiles, part, accP, pkP);
         s->midStep = true;
     }
     close_timing_pair(st, e0, e1, s->evStress);
@@ -635,7 +635,7 @@ static int velocity_part(bfd_sim *s, int part, hipStream_t st)
             if (part != 0) BFD_FAIL(-2, "split half-steps are not available with kernelVariant 4 on a whole domain");
             bfd_launch_fused(d, st, accP, pkP, &s->tiles, 0, s->tiles.nFused);        // both half-steps of its runs: old fields -> W copies
         }
-        bfd_launch_velocity_v2(new_stress_view(d), st, accP, pkP, &s->tiles, part, !paired);
+        bfd_launch_velocity_tiled(new_stress_view(d), st, accP, pkP, &s->tiles, part, !paired);
     }
     close_timing_pair(st, e0, e1, s->evVelocity);
     if (s->nSrcVox && s->cfg.typeSource < 2 && s->step < s->lengthSource) { rc = bfd_inject_part(s, part, new_velocity_view(d), st); if (rc) return rc; }
@@ -674,9 +674,9 @@ int bfd_half_step_velocity_part_on(bfd_sim *s, int32_t part, void *hipStream)
 static void record_plain_step(bfd_sim *s, hipStream_t cs)
 {
     const bfd_dev &d = s->d;
-    if (s->cfg.kernelVariant == 1) bfd_launch_stress_v1(d, cs); else bfd_launch_stress_v2(d, cs, &s->tiles, 0);
+    if (s->cfg.kernelVariant == 1) bfd_launch_stress_v1(d, cs); else bfd_launch_stress_tiled(d, cs, &s->tiles, 0);
     if (s->cfg.typeSource >= 2) bfd_record_injection(s, cs);
-    if (s->cfg.kernelVariant == 1) bfd_launch_velocity_v1(d, cs); else bfd_launch_velocity_v2(d, cs, nullptr, nullptr, &s->tiles, 0);
+    if (s->cfg.kernelVariant == 1) bfd_launch_velocity_v1(d, cs); else bfd_launch_velocity_tiled(d, cs, nullptr, nullptr, &s->tiles, 0);
     if (s->cfg.typeSource < 2) bfd_record_injection(s, cs);
     hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, cs, s->stepDev);
 }

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the tiled kernels (bfd_kernels_v2.hip, bfd_kernels_fused.hip). gfx950 only.
+// Device-side helpers shared by the tiled kernels (bfd_kernels_dense / _fluid / _solid / _shear / _setup.hip, bfd_kernels_fused.hip). gfx950 only.
 #pragma once
 #include "bfd_internal.h"
 
@@ -62,6 +62,32 @@ template <typename T> __device__ __forceinline__ T LDNT(const T *p)             
 }
 __device__ __forceinline__ unsigned U2(const uint16_t *base, unsigned byteOfs) { return *(const uint16_t *)((const char *)uni(base) + byteOfs); }
 __device__ __forceinline__ unsigned U1(const uint8_t *base, unsigned byteOfs) { return uni(base)[byteOfs]; }
+
+// The same accesses as GLOBAL instructions (wave-uniform base in SGPRs + 32-bit byte offset), for the kernels whose prefetch has to stay in
+// flight across their LDS phases (velocity_solid, the fused time step): a flat load counts on lgkmcnt as well, so the first wait for an LDS
+// read would also wait for every load of the next plane just issued.
+#define BFD_GLOBAL __attribute__((address_space(1)))
+template <typename T> __device__ __forceinline__ BFD_GLOBAL T *guni(const T *p)
+{
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (BFD_GLOBAL T *)(((unsigned long long)hi << 32) | lo);
+}
+// keeps the 32-bit offset a value of the block that uses it (hoisted out of the loop its zero-extension becomes a 64-bit VGPR address)
+// (round 6: pinning the BASE as an opaque scalar pair instead of the lane's offset -- to save the v_mov each pinned offset costs -- makes the compiler form
+// 64-bit vector addresses again: v_lshl_add_u64 6 -> 30 per plane, 92 -> 100 registers; not kept)
+__device__ __forceinline__ unsigned pin(unsigned v) { asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ float GL4(const float *base, unsigned ofs) { return *(BFD_GLOBAL const float *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
+__device__ __forceinline__ float GLNT(const float *base, unsigned ofs) { return __builtin_nontemporal_load((BFD_GLOBAL const float *)((BFD_GLOBAL const char *)guni(base) + pin(ofs))); }
+__device__ __forceinline__ unsigned GL2(const uint16_t *base, unsigned ofs) { return *(BFD_GLOBAL const uint16_t *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
+__device__ __forceinline__ unsigned GL1(const uint8_t *base, unsigned ofs) { return *(BFD_GLOBAL const uint8_t *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
+// predicated: lanes with c == false read dword 0 of the plane and get 0
+__device__ __forceinline__ float GLP(const float *base, unsigned ofs, bool c) { const float v = GL4(base, c ? ofs : 0u); return c ? v : 0.0f; }
+__device__ __forceinline__ void GS4(float *base, unsigned ofs, float v) { *(BFD_GLOBAL float *)((BFD_GLOBAL char *)guni(base) + pin(ofs)) = v; }
+__device__ __forceinline__ void GS4NT(float *base, unsigned ofs, float v)
+{
+    __builtin_nontemporal_store(v, (BFD_GLOBAL float *)((BFD_GLOBAL char *)guni(base) + pin(ofs)));
+}
 
 // XCD-aware tile order: consecutive block ids land on different XCDs (round robin over 8), so give
 // XCD e the e-th contiguous run of tiles.

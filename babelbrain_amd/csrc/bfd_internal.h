@@ -29,7 +29,7 @@
 #define BFD_STAB (6.0 / 7.0)
 #endif
 
-// tile geometry of the class-specialised kernels (bfd_kernels_v2.hip): 64 x 8 cells per workgroup plane,
+// tile geometry of the tiled kernels (bfd_tile.h, bfd_kernels_dense / _fluid / _solid / _shear / _setup.hip): 64 x 8 cells per workgroup plane,
 // classification in sub-tiles of BFD_SUBZ planes
 #define BFD_TILE_X 64
 #define BFD_TILE_Y 8
@@ -77,7 +77,7 @@ struct bfd_dev {
     float *cSxx, *cSyy, *cSxy, *cSxz, *cSyz, *cRxx, *cRyy, *cRxy, *cRxz, *cRyz;
     // Activity map (round 6; null = every run works in every half-step): one byte per 64 x 8 x BFD_SUBZ sub-tile, 1 = a non-zero V or S value has
     // been written there. Padded by one sub-tile on every side: sub-tile (bx, by, q) at ((q + 1) * actY + by + 1) * actX + bx + 1. A run whose
-    // sub-tiles and all their neighbours are clear returns at entry (bfd_kernels_v2.hip, "QUIET runs"). Production calls only (whole domains and Z-slabs).
+    // sub-tiles and all their neighbours are clear returns at entry (bfd_tile.h, "QUIET runs"). Production calls only (whole domains and Z-slabs).
     unsigned char *act; int actX, actY;
     int actLo, actHi;      // Z-slabs: runs that touch local planes below actLo or from actHi on (the sub-tiles a neighbour's planes reach) always work; whole domains: 0, INT_MAX
 };
@@ -345,17 +345,27 @@ void bfd_release_pinned_pieces(void);
 void bfd_advise_result_buffer(void *p, size_t bytes);
 // bfd_get_sensors with a row pitch: the series of selected map q at out + q * rowElems (bfd_outputs.hip; bfd_group.hip: a slab writes into its columns)
 int bfd_sensors_into(bfd_sim *s, float *out, int64_t rowElems);
-// kernel launchers (bfd_kernels_*.hip)
+// kernel launchers (bfd_kernels_*.hip), by the file that defines them
+// --- bfd_kernels_v1.hip
 void bfd_launch_stress_v1(const bfd_dev &d, hipStream_t s);
 void bfd_launch_velocity_v1(const bfd_dev &d, hipStream_t s);
-void bfd_tile_grid(const bfd_dev &d, int *tilesX, int *tilesY, int *subZ);
-// runs [off, off + n) of the fused list (bfd_kernels_fused.hip)
+// --- bfd_kernels_fused.hip: runs [off, off + n) of the fused list
 void bfd_launch_fused(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int off, int n);
 int bfd_fused_rows(void);
 int bfd_fused_max_materials(void);
+// --- bfd_kernels_setup.hip: the tile grid's sizes and the kernels of the planner and of the placement
+void bfd_tile_grid(const bfd_dev &d, int *tilesX, int *tilesY, int *subZ);
 int bfd_tile_subz(void);
+int bfd_tile_zchunk(void);
 void bfd_launch_classify(const bfd_dev &d, hipStream_t s, int *flagsDev, int *tileMatDev);
 void bfd_launch_mark_source_subtiles(const bfd_dev &d, hipStream_t s, const uint32_t *lin, long n);
+void bfd_launch_cell_classes(const bfd_dev &d, hipStream_t s, uint8_t *clsBase, long nalloc);
+// counts over the cells of the solid runs: [0] fluid no-memory, [1] fluid with memory, [2] solid no-memory, [3] solid with memory,
+// [4] active shear edges, [5] reflector cells
+void bfd_launch_count_solid_cells(const bfd_dev &d, hipStream_t s, const int4 *solidRuns, int nSolid, unsigned long long *counts6);
+// placement probe: arrays a and b (pointers to local plane 0) updated in place along all runs of the slab, planes [0, kmax)
+void bfd_launch_probe_pair(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, float *a, float *b, int kmax);
+// --- bfd_kernels_shear.hip: the sparse shear kernel, its list and the compact solid state
 // flags the cells of the sparse shear list: solid, non-reflector centre
 void bfd_launch_mark_solid(const bfd_dev &d, hipStream_t s, unsigned char *flag, long n);
 void bfd_launch_shear_order_keys(const bfd_dev &d, hipStream_t s, const unsigned *cells, unsigned long long *keys, long n, int lowPlanes, int hiStart);
@@ -369,18 +379,24 @@ void bfd_launch_css_row_table(const bfd_dev &d, hipStream_t s, const unsigned *c
 // the reverse into dstCompact from a full-volume source. cells / n: the list the entries belong to.
 void bfd_launch_css_scatter(hipStream_t s, const unsigned *cells, long n, const float *compact, float *dstFull);
 void bfd_launch_css_gather(hipStream_t s, const unsigned *cells, long n, const float *srcFull, float *dstCompact);
-void bfd_launch_cell_classes(const bfd_dev &d, hipStream_t s, uint8_t *clsBase, long nalloc);
-// counts over the cells of the solid runs: [0] fluid no-memory, [1] fluid with memory, [2] solid no-memory, [3] solid with memory,
-// [4] active shear edges, [5] reflector cells
-void bfd_launch_count_solid_cells(const bfd_dev &d, hipStream_t s, const int4 *solidRuns, int nSolid, unsigned long long *counts6);
-int bfd_tile_zchunk(void);
-// placement probe: arrays a and b (pointers to local plane 0) updated in place along all runs of the slab, planes [0, kmax)
-void bfd_launch_probe_pair(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, float *a, float *b, int kmax);
-// part: 0 = every tile, 1 = boundary tiles, 2 = interior tiles (variant 2 lists every tile as solid)
-// accP / pkP not null: the plain fluid runs take the pairing flavour, which adds the Pressure of the previous and of this step to the maps
-void bfd_launch_stress_v2(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part, float *accP = nullptr, float *pkP = nullptr);
-// accP / pkP: Pressure RMS / peak accumulators of this step (slab-local, x-fastest) or nullptr; fluidAcc = false: only the solid runs
-// accumulate (the fluid runs are paired in the stress half-step)
-void bfd_launch_velocity_v2(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc = true);
+// the sparse kernel over cells [b, e) of the list; R: their list-ordered memory variables (null with the compact solid state)
+void bfd_launch_stress_shear(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, long b, long e, float *R);
+// --- bfd_kernels_fluid.hip. runs / cnt: the range of the run list; m: index of its cost-balanced map (bfd_tiles::xmap), -1 = none
+// pair: the plain fluid runs take the pairing flavour, which adds the Pressure of the previous and of this step to the maps accP / pkP
+void bfd_launch_stress_fluid(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, const int4 *runs, int cnt, int m, bool pair, float *accP, float *pkP);
+void bfd_launch_velocity_fluid(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, const int4 *runs, int cnt, int m, bool acc, float *accP, float *pkP);
 // adds the Pressure of the current Szz to the maps at the accumulating cells of the fluid runs (paired accumulation with its partner step outstanding)
 void bfd_launch_flush_paired(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t);
+// --- bfd_kernels_solid.hip. pml: the runs of the range touch the absorbing layer; part as below
+void bfd_launch_stress_solid(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, const int4 *runs, int cnt, int m);
+void bfd_launch_velocity_solid(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part, bool pml, const int4 *runs, int cnt, int m, float *accP, float *pkP);
+// --- bfd_kernels_dense.hip (kernelVariant 2)
+void bfd_launch_stress_dense(const bfd_dev &d, hipStream_t s, const int4 *runs, int n);
+void bfd_launch_velocity_dense(const bfd_dev &d, hipStream_t s, const int4 *runs, int n, float *accP, float *pkP);
+// --- bfd_kernels_tiled.hip: the launches of a half-step in their order
+// part: 0 = every tile, 1 = boundary tiles, 2 = interior tiles (variant 2 lists every tile as solid)
+// accP / pkP not null: the plain fluid runs take the pairing flavour, which adds the Pressure of the previous and of this step to the maps
+void bfd_launch_stress_tiled(const bfd_dev &d, hipStream_t s, const bfd_tiles *t, int part, float *accP = nullptr, float *pkP = nullptr);
+// accP / pkP: Pressure RMS / peak accumulators of this step (slab-local, x-fastest) or nullptr; fluidAcc = false: only the solid runs
+// accumulate (the fluid runs are paired in the stress half-step)
+void bfd_launch_velocity_tiled(const bfd_dev &d, hipStream_t s, float *accP, float *pkP, const bfd_tiles *t, int part, bool fluidAcc = true);

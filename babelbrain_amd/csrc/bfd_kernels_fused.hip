@@ -45,22 +45,8 @@ static_assert(NTX <= 128 && NTY <= 256, "halo tasks fit their waves");
 constexpr int FUSED_WAVES_PER_SIMD = 4;
 constexpr int FUSED_TAB_MAX = BFD_FUSED_MAX_MATERIALS;  // materials whose AP, BP, 1/rho fit the LDS table of the multi-material flavour
 
-// Accesses of this kernel are GLOBAL instructions (wave-uniform base in SGPRs + 32-bit byte offset), not the FLAT ones of
-// bfd_device.h: a flat load counts on lgkmcnt as well, so the first wait for an LDS read would also wait for every load of
-// the next plane just issued -- the prefetch of this kernel has to stay in flight across its LDS phases.
-#define BFD_GLOBAL __attribute__((address_space(1)))
-template <typename T> __device__ __forceinline__ BFD_GLOBAL T *guni(const T *p)
-{
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (BFD_GLOBAL T *)(((unsigned long long)hi << 32) | lo);
-}
-// keeps the 32-bit offset a value of the block that uses it (hoisted out of the loop its zero-extension becomes a 64-bit VGPR address)
-__device__ __forceinline__ unsigned pin(unsigned v) { asm("" : "+v"(v)); return v; }
-__device__ __forceinline__ float GL4(const float *base, unsigned ofs) { return *(BFD_GLOBAL const float *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
-__device__ __forceinline__ float GLNT(const float *base, unsigned ofs) { return __builtin_nontemporal_load((BFD_GLOBAL const float *)((BFD_GLOBAL const char *)guni(base) + pin(ofs))); }
-__device__ __forceinline__ unsigned GL2(const uint16_t *base, unsigned ofs) { return *(BFD_GLOBAL const uint16_t *)((BFD_GLOBAL const char *)guni(base) + pin(ofs)); }
-__device__ __forceinline__ void GS4(float *base, unsigned ofs, float v) { *(BFD_GLOBAL float *)((BFD_GLOBAL char *)guni(base) + pin(ofs)) = v; }
+// Accesses of this kernel are the GLOBAL ones of bfd_device.h (GL4, GLNT, GL2, GS4), not the FLAT ones: the prefetch of this kernel has
+// to stay in flight across its LDS phases.
 // Stores are plain in this kernel: non-temporal ones wrote 1.98 GB per launch where 1.78 are needed and cost 7 % (C1 512^3, same
 // box: 0.953 -> 0.889 ms; profiles/r4/fused_experiments.txt).
 __device__ __forceinline__ void GSNT(float *base, unsigned ofs, float v) { GS4(base, ofs, v); }

@@ -313,7 +313,7 @@ static int build_shear_list(bfd_sim *s, const TileGrid &G, int *countOut, bool *
     }
     hostCells.resize((size_t)count);
     if (e == hipSuccess && count) e = hipMemcpy(hostCells.data(), sel, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost);
-    // list order (bfd_kernels_v2.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
+    // list order (bfd_kernels_shear.hip, shear_order_keys): by z-chunk and band of 8 rows, so that the z neighbours a cell gathers were
     // touched one band-plane earlier instead of one whole plane of the shell
     if (e == hipSuccess && count > 0) {
         DevTemp<unsigned long long> k0, k1; DevTemp<unsigned> v1; DevTemp<char> w2; size_t w2b = 0;
@@ -504,7 +504,7 @@ static bool adv_vz_engine(const bfd_sim *s, int nSolid)          // run lists ju
            s->cfg.typeSource < 2 && nSolid == 0 && !quiet_runs_wanted(s);
 }
 
-// Build the run lists of the tiled kernels (bfd_kernels_v2.hip). Sub-tiles of 64 x 8 x 8 cells are
+// Build the run lists of the tiled kernels (bfd_kernels_fluid / _solid / _dense.hip; their order: bfd_kernels_tiled.hip). Sub-tiles of 64 x 8 x 8 cells are
 // classified on the device; consecutive sub-tiles of one (bx,by) column with identical class merge into
 // runs that never cross a 32-plane chunk boundary. Variant 2: every sub-tile counts as solid (dense kernels).
 int build_tile_lists(bfd_sim *s)
@@ -594,7 +594,7 @@ int build_tile_lists(bfd_sim *s)
     return 0;
 }
 
-// Quiet runs (bfd_dev::act; bfd_kernels_v2.hip): a production call lets the runs ahead of the wave front return at entry. On when the
+// Quiet runs (bfd_dev::act; bfd_tile.h): a production call lets the runs ahead of the wave front return at entry. On when the
 // engine (a whole domain or a Z-slab of at least three sub-tiles: its boundary runs always work) accumulates its maps over the caller's own window (rmsFirstStep = 0: bench.py's timed windows, which accumulate from
 // step 1, never see it), runs the class-specialised kernels (variants 0 / 3, in-place update) and keeps solid-only values compact; BFD_SKIP_ZERO=0
 // switches it off. The map starts with the sub-tiles of the source voxels at step 0; when inputs are set again in the middle of a run every sub-tile

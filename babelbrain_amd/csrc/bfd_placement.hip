@@ -1,5 +1,5 @@
 // Placement of the per-voxel arrays by memory region (bfd_prepare -> bfd_choose_placement) and the cache of buffers a search found.
-// Host code only: the probe kernel is bfd_kernels_v2.hip's (bfd_launch_probe_pair). gfx950 only.
+// Host code only: the probe kernel is bfd_kernels_setup.hip's (bfd_launch_probe_pair). gfx950 only.
 //
 // The tiled kernels stream 6 to 20 arrays at the same cell offset. Round 2 found that the same kernels on the same data run
 // 1.50 or 1.70 ms per step at C3 depending on nothing but where hipMalloc put those arrays, and chose among whole sets of

@@ -3,15 +3,19 @@
 
     make -C <tree>/babelbrain_amd/csrc -O -j16 EXTRA=-Rpass-analysis=kernel-resource-usage > <tree>.log 2>&1     (both trees; -O keeps the
                                                             remarks of one compiler together: without it parallel compilers tear each other's lines)
-    scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log [new=old ...]
+    scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log [new=old ...] [kernel:new=old ...]
 
 new=old (optional, e.g. bfd_outputs=bfd_api): kernels and resource records of object `new` of the second build are looked up under object `old`
-of the first (code that moved from one source file to another).
+of the first (code that moved from one source file to another). An `old` that the Makefile no longer names (a source file that was split up) is read from the
+first build all the same.
+kernel:new=old (optional): in the kernel names of the second build the text `new` is replaced by `old` before the lookup (a kernel that lost a template
+parameter: kernel:12stress_fluidILb=12stress_fluidILb1ELb). Without it such a kernel is listed once under each "only in".
 
 The fat binary section of every object is unbundled (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler --unbundle),
 disassembled (llvm-objdump -d) and cut at the kernel symbols; the instruction text of a kernel (addresses and encodings dropped) and its resource remarks (registers, spills, scratch, occupancy, LDS) must be equal on both sides.
 The literal of the s_add_u32 behind an s_getpc_b64 is left out of the comparison: it is the distance from the instruction to a constant of the object, which changes with
 the kernels that lie between them and not with the kernel's code.
+The s_nop filling behind a kernel's last instruction is left out as well: its length depends on the symbol that follows in the object.
 Exit status 0 = nothing differs and no kernel exists only in the second build."""
 import collections
 import os
@@ -49,6 +53,9 @@ def kernels(obj, tmp):
             if cur and cur[-1].startswith('s_getpc_b64'):      # the low word of a pc-relative address: where the object's data lies from here, not code
                 ins = re.sub(r'^(s_add_u32 \S+ \S+) 0x[0-9a-f]+$', r'\1 <pc-relative>', ins)
             cur.append(ins)
+    for ins in out.values():      # the s_nop filling between a kernel's end and the next aligned symbol: it changes with the kernel that follows
+        while ins and ins[-1] == 's_nop 0':
+            ins.pop()
     return out
 
 
@@ -77,17 +84,24 @@ def resources(log):
 
 def main():
     dirA, logA, dirB, logB = sys.argv[1:5]
-    moved = dict(a.split('=') for a in sys.argv[5:])
+    moved = dict(a.split('=') for a in sys.argv[5:] if not a.startswith('kernel:'))
+    renamed = [a[len('kernel:'):].split('=') for a in sys.argv[5:] if a.startswith('kernel:')]
+
+    def old_name(name):
+        for new, old in renamed:
+            name = name.replace(new, old)
+        return name
+    SRC.extend(sorted(set(moved.values()) - set(SRC)))
     with tempfile.TemporaryDirectory() as tmp:
         A, B = {}, {}
         for s in SRC:
             for d, K in ((dirA, A), (dirB, B)):
                 for name, ins in kernels(os.path.join(d, s + '.o'), tmp).items():
-                    key = (moved.get(s, s) if K is B else s, name)
+                    key = (moved.get(s, s), old_name(name)) if K is B else (s, name)
                     assert key not in K, 'kernel in two objects of one build (a copy): %s %s' % key
                     K[key] = ins
     RA = resources(logA)
-    RB = {(moved.get(f[:-4], f[:-4]) + '.hip', name): v for (f, name), v in resources(logB).items()}
+    RB = {(moved.get(f[:-4], f[:-4]) + '.hip', old_name(name)): v for (f, name), v in resources(logB).items()}
     onlyA, onlyB = sorted(set(A) - set(B)), sorted(set(B) - set(A))
     print('code symbols: first build %d, second build %d, in both %d' % (len(A), len(B), len(set(A) & set(B))))
     print('instructions compared: %d' % sum(len(A[k]) for k in set(A) & set(B)))

@@ -1,4 +1,4 @@
-"""Advanced Vz, the plane range (bfd_kernels_v2.hip, stress_fluid_body): a float32 model of the fluid time step on columns cut into z-runs. The
+"""Advanced Vz, the plane range (bfd_kernels_fluid.hip, stress_fluid_body): a float32 model of the fluid time step on columns cut into z-runs. The
 stress pass of a run, which holds the column's Vz, also stores the new Vz of the planes [kbeg + lo, kend - hi]; the velocity pass skips Vz there.
 Runs are visited in a random order in either pass and work on the live arrays, as workgroups do. With lo = 1, hi = 3 every order must equal the
 plain two-pass scheme bit for bit; one plane more at either end must differ for some order (the run below reads Vz(kbeg); the run above
