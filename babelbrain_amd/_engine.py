@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     'bfd_label_survey3d', 'bfd_assemble_material_map3d', 'bfd_sdr_rays3d',
     'bfd_integer_histogram3d', 'bfd_order_statistics3d', 'bfd_uniform_histogram3d', 'bfd_pseudo_ct_candidates3d', 'bfd_pseudo_ct_convert3d',
     'bfd_select_component3d', 'bfd_bone_rim_correct3d', 'bfd_class_extrema3d', 'bfd_loss_survey3d',
+    'bfd_thermal_create', 'bfd_thermal_destroy', 'bfd_thermal_set_inputs', 'bfd_thermal_median_region', 'bfd_thermal_loss_survey', 'bfd_thermal_set_scale',
+    'bfd_thermal_run', 'bfd_thermal_set_previous', 'bfd_thermal_merge_max', 'bfd_thermal_extrema', 'bfd_thermal_get', 'bfd_thermal_get_plane', 'bfd_thermal_traffic',
 ]
 
 
@@ -252,6 +254,22 @@ def load_library():
     lib.bfd_loss_survey3d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_thermal_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.bfd_thermal_destroy.argtypes = [C.c_void_p]
+    lib.bfd_thermal_destroy.restype = None
+    lib.bfd_thermal_set_inputs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.bfd_thermal_median_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    lib.bfd_thermal_loss_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_thermal_set_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.bfd_thermal_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    lib.bfd_thermal_set_previous.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bfd_thermal_merge_max.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.bfd_thermal_extrema.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.bfd_thermal_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.bfd_thermal_get_plane.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+    lib.bfd_thermal_traffic.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:

@@ -14,6 +14,7 @@
 // once for all of them. x-fastest layout.
 #include "bfd_internal.h"
 #include "bfd_device.h"
+#include "bfd_thermal_stages.h"
 #include <math.h>
 #include <vector>
 
@@ -575,97 +576,27 @@ __global__ __launch_bounds__(256) void bhte_capture(const float4 *__restrict__ T
     }
 }
 
-}  // namespace
-
-// The run behind all entry points. F, M, S: extents of the fastest, middle and slowest axis of the volumes as they lie in memory.
-// q (host, nFields volumes) or, if null, pressure + qf: the heat increments are then computed on the device (and copied to qOut).
-// initT (per material) replaces the upload of T when flags bit 0 is clear; the dose starts from zero when bit 1 is clear.
-// Captures (bfd_bhte_run_protocol; the other entry points pass none): at step boundary captureStep[c] (after step captureStep[c] - 1)
-// Tmax = max(Tmax, T) (the first copies T) and doseCap = dose; no pass crosses a capture boundary.
-// ID: the width of the material ids (unsigned char: nMat <= 256; uint16_t: nMat <= BFD_BHTE_MAX_MATERIALS); it selects the kernels' overloads.
+// The step loop of a run on device pointers (bfd_thermal_stages.h): what bhte_run_core does between its uploads and its downloads, and what the
+// thermal study (bfd_thermal_study.hip) runs on its resident volumes.
 template <bool REV, typename ID>
-static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_t nMat, const ID *mat, const float *cd, const float *cp,
-                         const float *qf, const float *initT, int32_t nFields, const float *q, const float *pressure, float *qOut, float *T, float *dose,
-                         int32_t flags, float Tcore, double dt, int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
-                         float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
-                         int32_t nCaptures = 0, const int32_t *captureStep = nullptr, float *Tmax = nullptr, float *doseCap = nullptr)
+hipError_t bhte_run_device(const bfd_bhte_device_run &r, int *curOut, double *kernelMs)
 {
-    if (nMat > IdTab<ID>::N) {
-        bfd_set_error("bfd_bhte_run: " + std::to_string(nMat) + " materials, at most " + std::to_string(IdTab<ID>::N) + " with " + std::to_string(IdTab<ID>::BITS) + "-bit ids" +
-                      (sizeof(ID) == 1 ? " (bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16 take up to " + std::to_string(BFD_BHTE_MAX_MATERIALS) + ")" : std::string()));
-        return -1;
-    }
-    if (F < 3 || M < 3 || S < 3 || nMat < 1 || nFields < 1 || !mat || !cd || !cp || (!q && !(pressure && qf)) || !T || !dose || nSteps < 0 ||
-        (nSteps > 0 && !fieldOfStep) || (!(flags & 1) && !initT) || nCaptures < 0 || (nCaptures > 0 && !(captureStep && Tmax && doseCap))) {
-        bfd_set_error("bfd_bhte_run: bad argument"); return -1;
-    }
-    for (int s = 0; s < nSteps; s++)
-        if (fieldOfStep[s] < -1 || fieldOfStep[s] >= nFields) { bfd_set_error("bfd_bhte_run: fieldOfStep entry out of range"); return -1; }
-    for (int c = 0; c < nCaptures; c++)
-        if (captureStep[c] < 0 || captureStep[c] > nSteps || (c > 0 && captureStep[c] < captureStep[c - 1])) {
-            bfd_set_error("bfd_bhte_run: captureStep must ascend within [0, nSteps]"); return -1;
-        }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { bfd_set_error("bfd_bhte_run: no HIP device available (no CPU fallback)"); return -3; }
-    if (device < 0 || device >= ndev) { bfd_set_error("bfd_bhte_run: device ordinal out of range"); return -3; }
-    BFD_HIP(hipSetDevice(device));
-    const int N1 = F, N2 = M, N3 = S;                            // the kernels' names: x fastest
+    const int N1 = r.N1, N2 = r.N2, N3 = r.N3, nMat = r.nMat, nSteps = r.nSteps, nCaptures = r.nCaptures, fm = r.fm, sliceJ = r.sliceJ;
     const size_t n = (size_t)N1 * N2 * N3;
-    if (sliceJ >= N2) { bfd_set_error("bfd_bhte_run: monitored plane outside the volume"); return -1; }
-    for (int64_t t = 0; t < nPoints && pointIndex && points; t++)
-        if (pointIndex[t] >= n) { bfd_set_error("bfd_bhte_run: monitored point outside the volume"); return -1; }
-    const int fm = nFactorMonitoring > 0 ? nFactorMonitoring : 1;
-    const long nSamples = (monitorSlice && sliceJ >= 0) ? (nSteps + fm - 1) / fm : 0;
-    float *dT[2] = {nullptr, nullptr}, *dDose = nullptr, *dq = nullptr, *dcd = nullptr, *dcp = nullptr, *dqf = nullptr, *dSlice = nullptr, *dPts = nullptr;
-    float *dTmax = nullptr, *dDoseCap = nullptr;
-    ID *dmat = nullptr; unsigned *dIdx = nullptr;
-    std::vector<void *> allocs;
-    auto A = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) allocs.push_back(*p); return e; };
-    // the volumes carry pads (elements): bhte_step2g addresses every cell of its 68 x 28 regions, also those that hang over the faces
-    const size_t padF = (((size_t)4 * N1 + 64 + 255) / 256) * 256, padB = (size_t)49 * N1 + 256;       // bhte_stepNg: 72 x 28 regions, 4 rows / cells in front
-    auto AP = [&](void **p, size_t elems, size_t elemBytes) {
-        void *raw = nullptr; const hipError_t e = A(&raw, (padF + elems + padB) * elemBytes);
-        if (e == hipSuccess) *p = (char *)raw + padF * elemBytes;
-        return e;
-    };
-    hipError_t e = AP((void **)&dT[0], n, 4);
-    if (e == hipSuccess) e = AP((void **)&dT[1], n, 4);
-    if (e == hipSuccess) e = AP((void **)&dDose, n, 4);
-    if (e == hipSuccess) e = AP((void **)&dq, n * (size_t)nFields, 4);
-    if (e == hipSuccess) e = AP((void **)&dmat, n, sizeof(ID));
-    if (e == hipSuccess && nCaptures) e = AP((void **)&dTmax, n, 4);
-    if (e == hipSuccess && nCaptures) e = AP((void **)&dDoseCap, n, 4);
-    if (e == hipSuccess) e = A((void **)&dcd, nMat * 4);
-    if (e == hipSuccess) e = A((void **)&dcp, nMat * 4);
-    if (e == hipSuccess) e = A((void **)&dqf, nMat * 4);
-    if (e == hipSuccess && nSamples) e = A((void **)&dSlice, (size_t)N1 * N3 * nSamples * 4);
-    if (e == hipSuccess && nPoints && points) { e = A((void **)&dIdx, nPoints * 4); if (e == hipSuccess) e = A((void **)&dPts, (size_t)nPoints * nSteps * 4); }
-    // 16-bit ids index the LDS table of the multi-step kernels: the ring cells that lie in the pads must read an id inside it too (any byte is inside the 8-bit table)
-    if (e == hipSuccess && sizeof(ID) > 1) e = hipMemset(dmat - padF, 0, (padF + n + padB) * sizeof(ID));
-    if (e == hipSuccess) e = hipMemcpy(dmat, mat, n * sizeof(ID), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dcd, cd, nMat * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dcp, cp, nMat * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if (flags & 1) e = hipMemcpy(dT[0], T, n * 4, hipMemcpyHostToDevice);
-        else {                                                                   // T = initT[material], via the table slot of qf
-            e = hipMemcpy(dqf, initT, nMat * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) { hipLaunchKernelGGL(table_lookup, dim3(2048), dim3(256), 0, 0, dmat, dqf, dT[0], n); e = hipDeviceSynchronize(); }
-        }
-    }
-    if (e == hipSuccess) e = (flags & 2) ? hipMemcpy(dDose, dose, n * 4, hipMemcpyHostToDevice) : hipMemset(dDose, 0, n * 4);
-    if (e == hipSuccess) {
-        if (q) e = hipMemcpy(dq, q, n * 4 * (size_t)nFields, hipMemcpyHostToDevice);
-        else {                                                                   // q = (p p) qf[material], in place
-            e = hipMemcpy(dqf, qf, nMat * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(dq, pressure, n * 4 * (size_t)nFields, hipMemcpyHostToDevice);
-            for (int f = 0; f < nFields && e == hipSuccess; f++) hipLaunchKernelGGL(heat_source, dim3(2048), dim3(256), 0, 0, dq + (size_t)f * n, dmat, dqf, dq + (size_t)f * n, n);
-            if (e == hipSuccess && qOut) e = hipMemcpy(qOut, dq, n * 4 * (size_t)nFields, hipMemcpyDeviceToHost);
-        }
-    }
-    if (e == hipSuccess && dIdx) e = hipMemcpy(dIdx, pointIndex, nPoints * 4, hipMemcpyHostToDevice);
+    float *const dT[2] = {r.T[0], r.T[1]};
+    float *const dDose = r.dose, *const dSlice = r.slice, *const dPts = r.pts, *const dTmax = r.Tmax, *const dDoseCap = r.doseCap;
+    const float *const dq = r.q, *const dcd = r.cd, *const dcp = r.cp;
+    const ID *const dmat = (const ID *)r.mat;
+    const unsigned *const dIdx = r.idx;
+    const int32_t *const fieldOfStep = r.fieldOfStep, *const captureStep = r.captureStep;
+    const int64_t nPoints = r.nPoints;
+    const long nSamples = r.nSamples;
+    const float Tcore = r.Tcore;
+    const double dt = r.dt;
+    hipError_t e = hipSuccess;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int cur = 0;
-    if (e == hipSuccess) {
+    {
         hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, 0);
         const dim3 block(64, 4, 1), grid((N1 + 63) / 64, (N2 + 3) / 4, N3);
         const float dtMin = (float)(dt / 60.0);
@@ -697,7 +628,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
         const int xcdOrder = 1;
         const int runsZ = (N3 + zrun - 1) / zrun;
         const long nBlocks2 = (long)tilesX * tilesY * runsZ;
-        auto Q = [&](int f) { return f < 0 ? (const float *)nullptr : dq + (size_t)f * n; };
+        auto Q = [&](int f) { return f < 0 ? (const float *)nullptr : dq + (size_t)f * r.qStride; };
         auto monitors = [&](int s) {
             if (dPts) hipLaunchKernelGGL(gather_points, dim3((unsigned)((nPoints + 255) / 256)), dim3(256), 0, 0, dT[cur], dIdx, dPts, (long)nPoints, (long)nSteps, (long)s);
             if (dSlice && s % fm == 0) hipLaunchKernelGGL(gather_slice<REV>, dim3(256), dim3(256), 0, 0, dT[cur], dSlice, N1, N2, N3, sliceJ, (long)(s / fm), nSamples);
@@ -707,7 +638,7 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
         auto captures = [&](int s) {
             for (; nextCap < nCaptures && captureStep[nextCap] == s; nextCap++)
                 hipLaunchKernelGGL(bhte_capture, dim3(2048), dim3(256), 0, 0, (const float4 *)dT[cur], (const float4 *)dDose, (float4 *)dTmax, (float4 *)dDoseCap,
-                                   (n + 3) / 4, nextCap == 0 ? 1 : 0);
+                                   (n + 3) / 4, (nextCap == 0 && !r.mergeFirstCapture) ? 1 : 0);
         };
         auto capFree = [&](int s, int L) { return nextCap >= nCaptures || (long)s + L <= captureStep[nextCap]; };
         // S steps per pass (round 6; BFD_BHTE_STEPS=2 keeps two): where the next S steps carry the same heat field (or none). Monitors of the steps
@@ -785,14 +716,126 @@ static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess && kernelMs) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *kernelMs = ms; }
     }
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    *curOut = cur;
+    return e;
+}
+
+}  // namespace
+
+void bfd_bhte_pads(int N1, size_t *front, size_t *back)
+{
+    // bhte_step2g addresses every cell of its 68 x 28 regions, also those that hang over the faces; bhte_stepNg: 72 x 28 regions, 4 rows / cells in front
+    *front = (((size_t)4 * N1 + 64 + 255) / 256) * 256;
+    *back = (size_t)49 * N1 + 256;
+}
+
+hipError_t bfd_stage_bhte_run(const bfd_bhte_device_run &r, int *cur, double *kernelMs)
+{
+    if (r.rev) return r.idBytes == 2 ? bhte_run_device<true, uint16_t>(r, cur, kernelMs) : bhte_run_device<true, unsigned char>(r, cur, kernelMs);
+    return r.idBytes == 2 ? bhte_run_device<false, uint16_t>(r, cur, kernelMs) : bhte_run_device<false, unsigned char>(r, cur, kernelMs);
+}
+
+// The run behind all entry points. F, M, S: extents of the fastest, middle and slowest axis of the volumes as they lie in memory.
+// q (host, nFields volumes) or, if null, pressure + qf: the heat increments are then computed on the device (and copied to qOut).
+// initT (per material) replaces the upload of T when flags bit 0 is clear; the dose starts from zero when bit 1 is clear.
+// Captures (bfd_bhte_run_protocol; the other entry points pass none): at step boundary captureStep[c] (after step captureStep[c] - 1)
+// Tmax = max(Tmax, T) (the first copies T) and doseCap = dose; no pass crosses a capture boundary.
+// ID: the width of the material ids (unsigned char: nMat <= 256; uint16_t: nMat <= BFD_BHTE_MAX_MATERIALS); it selects the kernels' overloads.
+template <bool REV, typename ID>
+static int bhte_run_core(int32_t device, int32_t F, int32_t M, int32_t S, int32_t nMat, const ID *mat, const float *cd, const float *cp,
+                         const float *qf, const float *initT, int32_t nFields, const float *q, const float *pressure, float *qOut, float *T, float *dose,
+                         int32_t flags, float Tcore, double dt, int32_t nSteps, const int32_t *fieldOfStep, int32_t sliceJ, int32_t nFactorMonitoring,
+                         float *monitorSlice, int64_t nPoints, const uint32_t *pointIndex, float *points, double *kernelMs,
+                         int32_t nCaptures = 0, const int32_t *captureStep = nullptr, float *Tmax = nullptr, float *doseCap = nullptr)
+{
+    if (nMat > IdTab<ID>::N) {
+        bfd_set_error("bfd_bhte_run: " + std::to_string(nMat) + " materials, at most " + std::to_string(IdTab<ID>::N) + " with " + std::to_string(IdTab<ID>::BITS) + "-bit ids" +
+                      (sizeof(ID) == 1 ? " (bfd_bhte_run_volumes16 / bfd_bhte_run_protocol16 take up to " + std::to_string(BFD_BHTE_MAX_MATERIALS) + ")" : std::string()));
+        return -1;
+    }
+    if (F < 3 || M < 3 || S < 3 || nMat < 1 || nFields < 1 || !mat || !cd || !cp || (!q && !(pressure && qf)) || !T || !dose || nSteps < 0 ||
+        (nSteps > 0 && !fieldOfStep) || (!(flags & 1) && !initT) || nCaptures < 0 || (nCaptures > 0 && !(captureStep && Tmax && doseCap))) {
+        bfd_set_error("bfd_bhte_run: bad argument"); return -1;
+    }
+    for (int s = 0; s < nSteps; s++)
+        if (fieldOfStep[s] < -1 || fieldOfStep[s] >= nFields) { bfd_set_error("bfd_bhte_run: fieldOfStep entry out of range"); return -1; }
+    for (int c = 0; c < nCaptures; c++)
+        if (captureStep[c] < 0 || captureStep[c] > nSteps || (c > 0 && captureStep[c] < captureStep[c - 1])) {
+            bfd_set_error("bfd_bhte_run: captureStep must ascend within [0, nSteps]"); return -1;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { bfd_set_error("bfd_bhte_run: no HIP device available (no CPU fallback)"); return -3; }
+    if (device < 0 || device >= ndev) { bfd_set_error("bfd_bhte_run: device ordinal out of range"); return -3; }
+    BFD_HIP(hipSetDevice(device));
+    const int N1 = F, N2 = M, N3 = S;                            // the kernels' names: x fastest
+    const size_t n = (size_t)N1 * N2 * N3;
+    if (sliceJ >= N2) { bfd_set_error("bfd_bhte_run: monitored plane outside the volume"); return -1; }
+    for (int64_t t = 0; t < nPoints && pointIndex && points; t++)
+        if (pointIndex[t] >= n) { bfd_set_error("bfd_bhte_run: monitored point outside the volume"); return -1; }
+    const int fm = nFactorMonitoring > 0 ? nFactorMonitoring : 1;
+    const long nSamples = (monitorSlice && sliceJ >= 0) ? (nSteps + fm - 1) / fm : 0;
+    float *dT[2] = {nullptr, nullptr}, *dDose = nullptr, *dq = nullptr, *dcd = nullptr, *dcp = nullptr, *dqf = nullptr, *dSlice = nullptr, *dPts = nullptr;
+    float *dTmax = nullptr, *dDoseCap = nullptr;
+    ID *dmat = nullptr; unsigned *dIdx = nullptr;
+    std::vector<void *> allocs;
+    auto A = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) allocs.push_back(*p); return e; };
+    // the volumes carry pads (elements): bhte_step2g addresses every cell of its 68 x 28 regions, also those that hang over the faces
+    size_t padF = 0, padB = 0;
+    bfd_bhte_pads(N1, &padF, &padB);
+    auto AP = [&](void **p, size_t elems, size_t elemBytes) {
+        void *raw = nullptr; const hipError_t e = A(&raw, (padF + elems + padB) * elemBytes);
+        if (e == hipSuccess) *p = (char *)raw + padF * elemBytes;
+        return e;
+    };
+    hipError_t e = AP((void **)&dT[0], n, 4);
+    if (e == hipSuccess) e = AP((void **)&dT[1], n, 4);
+    if (e == hipSuccess) e = AP((void **)&dDose, n, 4);
+    if (e == hipSuccess) e = AP((void **)&dq, n * (size_t)nFields, 4);
+    if (e == hipSuccess) e = AP((void **)&dmat, n, sizeof(ID));
+    if (e == hipSuccess && nCaptures) e = AP((void **)&dTmax, n, 4);
+    if (e == hipSuccess && nCaptures) e = AP((void **)&dDoseCap, n, 4);
+    if (e == hipSuccess) e = A((void **)&dcd, nMat * 4);
+    if (e == hipSuccess) e = A((void **)&dcp, nMat * 4);
+    if (e == hipSuccess) e = A((void **)&dqf, nMat * 4);
+    if (e == hipSuccess && nSamples) e = A((void **)&dSlice, (size_t)N1 * N3 * nSamples * 4);
+    if (e == hipSuccess && nPoints && points) { e = A((void **)&dIdx, nPoints * 4); if (e == hipSuccess) e = A((void **)&dPts, (size_t)nPoints * nSteps * 4); }
+    // 16-bit ids index the LDS table of the multi-step kernels: the ring cells that lie in the pads must read an id inside it too (any byte is inside the 8-bit table)
+    if (e == hipSuccess && sizeof(ID) > 1) e = hipMemset(dmat - padF, 0, (padF + n + padB) * sizeof(ID));
+    if (e == hipSuccess) e = hipMemcpy(dmat, mat, n * sizeof(ID), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dcd, cd, nMat * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dcp, cp, nMat * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (flags & 1) e = hipMemcpy(dT[0], T, n * 4, hipMemcpyHostToDevice);
+        else {                                                                   // T = initT[material], via the table slot of qf
+            e = hipMemcpy(dqf, initT, nMat * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) { hipLaunchKernelGGL(table_lookup, dim3(2048), dim3(256), 0, 0, dmat, dqf, dT[0], n); e = hipDeviceSynchronize(); }
+        }
+    }
+    if (e == hipSuccess) e = (flags & 2) ? hipMemcpy(dDose, dose, n * 4, hipMemcpyHostToDevice) : hipMemset(dDose, 0, n * 4);
+    if (e == hipSuccess) {
+        if (q) e = hipMemcpy(dq, q, n * 4 * (size_t)nFields, hipMemcpyHostToDevice);
+        else {                                                                   // q = (p p) qf[material], in place
+            e = hipMemcpy(dqf, qf, nMat * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(dq, pressure, n * 4 * (size_t)nFields, hipMemcpyHostToDevice);
+            for (int f = 0; f < nFields && e == hipSuccess; f++) hipLaunchKernelGGL(heat_source, dim3(2048), dim3(256), 0, 0, dq + (size_t)f * n, dmat, dqf, dq + (size_t)f * n, n);
+            if (e == hipSuccess && qOut) e = hipMemcpy(qOut, dq, n * 4 * (size_t)nFields, hipMemcpyDeviceToHost);
+        }
+    }
+    if (e == hipSuccess && dIdx) e = hipMemcpy(dIdx, pointIndex, nPoints * 4, hipMemcpyHostToDevice);
+    int cur = 0;
+    if (e == hipSuccess) {
+        const bfd_bhte_device_run r = {REV ? 1 : 0, (int)sizeof(ID), N1, N2, N3, nMat, {dT[0], dT[1]}, dDose, dq, n, dmat, dcd, dcp, Tcore, dt, nSteps, fieldOfStep,
+                                       sliceJ, fm, dSlice, nSamples, nPoints, dIdx, dPts, nCaptures, captureStep, dTmax, dDoseCap, 0};
+        e = bhte_run_device<REV, ID>(r, &cur, kernelMs);
+    }
     if (e == hipSuccess) e = hipMemcpy(T, dT[cur], n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(dose, dDose, n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dSlice) e = hipMemcpy(monitorSlice, dSlice, (size_t)N1 * N3 * nSamples * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dPts) e = hipMemcpy(points, dPts, (size_t)nPoints * nSteps * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dTmax) e = hipMemcpy(Tmax, dTmax, n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dDoseCap) e = hipMemcpy(doseCap, dDoseCap, n * 4, hipMemcpyDeviceToHost);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
     for (void *p : allocs) hipFree(p);
     if (e != hipSuccess) { bfd_set_error(std::string("bfd_bhte_run: ") + hipGetErrorString(e)); return -10; }
     return 0;

@@ -1,4 +1,4 @@
-// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip, bfd_bonerim.hip and bfd_thermal.hip (and by no other
+// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip, bfd_bonerim.hip, bfd_thermal.hip and bfd_thermal_study.hip (and by no other
 // source: the solver's translation units do not see this file). Host code only.
 //
 // The contract of the twenty-seven entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,

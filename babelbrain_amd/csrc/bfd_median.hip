@@ -21,6 +21,7 @@
 // (2-8 B per voxel) and the halo re-reads (through L2) are negligible beside 27-343 LDS reads per voxel and round. DESIGN.md, "Median filter".
 #include "bfd_internal.h"
 #include "bfd_call.h"
+#include "bfd_thermal_stages.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -183,6 +184,24 @@ void launch_median(const T *in, T *out, const uint8_t *mask, const median_args &
 
 }  // namespace
 
+// The launch of bfd_median_filter3d on device pointers (bfd_thermal_stages.h): in and out are distinct volumes, cvalKey the border value as a key
+hipError_t bfd_stage_median3d(int dtype, const void *in, void *out, const uint8_t *regionMask, int64_t N1, int64_t N2, int64_t N3, int s1, int s2, int s3,
+                              int mode, unsigned cvalKey)
+{
+    median_args p;
+    p.N1 = (int)N1; p.N2 = (int)N2; p.N3 = (int)N3;
+    p.r1 = s1 / 2; p.r2 = s2 / 2; p.r3 = s3 / 2;
+    p.mode = mode;
+    p.cvalKey = cvalKey;
+    p.nTk = (int)((N3 + MT_K - 1) / MT_K);
+    p.nTj = (int)((N2 + MT_J - 1) / MT_J);
+    p.nTiles = (long)p.nTk * p.nTj * ((N1 + MT_I - 1) / MT_I);
+    const unsigned blocks = blocks_for(p.nTiles, 1, MAX_BLOCKS);
+    if (dtype == 0) launch_median<uint8_t>((const uint8_t *)in, (uint8_t *)out, regionMask, p, blocks);
+    else launch_median<uint32_t>((const uint32_t *)in, (uint32_t *)out, regionMask, p, blocks);
+    return hipGetLastError();
+}
+
 extern "C" int bfd_median_filter3d(int device, int dtype, const void *in, void *out, const uint8_t *regionMask,
                                    int64_t N1, int64_t N2, int64_t N3, int s1, int s2, int s3, int mode, double cval, float *kernelMs)
 {
@@ -206,22 +225,16 @@ extern "C" int bfd_median_filter3d(int device, int dtype, const void *in, void *
     const size_t n = (size_t)(N1 * N2 * N3);
     const size_t esz = dtype == 0 ? 1 : 4;
     if (overlap(in, n * esz, out, n * esz)) BFD_FAIL(-1, std::string(who) + ": out may not alias in");      // partial overlap of the two buffers
-    median_args p;
-    p.N1 = (int)N1; p.N2 = (int)N2; p.N3 = (int)N3;
-    p.r1 = s1 / 2; p.r2 = s2 / 2; p.r3 = s3 / 2;
-    p.mode = mode;
+    unsigned cvalKey;
     if (dtype == 0) {
         if (!(cval >= 0.0 && cval <= 255.0) || cval != floor(cval)) BFD_FAIL(-1, std::string(who) + ": cval is not a uint8 value");
-        p.cvalKey = (unsigned)cval;
+        cvalKey = (unsigned)cval;
     } else {
         const float f = (float)cval;
         uint32_t u;
         memcpy(&u, &f, 4);
-        p.cvalKey = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+        cvalKey = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
     }
-    p.nTk = (int)((N3 + MT_K - 1) / MT_K);
-    p.nTj = (int)((N2 + MT_J - 1) / MT_J);
-    p.nTiles = (long)p.nTk * p.nTj * ((N1 + MT_I - 1) / MT_I);
 
     if (int rc = pick_device(who, device)) return rc;
     if (kernelMs) *kernelMs = 0.f;
@@ -237,10 +250,7 @@ extern "C" int bfd_median_filter3d(int device, int dtype, const void *in, void *
     if (regionMask) BFD_STEP(hipMemcpy(dmask, regionMask, n, hipMemcpyHostToDevice));
     BFD_STEP(ev.create());
     BFD_STEP(ev.record(0));
-    const unsigned blocks = blocks_for(p.nTiles, 1, MAX_BLOCKS);
-    if (dtype == 0) launch_median<uint8_t>((const uint8_t *)din.p, (uint8_t *)dout.p, dmask, p, blocks);
-    else launch_median<uint32_t>((const uint32_t *)din.p, (uint32_t *)dout.p, dmask, p, blocks);
-    BFD_STEP(hipGetLastError());
+    BFD_STEP(bfd_stage_median3d(dtype, din.p, dout.p, dmask, N1, N2, N3, s1, s2, s3, mode, cvalKey));
     BFD_STEP(ev.record(1));
     BFD_STEP(ev.sync(1));
     BFD_STEP(ev.elapsed(kernelMs, 0, 1));

@@ -19,6 +19,7 @@
 #include "bfd_internal.h"
 #include "bfd_call.h"
 #include "bfd_thermal_core.h"
+#include "bfd_thermal_stages.h"
 
 namespace {
 
@@ -290,59 +291,83 @@ extern "C" int bfd_class_extrema3d(int device, const float *const *volumes, int 
     if (kernelMs) *kernelMs = 0.f;
     std::vector<unsigned long long> pairs(slots, TH_NO_PAIR);
     unsigned long long counts[TH_CLASSES] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t first[TH_CLASSES];
+    uint32_t first[TH_CLASSES], flags = 0;
     for (int c = 0; c < TH_CLASSES; c++) first[c] = NO_INDEX;
     float total = 0.f;
     if (n) {
-        const int64_t quads = ((int64_t)n + 3) / 4;
         std::vector<Padded> vols((size_t)nVol);
+        std::vector<const float *> dvols((size_t)nVol);
         Padded dmap;
-        DevTemp<uint8_t> dtab;
-        DevTemp<unsigned long long> dout;
-        DevTemp<uint32_t> dsmall;                      // firstOut [8], flags
-        Events ev;
+        DevTemp<uint8_t> dtab, dscratch;
         for (int v = 0; v < nVol; v++) BFD_STEP(vols[(size_t)v].reserve(n, 4));
         BFD_STEP(dmap.reserve(n, (size_t)idBytes));
         BFD_STEP(dtab.alloc((size_t)nMat));
-        BFD_STEP(dout.alloc((MAX_VOL + 1) * TH_CLASSES));
-        BFD_STEP(dsmall.alloc(TH_CLASSES + 1));
-        for (int v = 0; v < nVol; v++) BFD_STEP(vols[(size_t)v].upload(volumes[v]));
+        BFD_STEP(dscratch.alloc(bfd_class_extrema_scratch()));
+        for (int v = 0; v < nVol; v++) { BFD_STEP(vols[(size_t)v].upload(volumes[v])); dvols[(size_t)v] = (const float *)vols[(size_t)v].d.p; }
         BFD_STEP(dmap.upload(map));
         BFD_STEP(hipMemcpy(dtab, classOf, (size_t)nMat, hipMemcpyHostToDevice));
-        BFD_STEP(ev.create());
-        const unsigned blocks = blocks_for(quads, THREADS, SWEEP_BLOCKS);
-        uint32_t flags = 0;
-        for (int v0 = 0; v0 < nVol; v0 += MAX_VOL) {  // ceil(nVol / 4) launches over the same map
-            const int nv = std::min(MAX_VOL, nVol - v0);
-            unsigned long long init[(MAX_VOL + 1) * TH_CLASSES];
-            uint32_t small[TH_CLASSES + 1];
-            for (int q = 0; q < (MAX_VOL + 1) * TH_CLASSES; q++) init[q] = 0;
-            for (int c = 0; c < TH_CLASSES; c++) small[c] = NO_INDEX;
-            small[TH_CLASSES] = 0;
-            extrema_args a;
-            for (int v = 0; v < MAX_VOL; v++) a.vol[v] = (const float *)vols[(size_t)(v0 + std::min(v, nv - 1))].d.p;
-            float ms = 0.f;
-            BFD_STEP(hipMemcpy(dout, init, sizeof init, hipMemcpyHostToDevice));
-            BFD_STEP(hipMemcpy(dsmall, small, sizeof small, hipMemcpyHostToDevice));
-            BFD_STEP(ev.record(0));
-            if (idBytes == 1) launch_extrema<1>(nv, blocks, a, dmap.d.p, (int64_t)n, quads, dtab.p, nMat, dout.p, dsmall.p, dsmall.p + TH_CLASSES);
-            else if (idBytes == 2) launch_extrema<2>(nv, blocks, a, dmap.d.p, (int64_t)n, quads, dtab.p, nMat, dout.p, dsmall.p, dsmall.p + TH_CLASSES);
-            else launch_extrema<4>(nv, blocks, a, dmap.d.p, (int64_t)n, quads, dtab.p, nMat, dout.p, dsmall.p, dsmall.p + TH_CLASSES);
-            BFD_STEP(hipGetLastError());
-            BFD_STEP(ev.record(1));
-            BFD_STEP(ev.sync(1));
-            BFD_STEP(ev.elapsed(&ms, 0, 1));
-            total += ms;
-            BFD_STEP(hipMemcpy(init, dout, sizeof init, hipMemcpyDeviceToHost));
-            BFD_STEP(hipMemcpy(small, dsmall, sizeof small, hipMemcpyDeviceToHost));
-            for (int v = 0; v < nv; v++)
-                for (int c = 0; c < TH_CLASSES; c++) pairs[(size_t)(v0 + v) * TH_CLASSES + c] = init[v * TH_CLASSES + c];
-            for (int c = 0; c < TH_CLASSES; c++) { counts[c] = init[MAX_VOL * TH_CLASSES + c]; first[c] = small[c]; }
-            flags |= small[TH_CLASSES];
-        }
-        if (flags & FLAG_ID) BFD_FAIL(-1, std::string(who) + DATA_REFUSED + "an id of the map is not below nMat");
-        if (flags & FLAG_VALUE) BFD_FAIL(-1, std::string(who) + DATA_REFUSED + "a value is not finite");
+        BFD_STEP(bfd_stage_class_extrema(dvols.data(), nVol, dmap.d.p, idBytes, (int64_t)n, dtab.p, nMat, dscratch.p, pairs.data(), counts, first, &flags, &total,
+                                         nullptr, nullptr));
     }
+    if (const int refused = bfd_class_extrema_finish(nVol, pairs.data(), counts, first, flags, count, maxIn, argIn, maxKey, argKey))
+        BFD_FAIL(-1, std::string(who) + DATA_REFUSED + (refused == 1 ? "an id of the map is not below nMat" : "a value is not finite"));
+    if (kernelMs) *kernelMs = total;
+    return 0;
+}
+
+size_t bfd_class_extrema_scratch(void) { return (MAX_VOL + 1) * TH_CLASSES * sizeof(unsigned long long) + (TH_CLASSES + 1) * sizeof(uint32_t); }
+
+hipError_t bfd_stage_class_extrema(const float *const *dVolumes, int nVol, const void *dMap, int idBytes, int64_t n, const uint8_t *dClassOf, int nMat,
+                                   void *scratch, unsigned long long *pairs, unsigned long long *counts, uint32_t *first, uint32_t *flags, float *kernelMs,
+                                   int64_t *bytesUp, int64_t *bytesDown)
+{
+#define TH_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+    unsigned long long *dout = (unsigned long long *)scratch;
+    uint32_t *dsmall = (uint32_t *)(dout + (MAX_VOL + 1) * TH_CLASSES);                      // firstOut [8], flags
+    const int64_t quads = (n + 3) / 4;
+    Events ev;
+    TH_TRY(ev.create());
+    const unsigned blocks = blocks_for(quads, THREADS, SWEEP_BLOCKS);
+    for (int v0 = 0; v0 < nVol; v0 += MAX_VOL) {  // ceil(nVol / 4) launches over the same map
+        const int nv = std::min(MAX_VOL, nVol - v0);
+        unsigned long long init[(MAX_VOL + 1) * TH_CLASSES];
+        uint32_t small[TH_CLASSES + 1];
+        for (int q = 0; q < (MAX_VOL + 1) * TH_CLASSES; q++) init[q] = 0;
+        for (int c = 0; c < TH_CLASSES; c++) small[c] = NO_INDEX;
+        small[TH_CLASSES] = 0;
+        extrema_args a;
+        for (int v = 0; v < MAX_VOL; v++) a.vol[v] = dVolumes[v0 + std::min(v, nv - 1)];
+        float ms = 0.f;
+        TH_TRY(hipMemcpy(dout, init, sizeof init, hipMemcpyHostToDevice));
+        TH_TRY(hipMemcpy(dsmall, small, sizeof small, hipMemcpyHostToDevice));
+        TH_TRY(ev.record(0));
+        if (idBytes == 1) launch_extrema<1>(nv, blocks, a, dMap, n, quads, dClassOf, nMat, dout, dsmall, dsmall + TH_CLASSES);
+        else if (idBytes == 2) launch_extrema<2>(nv, blocks, a, dMap, n, quads, dClassOf, nMat, dout, dsmall, dsmall + TH_CLASSES);
+        else launch_extrema<4>(nv, blocks, a, dMap, n, quads, dClassOf, nMat, dout, dsmall, dsmall + TH_CLASSES);
+        TH_TRY(hipGetLastError());
+        TH_TRY(ev.record(1));
+        TH_TRY(ev.sync(1));
+        TH_TRY(ev.elapsed(&ms, 0, 1));
+        if (kernelMs) *kernelMs += ms;
+        TH_TRY(hipMemcpy(init, dout, sizeof init, hipMemcpyDeviceToHost));
+        TH_TRY(hipMemcpy(small, dsmall, sizeof small, hipMemcpyDeviceToHost));
+        if (bytesUp) *bytesUp += (int64_t)(sizeof init + sizeof small);
+        if (bytesDown) *bytesDown += (int64_t)(sizeof init + sizeof small);
+        for (int v = 0; v < nv; v++)
+            for (int c = 0; c < TH_CLASSES; c++) pairs[(size_t)(v0 + v) * TH_CLASSES + c] = init[v * TH_CLASSES + c];
+        for (int c = 0; c < TH_CLASSES; c++) { counts[c] = init[MAX_VOL * TH_CLASSES + c]; first[c] = small[c]; }
+        *flags |= small[TH_CLASSES];
+    }
+    return hipSuccess;
+#undef TH_TRY
+}
+
+int bfd_class_extrema_finish(int nVol, const unsigned long long *pairs, const unsigned long long *counts, const uint32_t *first, uint32_t flags,
+                             int64_t *count, float *maxIn, int64_t *argIn, float *maxKey, int64_t *argKey)
+{
+    if (flags & FLAG_ID) return 1;
+    if (flags & FLAG_VALUE) return 2;
+    const size_t slots = (size_t)nVol * TH_CLASSES;
     for (int c = 0; c < TH_CLASSES; c++) count[c] = (int64_t)counts[c];
     for (size_t s = 0; s < slots; s++) {
         const int c = (int)(s % TH_CLASSES);
@@ -352,8 +377,45 @@ extern "C" int bfd_class_extrema3d(int device, const float *const *volumes, int 
         maxKey[s] = keyed == TH_NO_PAIR ? 0.f : th_key_value(th_pair_key(keyed));
         argKey[s] = th_pair_index(keyed);
     }
-    if (kernelMs) *kernelMs = total;
     return 0;
+}
+
+void bfd_loss_survey_scratch(int64_t rows, int64_t N3, size_t *partialWords, size_t *sumWords)
+{
+    const int64_t chunks = (rows + ROWS - 1) / ROWS, width = 3 * N3;
+    *partialWords = (size_t)(chunks * width);
+    *sumWords = (size_t)(((chunks + FOLD - 1) / FOLD) * width);
+}
+
+hipError_t bfd_stage_loss_survey(const float *p, float *pw, const void *map, int idBytes, const uint8_t *brainMask, const uint8_t *classOf, const double *rho,
+                                 const double *c, int nMat, int writeWater, int64_t rows, int64_t N3, double rhoWater, double cWater, double dx2, double *partial,
+                                 double *sums, unsigned long long *pairs, uint32_t *flags, const double **result)
+{
+    const int64_t chunks = (rows + ROWS - 1) / ROWS, width = 3 * N3;
+    const unsigned kBlocks = (unsigned)((N3 + THREADS - 1) / THREADS);
+    const dim3 grid((unsigned)(chunks * kBlocks));  // below 2^31: chunks * kBlocks <= (rows / 128 + 1) * (N3 / 256 + 1)
+    survey_args a = {p, pw, map, brainMask, classOf, rho, c, nMat, writeWater, rows, N3, kBlocks, rhoWater, cWater, dx2};
+    if (idBytes == 1) hipLaunchKernelGGL(th_survey<1>, grid, dim3(THREADS), 0, 0, a, partial, pairs, flags);
+    else if (idBytes == 2) hipLaunchKernelGGL(th_survey<2>, grid, dim3(THREADS), 0, 0, a, partial, pairs, flags);
+    else hipLaunchKernelGGL(th_survey<4>, grid, dim3(THREADS), 0, 0, a, partial, pairs, flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the levels of the tree go to and fro between the two buffers until one row of sums is left: ceil(log32(chunks)) launches, at least one
+    double *from = partial, *to = sums;
+    int64_t count = chunks;
+    do {
+        const int64_t nodes = (count + FOLD - 1) / FOLD;
+        for (int64_t g0 = 0; g0 < nodes; g0 += 65535) {      // gridDim.y is 65535 at the most
+            const unsigned gy = (unsigned)std::min<int64_t>(65535, nodes - g0);
+            hipLaunchKernelGGL(th_fold, dim3((unsigned)((width + THREADS - 1) / THREADS), gy), dim3(THREADS), 0, 0, (const double *)(from + g0 * FOLD * width),
+                               count - g0 * FOLD, width, to + g0 * width);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+        std::swap(from, to);
+        count = nodes;
+    } while (count > 1);
+    *result = from;
+    return hipSuccess;
 }
 
 extern "C" int bfd_loss_survey3d(int device, const float *p, const float *pw, int nFields, const void *map, int idBytes, int64_t N1, int64_t N2, int64_t N3,
@@ -398,7 +460,9 @@ extern "C" int bfd_loss_survey3d(int device, const float *p, const float *pw, in
     std::vector<unsigned long long> best(2 * F, TH_NO_PAIR);
     float total = 0.f;
     if (n) {
-        const int64_t rows = N1 * N2, chunks = (rows + ROWS - 1) / ROWS, width = 3 * N3;
+        const int64_t rows = N1 * N2, width = 3 * N3;
+        size_t partialWords = 0, sumWords = 0;
+        bfd_loss_survey_scratch(rows, N3, &partialWords, &sumWords);
         DevTemp<float> dp, dpw;                        // one tissue field; every water field where the cleared fields go back, else one
         DevTemp<uint8_t> dmap, dtab, dmask;
         DevTemp<double> drho, dc, dpartial, dsums;
@@ -412,8 +476,8 @@ extern "C" int bfd_loss_survey3d(int device, const float *p, const float *pw, in
         if (brainMask) BFD_STEP(dmask.alloc(n));
         BFD_STEP(drho.alloc((size_t)nMat));
         BFD_STEP(dc.alloc((size_t)nMat));
-        BFD_STEP(dpartial.alloc((size_t)(chunks * width)));
-        BFD_STEP(dsums.alloc((size_t)(((chunks + FOLD - 1) / FOLD) * width)));
+        BFD_STEP(dpartial.alloc(partialWords));
+        BFD_STEP(dsums.alloc(sumWords));
         BFD_STEP(dpairs.alloc(2));
         BFD_STEP(dflags.alloc(1));
         BFD_STEP(hipMemcpy(dmap, map, n * (size_t)idBytes, hipMemcpyHostToDevice));
@@ -423,35 +487,16 @@ extern "C" int bfd_loss_survey3d(int device, const float *p, const float *pw, in
         BFD_STEP(hipMemcpy(dc, c, 8 * (size_t)nMat, hipMemcpyHostToDevice));
         BFD_STEP(hipMemset(dflags, 0, 4));
         BFD_STEP(ev.create());
-        const unsigned kBlocks = (unsigned)((N3 + THREADS - 1) / THREADS);
-        const dim3 grid((unsigned)(chunks * kBlocks));  // below 2^31: chunks * kBlocks <= (rows / 128 + 1) * (N3 / 256 + 1)
         for (size_t f = 0; f < F; f++) {               // the fields are streamed through the same buffers
             float *w = dpw.p + (waterOut ? f * n : 0);
             float ms = 0.f;
             BFD_STEP(hipMemcpy(dp, p + f * n, 4 * n, hipMemcpyHostToDevice));
             BFD_STEP(hipMemcpy(w, pw + f * n, 4 * n, hipMemcpyHostToDevice));
             BFD_STEP(hipMemset(dpairs, 0, 16));
-            survey_args a = {dp.p, w, dmap.p, brainMask ? dmask.p : nullptr, dtab.p, drho.p, dc.p, nMat, waterOut ? 1 : 0, rows, N3, kBlocks, rhoWater, cWater, dx2};
+            const double *result = nullptr;
             BFD_STEP(ev.record(0));
-            if (idBytes == 1) hipLaunchKernelGGL(th_survey<1>, grid, dim3(THREADS), 0, 0, a, dpartial.p, dpairs.p, dflags.p);
-            else if (idBytes == 2) hipLaunchKernelGGL(th_survey<2>, grid, dim3(THREADS), 0, 0, a, dpartial.p, dpairs.p, dflags.p);
-            else hipLaunchKernelGGL(th_survey<4>, grid, dim3(THREADS), 0, 0, a, dpartial.p, dpairs.p, dflags.p);
-            BFD_STEP(hipGetLastError());
-            // the levels of the tree go to and fro between the two buffers until one row of sums is left: ceil(log32(chunks)) launches, at least one
-            double *from = dpartial.p, *to = dsums.p;
-            int64_t count = chunks;
-            do {
-                const int64_t nodes = (count + FOLD - 1) / FOLD;
-                for (int64_t g0 = 0; g0 < nodes; g0 += 65535) {      // gridDim.y is 65535 at the most
-                    const unsigned gy = (unsigned)std::min<int64_t>(65535, nodes - g0);
-                    hipLaunchKernelGGL(th_fold, dim3((unsigned)((width + THREADS - 1) / THREADS), gy), dim3(THREADS), 0, 0, (const double *)(from + g0 * FOLD * width),
-                                       count - g0 * FOLD, width, to + g0 * width);
-                    BFD_STEP(hipGetLastError());
-                }
-                std::swap(from, to);
-                count = nodes;
-            } while (count > 1);
-            const double *result = from;
+            BFD_STEP(bfd_stage_loss_survey(dp.p, w, dmap.p, idBytes, brainMask ? dmask.p : nullptr, dtab.p, drho.p, dc.p, nMat, waterOut ? 1 : 0, rows, N3, rhoWater,
+                                           cWater, dx2, dpartial.p, dsums.p, dpairs.p, dflags.p, &result));
             BFD_STEP(ev.record(1));
             BFD_STEP(ev.sync(1));
             BFD_STEP(ev.elapsed(&ms, 0, 1));

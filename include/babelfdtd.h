@@ -940,6 +940,98 @@ int bfd_loss_survey3d(int device, const float *p, const float *pw, int nFields, 
                       double rhoWater, double cWater, double dx2, float *maxTissue, int64_t *argTissue, float *maxWater, int64_t *argWater,
                       double *eWaterRaw, double *eWater, double *eTissue, float *waterOut /*may be NULL*/, float *kernelMs /*may be NULL*/);
 
+/* ---- Thermal study: the volumes of one Step-3 calculation resident on the device (csrc/bfd_thermal_study.hip) ----
+ * The flow of CalculateTemperatureEffects.py:908-1193 makes some ten calls over the same volumes; through the entries above every one of them
+ * uploads the pressure amplitude and the map again and brings whole volumes back. A bfd_thermal handle holds them on one device from the single
+ * upload of bfd_thermal_set_inputs to the results the caller asks for by name. The arithmetic is that of the entries above: the study runs the
+ * same launch sequences (csrc/bfd_thermal_stages.h), so every result equals what the separate calls give, element by element.
+ * Volumes are HOST pointers in numpy C order [N1][N2][N3] (last axis fastest), as bfd_bhte_run_volumes takes them; fields are
+ * [nFields][N1][N2][N3].
+ * The contract is that of the Step-1 entries: argument errors (-1) are reported before the device is touched, in the order each entry lists them;
+ * -3 for no device or a bad ordinal; -5 for a map id that is not below nMat; -6, with a text naming the missing stage, for a stage asked for
+ * before the stage it needs (set_inputs -> set_scale -> run; results of a stage exist after it); -10 for a HIP error. Outputs are untouched on a
+ * refusal; kernelMs may be NULL and brackets kernels only.
+ * Names of resident volumes (`which`): */
+enum {
+    BFD_THERMAL_TMAX = 0,             /* maximum of T over the captures of the last run; T at its end where it had none */
+    BFD_THERMAL_DOSE_AT_CAPTURE = 1,  /* the dose at the last capture; the dose at the end where the run had none */
+    BFD_THERMAL_T = 2,                /* temperature after the last run */
+    BFD_THERMAL_DOSE = 3,             /* thermal dose after the last run */
+    BFD_THERMAL_Q = 4,                /* heat increment of one ON step, [nFields] volumes, of the last run */
+    BFD_THERMAL_P_MAP = 5,            /* the scaled pressure (one field) or the maximum over the scaled fields (:1115, :1118) */
+    BFD_THERMAL_PW = 6,               /* the water fields, [nFields] volumes, as the median and the survey have left them */
+    BFD_THERMAL_P = 7,                /* the UNSCALED tissue fields, [nFields] volumes */
+    BFD_THERMAL_MAP = 8               /* the material ids (plane getter only) */
+};
+typedef struct bfd_thermal_s *bfd_thermal;
+
+/* N1, N2, N3 >= 3, fewer than 2^31 voxels; 1 <= nFields <= 4096; 1 <= nMat <= bfd_bhte_max_materials(): up to 256 rows give 8-bit resident ids, more
+ * 16-bit ones. Device memory, all of it taken here: 6 + 3 nFields float32 volumes (p, pw, q per field; two of T, dose, Tmax, doseAtCapture, one
+ * scratch volume), the ids and one byte per voxel, with the pads of the bio-heat kernels. -1: handle null; a dimension below 3; 2^31 voxels or
+ * more; nFields; nMat. */
+int bfd_thermal_create(int device, int64_t N1, int64_t N2, int64_t N3, int nFields, int nMat, bfd_thermal *handle);
+void bfd_thermal_destroy(bfd_thermal handle);            /* NULL is accepted */
+
+/* ONE upload each of p and pw (float32 [nFields][N1][N2][N3]) and of the map (ids of idBytes 1, 2 or 4, narrowed on the device). An id that is not
+ * below nMat: -5, nothing is kept and set_inputs has to be called again. Any earlier scale and run are forgotten. -1: a null pointer; idBytes. */
+int bfd_thermal_set_inputs(bfd_thermal handle, const float *p, const float *pw, const void *map, int idBytes);
+
+/* The 3 x 3 x 3 median (reflect) of :908-918 merged under class bit `bit` of classOf (uint8 [nMat]), in place on every resident field of `which`
+ * (BFD_THERMAL_P or BFD_THERMAL_PW): what bfd_median_filter3d gives with the region mask formed from map and table. -1: a null pointer; bit outside
+ * 0 .. 7; which. */
+int bfd_thermal_median_region(bfd_thermal handle, const uint8_t *classOf, int bit, int which, float *kernelMs /*may be NULL*/);
+
+/* bfd_loss_survey3d on the resident fields: same arguments from classOf on, same outputs ([nFields], sums [nFields][N3]); the resident water fields
+ * are cleared over class bit 1, as waterOut == pw does. brainMask (uint8 [N1][N2][N3], may be NULL) is uploaded where given. -1: a null pointer;
+ * rhoWater, cWater; a rho or c; dx2; after the pass, a value that is not finite ("refused data"). */
+int bfd_thermal_loss_survey(bfd_thermal handle, const uint8_t *classOf, const uint8_t *brainMask /*may be NULL*/, const double *rho, const double *c,
+                            double rhoWater, double cWater, double dx2, float *maxTissue, int64_t *argTissue, float *maxWater, int64_t *argWater,
+                            double *eWaterRaw, double *eWater, double *eTissue, float *kernelMs /*may be NULL*/);
+
+/* The pressure ratio of every field. No pass over a volume: p stays unscaled on the device, and the scaled value of a voxel, defined once in
+ * csrc/bfd_thermal_study_core.h, is formed wherever it is used (heat source, p_map, its extrema and planes):
+ *   mode 0  one field, pAmp * PressureRatio (:960, :1029): (float)((double)p * ratio[0]), the float64 product NumPy >= 2 forms, rounded once
+ *   mode 1  InputsBHTE[n] *= PressureRatio[n] (:975-977): the float32 product p * (float)ratio[n]
+ * -1: a null pointer; mode; mode 0 with several fields; a ratio that is not finite. */
+int bfd_thermal_set_scale(bfd_thermal handle, const double *ratio /*[nFields]*/, int mode);
+
+/* The step loop of bfd_bhte_run_protocol on the resident volumes: cd, cp, qf, initT float32 [nMat]; q = ((s s) qf[m]) from the scaled pressure s.
+ * flags bit 0: T0 holds the initial temperature; bit 1: dose0 the initial dose; bit 2: start over; bit 3: the first capture of a run that continues
+ * merges into the Tmax held, so that Tmax spans the runs (np.maximum over the chunks of :1094-1098); bit 4 (without bits 0 and 1): start from the
+ * temperature and dose of bfd_thermal_set_previous, copied on the device. A run without bit 0 (bit 1) continues from the
+ * resident temperature (dose) of the run before; the first run, or one with bit 2, starts from initT[material] (a dose of zero). points
+ * [nPoints][nSteps] of pointIndex (C-order linear indices) come back; T, dose, q, Tmax and the dose at the last capture stay. Without captures Tmax
+ * is T at the end. nSteps == 0 sets the start state and returns. nFactorMonitoring is accepted and unused: the study keeps no monitored plane.
+ * -1: a null pointer (handle, cd, cp, qf); flags; a volume the flags announce; a fresh start without T0 and initT; nSteps; a schedule entry; the
+ * point list; a point outside the volume; the capture list. */
+int bfd_thermal_run(bfd_thermal handle, const float *cd, const float *cp, const float *qf, const float *initT /*may be NULL*/, int flags,
+                    const float *T0 /*may be NULL*/, const float *dose0 /*may be NULL*/, float Tcore, double dt, int nSteps, const int32_t *fieldOfStep,
+                    int nFactorMonitoring, int64_t nPoints, const uint32_t *pointIndex, float *points, int nCaptures, const int32_t *captureStep,
+                    double *kernelMs /*may be NULL*/);
+
+/* PreviousData's volumes (:948-956), uploaded ONCE: FinalTemp and FinalDose start the first bio-heat call (:972) and the protocol (:1065), TempEndFUS is
+ * merged twice (:994, :1108). Three more float32 volumes of device memory, taken here. -1: a null pointer. */
+int bfd_thermal_set_previous(bfd_thermal handle, const float *finalTemp, const float *finalDose, const float *tempEndFUS);
+
+/* resident = np.maximum(resident, hostVolume) (:994, :1108) for Tmax, doseAtCapture, T or dose; a NaN on either side wins. hostVolume NULL: the
+ * TempEndFUS of bfd_thermal_set_previous (-6 without it). */
+int bfd_thermal_merge_max(bfd_thermal handle, int which, const float *hostVolume);
+
+/* bfd_class_extrema3d over resident volumes named in which[nVol] (Tmax, doseAtCapture, T, dose, p_map and, with one field, the unscaled p;
+ * 1 <= nVol <= 64), same outputs. */
+int bfd_thermal_extrema(bfd_thermal handle, const int *which, int nVol, const uint8_t *classOf /*[nMat]*/, int64_t *count /*[8]*/, float *maxIn,
+                        int64_t *argIn, float *maxKey, int64_t *argKey, float *kernelMs /*may be NULL*/);
+
+/* One named result to the host, float32 (dtype 0); q, pw and p come as [nFields] volumes. dtype 1: float64, for p_map of one field in mode 0 alone,
+ * (double)p * ratio, the type SaveDict['p_map'] has at :1115. */
+int bfd_thermal_get(bfd_thermal handle, int which, void *out, int dtype);
+/* [:, j, :] of p_map (float32 [N1][N3]), of the map (uint32 [N1][N3]) or, with one field, of the unscaled p: p_map_central (for one field the
+ * caller forms pAmp[:, cy, :] * PressureRatio in float64, as :1116 does) and MaterialMap_central of :1116-1120 */
+int bfd_thermal_get_plane(bfd_thermal handle, int which, int64_t j, void *out);
+
+/* Bytes the study has copied host -> device and device -> host since its creation, counted where each copy is issued */
+int bfd_thermal_traffic(bfd_thermal handle, int64_t *bytesUp, int64_t *bytesDown);
+
 #ifdef __cplusplus
 }
 #endif
