@@ -153,11 +153,12 @@ def _axis_rule(ind, ffs, stepf, N, pml, tight, isZ, LOffset, ROffset, Shrink_L, 
 
 def plan_domain(labels, SpatialStep, *, PMLThickness=12, FocalLength, Aperture, ZIntoSkin=0.0, TxMechanicalAdjustmentX=0.0, TxMechanicalAdjustmentY=0.0,
                 TxMechanicalAdjustmentZ=0.0, ExtraDepthAdjust=0.0, ExtraAdjustX=(0.0,), ExtraAdjustY=(0.0,), PaddingForRayleigh=0, PaddingForKArray=0,
-                ZTxCorrecton=0.0, bTightNarrowBeamDomain=False, zLengthBeyonFocalPointWhenNarrow=4e-2, DomeType=False, flip_k=True):
+                ZTxCorrecton=0.0, bTightNarrowBeamDomain=False, zLengthBeyonFocalPointWhenNarrow=4e-2, DomeType=False, flip_k=True, survey=None):
     """The DomainPlan of UpdateConditions, :1840-2074, for the label volume `labels` (uint8, as stored) and the parameters the method reads from
     `self`, under their names there. Two passes: the first grows an offset where the cone reaches into the absorbing layer and, with
     bTightNarrowBeamDomain, shrinks the crop to the cone; the second sizes the domain. Each pass calls survey once on the crop in force; no
-    volume is formed on the host. ValueError where the reference raises: not exactly one voxel of 5, no tissue in the crop, empty ExtraAdjust lists,
+    volume is formed on the host. survey: a callable with survey's signature that the two passes call instead (None: survey itself, which uploads the
+    labels for each call; AcousticStudy.survey reads labels that are on the device already). ValueError where the reference raises: not exactly one voxel of 5, no tissue in the crop, empty ExtraAdjust lists,
     a bound read from an empty cone. NotImplementedError for DomeType."""
     if DomeType:
         raise NotImplementedError('DomeType domains are not planned here')
@@ -171,6 +172,7 @@ def plan_domain(labels, SpatialStep, *, PMLThickness=12, FocalLength, Aperture, 
     if not ExtraAdjustX or not ExtraAdjustY:
         raise ValueError('ExtraAdjustX and ExtraAdjustY must hold at least one entry (the reference raises at :1991 otherwise)')
     tight = bool(bTightNarrowBeamDomain)
+    survey_of = globals()['survey'] if survey is None else survey          # the keyword carries the function's name; the module's is looked up per call
     M = np.array(a.shape, np.int64)
     ZSourceLocation = int(np.round(ZIntoSkin / SpatialStep)) + pml
     LOff = [pml, pml, pml + operator.index(PaddingForRayleigh) + operator.index(PaddingForKArray) + int(np.round(ZTxCorrecton / SpatialStep))]
@@ -184,7 +186,7 @@ def plan_domain(labels, SpatialStep, *, PMLThickness=12, FocalLength, Aperture, 
             hi = [int(M[q]) - ShR[q] for q in range(3)]
             if any(ShL[q] < 0 or ShL[q] > hi[q] for q in range(3)):
                 raise ValueError('the crop %r : %r is empty or outside the label volume' % (ShL, hi))
-            _, bounds, focal = survey(a, (list(ShL), hi), flip_k)
+            _, bounds, focal = survey_of(a, (list(ShL), hi), flip_k)
             if bounds[4] < 0:
                 raise ValueError('no tissue in the crop %r : %r of the label volume (np.min of an empty array at :1904)' % (ShL, hi))
             FirstVoxelTissueZ = int(bounds[4]) + LOff[2]

@@ -44,6 +44,9 @@ ABI_SYMBOLS = [
     'bfd_select_component3d', 'bfd_bone_rim_correct3d', 'bfd_class_extrema3d', 'bfd_loss_survey3d',
     'bfd_thermal_create', 'bfd_thermal_destroy', 'bfd_thermal_set_inputs', 'bfd_thermal_median_region', 'bfd_thermal_loss_survey', 'bfd_thermal_set_scale',
     'bfd_thermal_run', 'bfd_thermal_set_previous', 'bfd_thermal_merge_max', 'bfd_thermal_extrema', 'bfd_thermal_get', 'bfd_thermal_get_plane', 'bfd_thermal_traffic',
+    'bfd_set_material_map_device', 'bfd_set_reflector_device', 'bfd_set_sensor_box', 'bfd_pack_results',
+    'bfd_acoustic_create', 'bfd_acoustic_destroy', 'bfd_acoustic_set_volumes', 'bfd_acoustic_survey', 'bfd_acoustic_assemble', 'bfd_acoustic_attach',
+    'bfd_acoustic_pack', 'bfd_acoustic_get', 'bfd_acoustic_traffic',
 ]
 
 
@@ -54,6 +57,21 @@ class Config(C.Structure):
                 ('selMapsRMS', C.c_uint32), ('selMapsSensors', C.c_uint32), ('qfactorCorrection', C.c_int32),
                 ('device', C.c_int32), ('kernelVariant', C.c_int32), ('rmsFirstStep', C.c_int32), ('sensorMode', C.c_int32),
                 ('h', C.c_double), ('dt', C.c_double), ('freq', C.c_double), ('reflectionLimit', C.c_double)]
+
+
+class PackSpec(C.Structure):
+    """bfd_pack_spec of include/babelfdtd.h"""
+    _fields_ = [('lo', C.c_int32 * 3), ('hi', C.c_int32 * 3), ('zSource', C.c_int32), ('O', C.c_int32 * 3), ('at', C.c_int32 * 3),
+                ('flipK', C.c_int32), ('applyScale', C.c_int32), ('ampScale', C.c_double), ('correction', C.c_double)]
+
+
+def pack_spec(lo, hi, zSource, O, at=(0, 0, 0), flipK=True, correction=None):
+    """The PackSpec of a kept region and an output: the one place where the two scales are formed. correction None: no scaling at all; else
+    ampScale = correction * sqrt(2) in float64 (BASE:2440) and the factor itself."""
+    i3 = C.c_int32 * 3
+    scaled = correction is not None
+    return PackSpec(i3(*[int(v) for v in lo]), i3(*[int(v) for v in hi]), int(zSource), i3(*[int(v) for v in O]), i3(*[int(v) for v in at]), int(bool(flipK)),
+                    int(scaled), float(correction * np.sqrt(2)) if scaled else 0.0, float(correction) if scaled else 0.0)
 
 
 class EngineError(RuntimeError):
@@ -115,6 +133,10 @@ def load_library():
     lib.bfd_set_sources_separable.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.bfd_set_sensor_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+    lib.bfd_set_material_map_device.argtypes = lib.bfd_set_material_map.argtypes
+    lib.bfd_set_reflector_device.argtypes = lib.bfd_set_reflector.argtypes
+    lib.bfd_set_sensor_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.bfd_pack_results.argtypes = [C.c_void_p, C.POINTER(PackSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     lib.bfd_run.argtypes = [C.c_void_p, C.c_int32]
     lib.bfd_half_step_stress.argtypes = [C.c_void_p]
     lib.bfd_half_step_velocity.argtypes = [C.c_void_p]
@@ -270,6 +292,17 @@ def load_library():
     lib.bfd_thermal_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.bfd_thermal_get_plane.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
     lib.bfd_thermal_traffic.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.bfd_acoustic_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.bfd_acoustic_destroy.argtypes = [C.c_void_p]
+    lib.bfd_acoustic_destroy.restype = None
+    lib.bfd_acoustic_set_volumes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bfd_acoustic_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bfd_acoustic_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_int, C.c_void_p]
+    lib.bfd_acoustic_attach.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bfd_acoustic_pack.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PackSpec), C.c_int]
+    lib.bfd_acoustic_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.bfd_acoustic_traffic.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.bfd_placement_cache_release.argtypes = []
     lib.bfd_placement_cache_release.restype = C.c_int64
     if lib.bfd_abi_version() != 7:
@@ -449,6 +482,43 @@ class Engine:
         _check(self.lib.bfd_set_sensor_map(self.h, _ptr(a), *_estrides(a), C.byref(n)), 'bfd_set_sensor_map')
         return n.value
 
+    # ---- inputs that are on the device already ----
+    def _device_view(self, t, shape):
+        """(pointer, element strides) of a 4-byte integer torch tensor on this engine's device; what wrote it is waited for."""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise TypeError('a torch tensor on the device is expected (host arrays go through the host setters)')
+        if t.element_size() != 4 or t.is_floating_point():
+            raise TypeError('a 32-bit integer tensor is expected, got %s' % t.dtype)
+        assert tuple(t.shape) == tuple(shape), (tuple(t.shape), tuple(shape))
+        if any(s < 0 for s in t.stride()):
+            raise ValueError('negative strides are not supported')
+        torch.cuda.current_stream(t.device).synchronize()       # the engine's stream waits for no other stream
+        return t.data_ptr(), [int(s) for s in t.stride()]
+
+    def set_material_map_device(self, slab_with_ghosts, ghostLow=0, ghostHigh=0):
+        """set_material_map from a 32-bit integer torch tensor (N1,N2,ghostLow+nk+ghostHigh) on the engine's device, any strides >= 0:
+        read in place (bfd_set_material_map_device). The tensor may be released when the call has returned."""
+        p, st = self._device_view(slab_with_ghosts, (self.shape[0], self.shape[1], self.shape[2] + ghostLow + ghostHigh))
+        _check(self.lib.bfd_set_material_map_device(self.h, C.c_void_p(p + 4 * ghostLow * st[2]), st[0], st[1], st[2], ghostLow, ghostHigh),
+               'bfd_set_material_map_device')
+
+    def set_reflector_device(self, mask):
+        """set_reflector from a 32-bit integer torch tensor of the slab's shape on the engine's device; None clears the mask."""
+        if mask is None:
+            _check(self.lib.bfd_set_reflector_device(self.h, None, 0, 0, 0), 'bfd_set_reflector_device')
+            return
+        p, st = self._device_view(mask, self.shape)
+        _check(self.lib.bfd_set_reflector_device(self.h, C.c_void_p(p), *st), 'bfd_set_reflector_device')
+
+    def set_sensor_box(self, lo, size):
+        """The sensors of the dense box lo <= (i, j, k) < lo + size without a SensorMap volume (bfd_set_sensor_box); returns their number."""
+        lo_, size_ = np.ascontiguousarray(lo, np.int32), np.ascontiguousarray(size, np.int32)
+        assert lo_.shape == (3,) and size_.shape == (3,)
+        n = C.c_int64()
+        _check(self.lib.bfd_set_sensor_box(self.h, _ptr(lo_), _ptr(size_), C.byref(n)), 'bfd_set_sensor_box')
+        return n.value
+
     # ---- stepping ----
     def run(self, nSteps):
         _check(self.lib.bfd_run(self.h, int(nSteps)), 'bfd_run')
@@ -558,6 +628,29 @@ class Engine:
         pk = np.zeros((len(self.selS), self.num_sensors), np.float32)
         _check(self.lib.bfd_get_sensor_dft(self.h, float(freq), _ptr(F.view(np.float32)), _ptr(pk)), 'bfd_get_sensor_dft')
         return F, pk
+
+    def pack_results(self, lo, hi, zSource, O=None, at=(0, 0, 0), flipK=True, correction=None, want=('p_amp', 'p_complex', 'peak')):
+        """The Pressure results of a sensorMode 1 run as the cropped, zeroed, scaled and flipped volumes the caller saves, formed on the device
+        (bfd_pack_results). lo / hi: the Crop offsets of the kept region; O: output shape (default: the kept size), at: where the kept region lands
+        in it; correction: the dispersion factor (None: no scaling at all, not even the sqrt(2) of the amplitude). Returns
+        {'p_amp': float32, 'p_complex': complex64, 'peak': float32} for the names in `want`, and the kernel time in 'kernel_ms'."""
+        kept = [n - int(l) - int(h) for n, l, h in zip(self.shape, lo, hi)]
+        O = kept if O is None else [int(v) for v in O]
+        sp = pack_spec(lo, hi, zSource, O, at, flipK, correction)
+        shape = tuple(max(v, 0) for v in O)
+        out = {}
+        if 'p_amp' in want:
+            out['p_amp'] = np.zeros(shape, np.float32)
+        if 'p_complex' in want:
+            out['p_complex'] = np.zeros(shape, np.complex64)
+        if 'peak' in want:
+            out['peak'] = np.zeros(shape, np.float32)
+        ms = C.c_float()
+        cplx = out['p_complex'].view(np.float32) if 'p_complex' in out else None
+        _check(self.lib.bfd_pack_results(self.h, C.byref(sp), _ptr(out.get('p_amp')), _ptr(cplx), _ptr(out.get('peak')), C.byref(ms)),
+               'bfd_pack_results')
+        out['kernel_ms'] = ms.value
+        return out
 
     def get_map(self, kind, name, out=None):
         if out is None:

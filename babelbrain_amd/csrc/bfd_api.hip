@@ -464,6 +464,47 @@ int bfd_set_materials(bfd_sim *s, const double *matlist, const double *qcorr)
     return 0;
 }
 
+}  // extern "C"
+
+// The material ids of the readable span [k = -ghostLow .. nk-1+ghostHigh] that starts at devBase (device memory), into the engine's x-fastest ids:
+// the tail the host form and the device form of the setter share. who = the entry's name for the messages
+static int material_map_from_device(bfd_sim *s, const char *who, const uint32_t *devBase, int64_t s1, int64_t s2, int64_t s3, int32_t ghostLow, int nkSpan)
+{
+    const bfd_dev &d = s->d;
+    DevTemp<int> flag; int hflag = 0;
+    hipError_t e = flag.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s->stream);
+    if (e == hipSuccess) {
+        // destination covers local planes -2..nk+1; source plane index = local k + ghostLow, clamped to the span
+        hipLaunchKernelGGL((gather_to_xfast<0, uint16_t>), dim3(grid_for((long)s->nalloc)), dim3(256), 0, s->stream,
+                           devBase, (long)s1, (long)s2, (long)s3, s->matBase, d.N1, d.N2, d.nk + 4, ghostLow - 2, 0, nkSpan - 1,
+                           (uint32_t)s->cfg.nMat, flag.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) BFD_FAIL(-10, std::string(who) + ": " + hipGetErrorString(e));
+    if (hflag) BFD_FAIL(-5, std::string(who) + ": MaterialMap holds an id >= number of MaterialList rows");
+    s->haveMap = true; invalidate_lists(s);
+    return 0;
+}
+
+// The span [p, p + elems) of uint32 is device memory of the sim's own device, inside one allocation: what the device forms of the setters ask of
+// their pointer before a kernel reads through it. A host pointer, managed memory, another device's memory or a span that runs past its
+// allocation: false
+static bool device_span_of(const bfd_sim *s, const uint32_t *p, size_t elems)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (at.type != hipMemoryTypeDevice || at.device != s->cfg.device) return false;
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)base;
+    return a >= b && elems * sizeof(uint32_t) <= size - (a - b);
+}
+
+extern "C" {
+
 int bfd_set_material_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3,
                          int32_t ghostLow, int32_t ghostHigh)
 {
@@ -478,23 +519,38 @@ int bfd_set_material_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2
     const int nkSpan = d.nk + ghostLow + ghostHigh;
     if (s1 < 0 || s2 < 0 || s3 < 0) BFD_FAIL(-2, "negative strides are not supported");
     const size_t span = span_elems(d.N1, d.N2, nkSpan, s1, s2, s3);
-    DevTemp<uint32_t> tmp; DevTemp<int> flag; int hflag = 0;
+    DevTemp<uint32_t> tmp;
     BFD_HIP(tmp.alloc(span));
-    hipError_t e = hipMemcpyAsync(tmp, base, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = flag.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s->stream);
-    if (e == hipSuccess) {
-        // destination covers local planes -2..nk+1; source plane index = local k + ghostLow, clamped to the span
-        hipLaunchKernelGGL((gather_to_xfast<0, uint16_t>), dim3(grid_for((long)s->nalloc)), dim3(256), 0, s->stream,
-                           tmp.p, (long)s1, (long)s2, (long)s3, s->matBase, d.N1, d.N2, d.nk + 4, ghostLow - 2, 0, nkSpan - 1,
-                           (uint32_t)s->cfg.nMat, flag.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    const hipError_t e = hipMemcpyAsync(tmp, base, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream);
     if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_set_material_map: ") + hipGetErrorString(e));
-    if (hflag) BFD_FAIL(-5, "bfd_set_material_map: MaterialMap holds an id >= number of MaterialList rows");
-    s->haveMap = true; invalidate_lists(s);
+    return material_map_from_device(s, "bfd_set_material_map", tmp, s1, s2, s3, ghostLow, nkSpan);
+}
+
+int bfd_set_material_map_device(bfd_sim *s, const uint32_t *devMap, int64_t s1, int64_t s2, int64_t s3,
+                                int32_t ghostLow, int32_t ghostHigh)
+{
+    if (!s || !devMap) BFD_FAIL(-1, "bfd_set_material_map_device: null argument");
+    if (ghostLow < 0 || ghostLow > 2 || ghostHigh < 0 || ghostHigh > 2) BFD_FAIL(-2, "ghost plane counts must be 0..2");
+    if (s1 < 0 || s2 < 0 || s3 < 0) BFD_FAIL(-2, "negative strides are not supported");
+    BFD_REFUSE_MID_STEP("bfd_set_material_map_device");
+    const bfd_dev &d = s->d;
+    const uint32_t *base = devMap - (int64_t)ghostLow * s3;
+    const int nkSpan = d.nk + ghostLow + ghostHigh;
+    BFD_HIP(hipSetDevice(s->cfg.device));
+    if (!device_span_of(s, base, span_elems(d.N1, d.N2, nkSpan, s1, s2, s3)))
+        BFD_FAIL(-1, "bfd_set_material_map_device: devMap is not device memory of the sim's device that holds the whole view");
+    { const int rc = flush_pending(s); if (rc) return rc; }
+    return material_map_from_device(s, "bfd_set_material_map_device", base, s1, s2, s3, ghostLow, nkSpan);      // read in place
+}
+
+// mask (device memory, or null with clear) into the reflector bit of the ids
+static int reflector_from_device(bfd_sim *s, const uint32_t *devMask, int64_t s1, int64_t s2, int64_t s3)
+{
+    const bfd_dev &d = s->d;
+    hipLaunchKernelGGL(or_reflector, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, devMask, (long)s1, (long)s2, (long)s3,
+                       s->matBase + 2 * (size_t)d.plane, d.N1, d.N2, d.nk, devMask ? 0 : 1);
+    BFD_HIP(hipStreamSynchronize(s->stream));
+    invalidate_lists(s);      // reflector cells end the UNI class of their tiles
     return 0;
 }
 
@@ -512,11 +568,21 @@ int bfd_set_reflector(bfd_sim *s, const uint32_t *mask, int64_t s1, int64_t s2, 
         BFD_HIP(tmp.alloc(span));
         BFD_HIP(hipMemcpyAsync(tmp, mask, span * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     }
-    hipLaunchKernelGGL(or_reflector, dim3(grid_for((long)s->nloc)), dim3(256), 0, s->stream, tmp.p, (long)s1, (long)s2, (long)s3,
-                       s->matBase + 2 * (size_t)d.plane, d.N1, d.N2, d.nk, mask ? 0 : 1);
-    BFD_HIP(hipStreamSynchronize(s->stream));
-    invalidate_lists(s);      // reflector cells end the UNI class of their tiles
-    return 0;
+    return reflector_from_device(s, tmp, s1, s2, s3);
+}
+
+int bfd_set_reflector_device(bfd_sim *s, const uint32_t *devMask, int64_t s1, int64_t s2, int64_t s3)
+{
+    if (!s) BFD_FAIL(-1, "bfd_set_reflector_device: null sim");
+    if (devMask && (s1 < 0 || s2 < 0 || s3 < 0)) BFD_FAIL(-2, "negative strides are not supported");
+    if (!s->haveMap) BFD_FAIL(-6, "bfd_set_reflector_device: set the material map first");
+    BFD_REFUSE_MID_STEP("bfd_set_reflector_device");
+    const bfd_dev &d = s->d;
+    BFD_HIP(hipSetDevice(s->cfg.device));
+    if (devMask && !device_span_of(s, devMask, span_elems(d.N1, d.N2, d.nk, s1, s2, s3)))
+        BFD_FAIL(-1, "bfd_set_reflector_device: devMask is not device memory of the sim's device that holds the whole view");
+    { const int rc = flush_pending(s); if (rc) return rc; }
+    return reflector_from_device(s, devMask, s1, s2, s3);      // read in place
 }
 
 }  // extern "C"

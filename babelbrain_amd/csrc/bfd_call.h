@@ -1,7 +1,7 @@
-// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip, bfd_bonerim.hip, bfd_thermal.hip and bfd_thermal_study.hip (and by no other
+// The host side of a Step-1 device call, shared by bfd_median.hip, bfd_morphology.hip, bfd_resample.hip, bfd_voxelize.hip, bfd_distance.hip, bfd_tissue.hip, bfd_domain.hip, bfd_pseudoct.hip, bfd_bonerim.hip, bfd_thermal.hip, bfd_thermal_study.hip and bfd_acoustic.hip (and by no other
 // source: the solver's translation units do not see this file). Host code only.
 //
-// The contract of the twenty-seven entries (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
+// The contract of the stand-alone device calls (bfd_median_filter3d, bfd_binary_morphology3d, bfd_label3d, bfd_affine_transform3d, bfd_spline_filter3d,
 // bfd_voxelize_mesh, bfd_voxel_points, bfd_map_values3d, bfd_distance_transform_edt3d, bfd_gaussian_filter3d, bfd_voxel_scatter3d,
 // bfd_voxelize_scatter3d, bfd_paint_components3d, bfd_quantize_values3d, bfd_clear_beyond_bone3d,
 // bfd_label_survey3d, bfd_assemble_material_map3d, bfd_sdr_rays3d, bfd_integer_histogram3d, bfd_order_statistics3d, bfd_uniform_histogram3d,

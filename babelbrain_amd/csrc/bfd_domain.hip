@@ -21,6 +21,7 @@
 #include "bfd_internal.h"
 #include "bfd_call.h"
 #include "bfd_domain_core.h"
+#include "bfd_domain_stages.h"
 
 namespace {
 
@@ -334,18 +335,98 @@ static bool box_inside(const int64_t *lo, const int64_t *size, const int64_t *M)
 
 }  // namespace
 
-extern "C" int bfd_label_survey3d(int device, const uint8_t *labels, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo, const int64_t *hi, int flipK,
-                                  int64_t *hist, int64_t *bounds, int64_t *focal, float *kernelMs)
+// ---------------------------------------------------------------- the stages (bfd_domain_stages.h) ----------------------------------------------------------------
+
+hipError_t bfd_stage_label_survey(const uint8_t *dLabels, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo, const int64_t *hi, int flipK,
+                                  unsigned long long *dHist, int *dBnd, unsigned *dFirst)
 {
-    static const char *who = "bfd_label_survey3d";
-    // every argument error is reported before a device is looked for
-    if (!labels || !lo || !hi || !hist || !bounds || !focal) BFD_FAIL(-1, std::string(who) + ": null argument");
+    survey_args a;
+    a.rows = M1 * M2; a.M2 = (int)M2; a.M3 = (int)M3;
+    a.lo0 = (int)lo[0]; a.hi0 = (int)hi[0]; a.lo1 = (int)lo[1]; a.hi1 = (int)hi[1]; a.lo2 = (int)lo[2]; a.hi2 = (int)hi[2];
+    a.flipK = flipK;
+    hipLaunchKernelGGL(label_survey, dim3(blocks_for(a.rows, WAVES, SWEEP_BLOCKS)), dim3(THREADS), 0, 0, dLabels, a, dHist, dBnd, dFirst);
+    return hipGetLastError();
+}
+
+void bfd_label_survey_finish(const unsigned long long *h, const int *bnd, unsigned first, int64_t *hist, int64_t *bounds, int64_t *focal)
+{
+    for (int q = 0; q < HIST; q++) hist[q] = (int64_t)h[q];
+    for (int q = 0; q < 6; q++) bounds[q] = bnd[1] < 0 ? -1 : bnd[q];
+    focal[0] = (int64_t)h[HIST];
+    focal[1] = first == 0xFFFFFFFFu ? -1 : (int64_t)first;
+}
+
+hipError_t bfd_stage_assemble_map(const uint8_t *dLabels, const void *dCt, int ctBytes, const uint8_t *dAir, int64_t M2, int64_t M3, const int64_t *N,
+                                  const int64_t *lo, const int64_t *size, const int64_t *padLo, int flipK, const uint32_t *dLut, uint32_t ctOffset, int64_t zWater,
+                                  int64_t nMaterials, const int64_t *focalIJ, uint32_t *dMap, uint32_t *dMapNoCT, uint32_t *dAirOut, unsigned long long *d64,
+                                  unsigned *d32)
+{
+    assemble_args a;
+    a.total = N[0] * N[1] * N[2];
+    a.M2 = (int)M2; a.M3 = (int)M3; a.N2 = (int)N[1]; a.N3 = (int)N[2];
+    for (int q = 0; q < 3; q++) { a.lo[q] = (int)lo[q]; a.size[q] = (int)size[q]; a.padLo[q] = (int)padLo[q]; }
+    a.flipK = flipK; a.focalI = (int)focalIJ[0]; a.focalJ = (int)focalIJ[1];
+    a.zWater = zWater; a.ctOffset = ctOffset; a.nMaterials = (uint32_t)nMaterials;
+    const unsigned blocks = blocks_for(a.total, THREADS, SWEEP_BLOCKS);
+    if (ctBytes == 2)
+        hipLaunchKernelGGL(assemble_map<uint16_t>, dim3(blocks), dim3(THREADS), 0, 0, dLabels, (const uint16_t *)dCt, dAir, dLut, a, dMap, dMapNoCT, dAirOut, d64, d32);
+    else
+        hipLaunchKernelGGL(assemble_map<uint32_t>, dim3(blocks), dim3(THREADS), 0, 0, dLabels, (const uint32_t *)dCt, dAir, dLut, a, dMap, dMapNoCT, dAirOut, d64, d32);
+    return hipGetLastError();
+}
+
+void bfd_assemble_finish(const unsigned long long *c64, const unsigned *c32, int64_t *stats)
+{
+    stats[0] = (int64_t)c64[0];
+    stats[1] = c64[0] ? (int64_t)c32[0] : -1;
+    stats[2] = c64[0] ? (int64_t)c32[1] : -1;
+    stats[3] = (int64_t)c64[1];
+    stats[4] = (int64_t)c32[2];
+    stats[5] = c64[1] ? (int64_t)c32[3] : -1;
+    stats[6] = c32[4] == 0x7FFFFFFFu ? -1 : (int64_t)c32[4];
+    stats[7] = (int64_t)c64[2];
+}
+
+int bfd_survey_arguments(const char *who, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo, const int64_t *hi, int flipK)
+{
     if (M1 < 0 || M2 < 0 || M3 < 0) BFD_FAIL(-1, std::string(who) + ": negative dimension");
     if (!volume_fits(M1, M2, M3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
     const int64_t M[3] = {M1, M2, M3};
     for (int q = 0; q < 3; q++)
         if (lo[q] < 0 || lo[q] > hi[q] || hi[q] > M[q]) BFD_FAIL(-1, std::string(who) + ": the box must satisfy 0 <= lo <= hi <= M on every axis");
     if (flipK != 0 && flipK != 1) BFD_FAIL(-1, std::string(who) + ": flipK must be 0 or 1");
+    return 0;
+}
+
+int bfd_assemble_arguments(const char *who, int64_t M1, int64_t M2, int64_t M3, bool haveCt, const int64_t *lo, const int64_t *size, const int64_t *padLo,
+                           const int64_t *padHi, int flipK, const uint32_t *lut, int64_t zWater, int64_t nMaterials, const int64_t *focalIJ, int64_t *N)
+{
+    const int64_t M[3] = {M1, M2, M3};
+    if (!box_inside(lo, size, M)) BFD_FAIL(-1, std::string(who) + ": the box must satisfy 0 <= lo and lo + size <= M on every axis");
+    const int64_t LIMIT = (int64_t)1 << 31;
+    for (int q = 0; q < 3; q++) {
+        if (padLo[q] < 0 || padHi[q] < 0 || padLo[q] >= LIMIT || padHi[q] >= LIMIT) BFD_FAIL(-1, std::string(who) + ": the padding must be 0 .. 2^31 - 1");
+        N[q] = size[q] + padLo[q] + padHi[q];
+    }
+    if (!volume_fits(N[0], N[1], N[2])) BFD_FAIL(-1, std::string(who) + ": the map has 2^31 voxels or more (limit: fewer than 2^31)");
+    if (flipK != 0 && flipK != 1) BFD_FAIL(-1, std::string(who) + ": flipK must be 0 or 1");
+    if (!haveCt)
+        for (int q = 0; q < HIST; q++)
+            if (lut[q] & DM_LUT_BONE) BFD_FAIL(-1, std::string(who) + ": the lut marks a label as bone and there is no ct");
+    if (zWater < -1) BFD_FAIL(-1, std::string(who) + ": zWater must be -1 or a plane index");
+    if (nMaterials < 0 || nMaterials > 0xFFFFFFFFll) BFD_FAIL(-1, std::string(who) + ": nMaterials must be 0 .. 2^32 - 1");
+    if (N[0] * N[1] * N[2] && (focalIJ[0] < 0 || focalIJ[0] >= N[0] || focalIJ[1] < 0 || focalIJ[1] >= N[1]))
+        BFD_FAIL(-1, std::string(who) + ": focalIJ must be a column of the map");
+    return 0;
+}
+
+extern "C" int bfd_label_survey3d(int device, const uint8_t *labels, int64_t M1, int64_t M2, int64_t M3, const int64_t *lo, const int64_t *hi, int flipK,
+                                  int64_t *hist, int64_t *bounds, int64_t *focal, float *kernelMs)
+{
+    static const char *who = "bfd_label_survey3d";
+    // every argument error is reported before a device is looked for
+    if (!labels || !lo || !hi || !hist || !bounds || !focal) BFD_FAIL(-1, std::string(who) + ": null argument");
+    if (int rc = bfd_survey_arguments(who, M1, M2, M3, lo, hi, flipK)) return rc;
 
     if (int rc = pick_device(who, device)) return rc;
     if (kernelMs) *kernelMs = 0.f;
@@ -358,10 +439,6 @@ extern "C" int bfd_label_survey3d(int device, const uint8_t *labels, int64_t M1,
     }
 
     const size_t np = (n + 3) / 4 * 4;                // whole words: a row's last word may reach past the volume's last voxel
-    survey_args a;
-    a.rows = M1 * M2; a.M2 = (int)M2; a.M3 = (int)M3;
-    a.lo0 = (int)lo[0]; a.hi0 = (int)hi[0]; a.lo1 = (int)lo[1]; a.hi1 = (int)hi[1]; a.lo2 = (int)lo[2]; a.hi2 = (int)hi[2];
-    a.flipK = flipK;
     DevTemp<uint8_t> din;
     DevTemp<unsigned long long> dhist;
     DevTemp<int> dbnd;
@@ -381,18 +458,14 @@ extern "C" int bfd_label_survey3d(int device, const uint8_t *labels, int64_t M1,
     BFD_STEP(hipMemcpy(dfirst, &first, sizeof first, hipMemcpyHostToDevice));
     BFD_STEP(ev.create());
     BFD_STEP(ev.record(0));
-    hipLaunchKernelGGL(label_survey, dim3(blocks_for(a.rows, WAVES, SWEEP_BLOCKS)), dim3(THREADS), 0, 0, din.p, a, dhist.p, dbnd.p, dfirst.p);
-    BFD_STEP(hipGetLastError());
+    BFD_STEP(bfd_stage_label_survey(din, M1, M2, M3, lo, hi, flipK, dhist, dbnd, dfirst));
     BFD_STEP(ev.record(1));
     BFD_STEP(ev.sync(1));
     BFD_STEP(ev.elapsed(kernelMs, 0, 1));
     BFD_STEP(hipMemcpy(h, dhist, sizeof h, hipMemcpyDeviceToHost));
     BFD_STEP(hipMemcpy(bnd, dbnd, sizeof bnd, hipMemcpyDeviceToHost));
     BFD_STEP(hipMemcpy(&first, dfirst, sizeof first, hipMemcpyDeviceToHost));
-    for (int q = 0; q < HIST; q++) hist[q] = (int64_t)h[q];
-    for (int q = 0; q < 6; q++) bounds[q] = bnd[1] < 0 ? -1 : bnd[q];
-    focal[0] = (int64_t)h[HIST];
-    focal[1] = first == 0xFFFFFFFFu ? -1 : (int64_t)first;
+    bfd_label_survey_finish(h, bnd, first, hist, bounds, focal);
     return 0;
 }
 
@@ -408,24 +481,9 @@ extern "C" int bfd_assemble_material_map3d(int device, const uint8_t *labels, co
     if (!volume_fits(M1, M2, M3)) BFD_FAIL(-1, std::string(who) + ": the volume has 2^31 voxels or more (limit: fewer than 2^31)");
     if ((ctBytes != 0 && ctBytes != 2 && ctBytes != 4) || (ctBytes == 0) != (ct == nullptr))
         BFD_FAIL(-1, std::string(who) + ": ctBytes must be 0 with a null ct, or 2 or 4 with a ct");
-    const int64_t M[3] = {M1, M2, M3};
-    if (!box_inside(lo, size, M)) BFD_FAIL(-1, std::string(who) + ": the box must satisfy 0 <= lo and lo + size <= M on every axis");
-    const int64_t LIMIT = (int64_t)1 << 31;
     int64_t N[3];
-    for (int q = 0; q < 3; q++) {
-        if (padLo[q] < 0 || padHi[q] < 0 || padLo[q] >= LIMIT || padHi[q] >= LIMIT) BFD_FAIL(-1, std::string(who) + ": the padding must be 0 .. 2^31 - 1");
-        N[q] = size[q] + padLo[q] + padHi[q];
-    }
-    if (!volume_fits(N[0], N[1], N[2])) BFD_FAIL(-1, std::string(who) + ": the map has 2^31 voxels or more (limit: fewer than 2^31)");
-    if (flipK != 0 && flipK != 1) BFD_FAIL(-1, std::string(who) + ": flipK must be 0 or 1");
-    if (!ct)
-        for (int q = 0; q < HIST; q++)
-            if (lut[q] & DM_LUT_BONE) BFD_FAIL(-1, std::string(who) + ": the lut marks a label as bone and there is no ct");
-    if (zWater < -1) BFD_FAIL(-1, std::string(who) + ": zWater must be -1 or a plane index");
-    if (nMaterials < 0 || nMaterials > 0xFFFFFFFFll) BFD_FAIL(-1, std::string(who) + ": nMaterials must be 0 .. 2^32 - 1");
+    if (int rc = bfd_assemble_arguments(who, M1, M2, M3, ct != nullptr, lo, size, padLo, padHi, flipK, lut, zWater, nMaterials, focalIJ, N)) return rc;
     const size_t n = (size_t)(M1 * M2 * M3), nOut = (size_t)(N[0] * N[1] * N[2]);
-    if (nOut && (focalIJ[0] < 0 || focalIJ[0] >= N[0] || focalIJ[1] < 0 || focalIJ[1] >= N[1]))
-        BFD_FAIL(-1, std::string(who) + ": focalIJ must be a column of the map");
     if (nOut) {
         const void *outs[3] = {map, mapNoCT, airOut};
         const void *ins[3] = {labels, ct, air};
@@ -445,12 +503,6 @@ extern "C" int bfd_assemble_material_map3d(int device, const uint8_t *labels, co
         return 0;
     }
 
-    assemble_args a;
-    a.total = (int64_t)nOut;
-    a.M2 = (int)M2; a.M3 = (int)M3; a.N2 = (int)N[1]; a.N3 = (int)N[2];
-    for (int q = 0; q < 3; q++) { a.lo[q] = (int)lo[q]; a.size[q] = (int)size[q]; a.padLo[q] = (int)padLo[q]; }
-    a.flipK = flipK; a.focalI = (int)focalIJ[0]; a.focalJ = (int)focalIJ[1];
-    a.zWater = zWater; a.ctOffset = ctOffset; a.nMaterials = (uint32_t)nMaterials;
     DevTemp<uint8_t> dlab, dct, dair;
     DevTemp<uint32_t> dlut, dmap, dno, dairOut;
     DevTemp<unsigned long long> d64;
@@ -476,15 +528,9 @@ extern "C" int bfd_assemble_material_map3d(int device, const uint8_t *labels, co
     BFD_STEP(hipMemcpy(d64, c64, sizeof c64, hipMemcpyHostToDevice));
     BFD_STEP(hipMemcpy(d32, c32, sizeof c32, hipMemcpyHostToDevice));
     BFD_STEP(ev.create());
-    const unsigned blocks = blocks_for(a.total, THREADS, SWEEP_BLOCKS);
     BFD_STEP(ev.record(0));
-    if (ctBytes == 2)
-        hipLaunchKernelGGL(assemble_map<uint16_t>, dim3(blocks), dim3(THREADS), 0, 0, dlab.p, (const uint16_t *)dct.p, dair.p, dlut.p, a, dmap.p, dno.p, dairOut.p,
-                           d64.p, d32.p);
-    else
-        hipLaunchKernelGGL(assemble_map<uint32_t>, dim3(blocks), dim3(THREADS), 0, 0, dlab.p, (const uint32_t *)dct.p, dair.p, dlut.p, a, dmap.p, dno.p, dairOut.p,
-                           d64.p, d32.p);
-    BFD_STEP(hipGetLastError());
+    BFD_STEP(bfd_stage_assemble_map(dlab, dct, ctBytes, dair, M2, M3, N, lo, size, padLo, flipK, dlut, ctOffset, zWater, nMaterials, focalIJ, dmap, dno, dairOut,
+                                    d64, d32));
     BFD_STEP(ev.record(1));
     BFD_STEP(ev.sync(1));
     BFD_STEP(ev.elapsed(kernelMs, 0, 1));
@@ -493,14 +539,7 @@ extern "C" int bfd_assemble_material_map3d(int device, const uint8_t *labels, co
     BFD_STEP(hipMemcpy(map, dmap, 4 * nOut, hipMemcpyDeviceToHost));
     if (mapNoCT) BFD_STEP(hipMemcpy(mapNoCT, dno, 4 * nOut, hipMemcpyDeviceToHost));
     if (airOut) BFD_STEP(hipMemcpy(airOut, dairOut, 4 * nOut, hipMemcpyDeviceToHost));
-    stats[0] = (int64_t)c64[0];
-    stats[1] = c64[0] ? (int64_t)c32[0] : -1;
-    stats[2] = c64[0] ? (int64_t)c32[1] : -1;
-    stats[3] = (int64_t)c64[1];
-    stats[4] = (int64_t)c32[2];
-    stats[5] = c64[1] ? (int64_t)c32[3] : -1;
-    stats[6] = c32[4] == 0x7FFFFFFFu ? -1 : (int64_t)c32[4];
-    stats[7] = (int64_t)c64[2];
+    bfd_assemble_finish(c64, c32, stats);
     return 0;
 }
 

@@ -481,6 +481,39 @@ int bfd_clear_outputs(bfd_sim *s)
     return 0;
 }
 
+// A new sensor set of `count` voxels: what the old one held is released; the index list (unfilled), the series block or the running DFT sums and
+// peaks and the DFT bin are set up; the set counts as a list until the caller says it is a box. Shared by bfd_set_sensor_map and bfd_set_sensor_box
+static int sensor_storage(bfd_sim *s, int count)
+{
+    s->nSensors = count;
+    dev_release(s, &s->sensLin); dev_release(s, &s->sensOut); dev_release(s, &s->dftAcc); dev_release(s, &s->dftPk);
+    dev_release(s, &s->sensEnt); s->sensEntValid = false;
+    s->sensIsBox = false;
+    int rc = dev_alloc(s, &s->sensLin, (size_t)count, false);
+    if (!rc && s->nSelS && s->nTs > 0) {
+        if (s->cfg.sensorMode == 0) rc = dev_alloc(s, &s->sensOut, (size_t)s->nSelS * s->nTs * (size_t)count);
+        else {
+            rc = dev_alloc(s, &s->dftAcc, 2 * (size_t)s->nSelS * (size_t)count);
+            if (!rc) rc = dev_alloc(s, &s->dftPk, (size_t)s->nSelS * (size_t)std::max(count, 1), false);
+            if (!rc && count > 0) hipLaunchKernelGGL(fill_float, dim3(grid_for((long)s->nSelS * count)), dim3(256), 0, s->stream, s->dftPk, (long)s->nSelS * count, -INFINITY);
+            s->dftBin = dft_bin(s->nTs, s->cfg.dt * s->cfg.sensorSub, s->cfg.freq);
+        }
+    }
+    return rc;
+}
+// BFD_SENSOR_BOX=0 keeps the index list in use for the captures of a dense box
+static bool sensor_box_form_allowed()
+{
+    const char *ev = getenv("BFD_SENSOR_BOX");
+    return !ev || atoi(ev) != 0;
+}
+// the index list of a dense box, in the ascending x-fastest order bfd_set_sensor_map's select gives
+__global__ void box_sensor_indices(bfd_dev d, SensorBox B, long n, uint32_t *__restrict__ lin)
+{
+    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (long)gridDim.x * blockDim.x)
+        lin[s] = (uint32_t)sensor_cell(d, nullptr, B, s);
+}
+
 extern "C" {
 
 int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3, int64_t *nSensors)
@@ -508,24 +541,10 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
     const unsigned init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};      // both outlive the stream sync below
     unsigned mm[6] = {0, 0, 0, 0, 0, 0}; bool boxTried = false;
     if (e == hipSuccess) {
-        s->nSensors = count;
-        dev_release(s, &s->sensLin); dev_release(s, &s->sensOut); dev_release(s, &s->dftAcc); dev_release(s, &s->dftPk);
-        dev_release(s, &s->sensEnt); s->sensEntValid = false;
-        rc = dev_alloc(s, &s->sensLin, (size_t)count, false);
+        rc = sensor_storage(s, count);
         if (!rc && count) e = hipMemcpyAsync(s->sensLin, sel, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream);
-        if (!rc && s->nSelS && s->nTs > 0) {
-            if (s->cfg.sensorMode == 0) rc = dev_alloc(s, &s->sensOut, (size_t)s->nSelS * s->nTs * (size_t)count);
-            else {
-                rc = dev_alloc(s, &s->dftAcc, 2 * (size_t)s->nSelS * (size_t)count);
-                if (!rc) rc = dev_alloc(s, &s->dftPk, (size_t)s->nSelS * (size_t)std::max(count, 1), false);
-                if (!rc && count > 0) hipLaunchKernelGGL(fill_float, dim3(grid_for((long)s->nSelS * count)), dim3(256), 0, s->stream, s->dftPk, (long)s->nSelS * count, -INFINITY);
-                s->dftBin = dft_bin(s->nTs, s->cfg.dt * s->cfg.sensorSub, s->cfg.freq);
-            }
-        }
-        // a dense box of voxels? (count == volume of the bounding box: every voxel of the box is a sensor); BFD_SENSOR_BOX=0 keeps the index list in use
-        s->sensIsBox = false;
-        bool tryBox = count > 0;
-        if (const char *ev = getenv("BFD_SENSOR_BOX")) tryBox = tryBox && atoi(ev) != 0;
+        // a dense box of voxels? (count == volume of the bounding box: every voxel of the box is a sensor)
+        const bool tryBox = count > 0 && sensor_box_form_allowed();
         if (!rc && e == hipSuccess && tryBox) {
             unsigned *dbounds = (unsigned *)dcount.p;
             e = hipMemcpyAsync(dbounds, init, sizeof init, hipMemcpyHostToDevice, s->stream);
@@ -546,6 +565,32 @@ int bfd_set_sensor_map(bfd_sim *s, const uint32_t *map, int64_t s1, int64_t s2, 
     }
     if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_set_sensor_map: ") + hipGetErrorString(e));
     if (rc) return rc;
+    if (nSensors) *nSensors = s->nSensors;
+    return 0;
+}
+
+int bfd_set_sensor_box(bfd_sim *s, const int32_t *lo, const int32_t *size, int64_t *nSensors)
+{
+    if (!s || !lo || !size) BFD_FAIL(-1, "bfd_set_sensor_box: null argument");
+    const bfd_dev &d = s->d;
+    const int dim[3] = {d.N1, d.N2, d.nk};
+    for (int a = 0; a < 3; a++) {
+        if (size[a] <= 0) BFD_FAIL(-1, "bfd_set_sensor_box: empty box");
+        if (lo[a] < 0 || lo[a] >= dim[a] || size[a] > dim[a] - lo[a]) BFD_FAIL(-1, "bfd_set_sensor_box: the box leaves the slab");
+    }
+    if (s->nloc > (size_t)0x7FFFFFFF) BFD_FAIL(-2, "bfd_set_sensor_box: slab too large for 32-bit sensor counts");
+    BFD_HIP(hipSetDevice(s->cfg.device));
+    { const int rc = flush_pending(s); if (rc) return rc; }
+    const long count = (long)size[0] * size[1] * size[2];
+    const int rc = sensor_storage(s, (int)count);
+    if (rc) return rc;
+    s->sensBox[0] = size[0]; s->sensBox[1] = size[1]; s->sensBox[2] = lo[0]; s->sensBox[3] = lo[1]; s->sensBox[4] = lo[2];
+    const SensorBox B = {(unsigned)size[0], (unsigned)size[0] * (unsigned)size[1], (unsigned)lo[0], (unsigned)lo[1], (unsigned)lo[2]};
+    hipLaunchKernelGGL(box_sensor_indices, dim3(grid_for(count)), dim3(256), 0, s->stream, d, B, count, s->sensLin);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) BFD_FAIL(-10, std::string("bfd_set_sensor_box: ") + hipGetErrorString(e));
+    s->sensIsBox = sensor_box_form_allowed();
     if (nSensors) *nSensors = s->nSensors;
     return 0;
 }

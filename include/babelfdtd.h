@@ -147,6 +147,23 @@ int bfd_set_sources_separable(bfd_sim *sim, int64_t nVox, const uint32_t *localI
 /* SensorMap slab (BASE:2346); returns the number of sensors of this slab in *nSensors */
 int bfd_set_sensor_map(bfd_sim *sim, const uint32_t *map, int64_t s1, int64_t s2, int64_t s3,
                        int64_t *nSensors);
+/* The three setters above for callers whose volumes are on the device already (ABI 7, additive).
+ * bfd_set_material_map_device / bfd_set_reflector_device: the same view (element strides >= 0, ghost planes), the same meaning, return codes
+ * (-2 ghost counts or strides, -6 mid-step or no map yet, -5 an id >= nMat) and side effects as the host forms (a new map clears the reflector;
+ * the run lists are rebuilt), but devMap / devMask is DEVICE memory of the sim's own device: the layout kernel reads it in place, no temporary
+ * is allocated and nothing is copied. The pointer is looked up first (hipPointerGetAttributes, hipMemGetAddressRange): a host pointer, managed
+ * memory, memory of another device, or a view that does not lie inside one allocation is refused with -1 and the sim is unchanged. The work that
+ * wrote the volume must have finished: the sim's stream waits for no other stream. The call returns when the kernel has read the volume.
+ * devMask = NULL clears the reflector, as in the host form. */
+int bfd_set_material_map_device(bfd_sim *sim, const uint32_t *devMap, int64_t s1, int64_t s2, int64_t s3,
+                                int32_t ghostLow, int32_t ghostHigh);
+int bfd_set_reflector_device(bfd_sim *sim, const uint32_t *devMask, int64_t s1, int64_t s2, int64_t s3);
+/* The sensors of a dense box of voxels without a volume: voxels lo[a] <= index < lo[a] + size[a] of the slab's (N1, N2, nk) volume (k local to
+ * the slab). The index list is written on the device in ascending x-fastest order; afterwards the sim is in the state bfd_set_sensor_map reaches
+ * from a volume that is 1 inside the box and 0 outside: same count, same bfd_get_sensor_index, same DFT bin, series block or DFT sums, and
+ * the captures take the box form (BFD_SENSOR_BOX=0 keeps the list form, as there). -1: sim, lo or size NULL, an empty box (a size <= 0), a box
+ * that leaves the slab; nothing is changed then. nSensors may be NULL. */
+int bfd_set_sensor_box(bfd_sim *sim, const int32_t *lo /*[3]*/, const int32_t *size /*[3]*/, int64_t *nSensors);
 
 /* time stepping. bfd_run = nSteps x (stress half-step, velocity half-step, accumulate, sensors)
  * for a slab without neighbours. With neighbours the caller alternates:
@@ -262,6 +279,34 @@ int bfd_get_sensor_dft(bfd_sim *sim, double freq, float *outReIm, float *outPeak
 /* the same transform for a host series [nSensors][nTs] (row-major), sampling period dtSensor */
 int bfd_dft_series(int32_t device, int64_t nSensors, int32_t nTs, const float *series, double dtSensor, double freq,
                    float *outReIm, float *outPeak);
+
+/* Result packing (ABI 7, additive): the Pressure results of a run with sensorMode 1 as the volumes the caller saves, formed on the device --
+ * what CalculatePhaseData's scatter (BASE:2503-2520), the dispersion scaling (BASE:2433-2456) and ReturnResults' zero / crop / paste / flip
+ * (BASE:2729-2885) make of them on the host. Coordinates are voxels of the slab's (N1, N2, nk) volume, k local to the slab.
+ *   kept region: lo[a] <= index < dim[a] - hi[a] (the Crop offsets; hi counts planes dropped at the high end)
+ *   output: numpy C order [O[0]][O[1]][O[2]]; the kept region lands at offset at[a], the rest is 0; with flipK = 1 the output is then
+ *           reversed along its last axis. O = kept size and at = 0 gives DataForSim; O = the mask's shape and at = the shrinks gives
+ *           paste_and_flip.
+ *   zero where the voxel's global k <= zSource, and (pComplex, pPeak) where the voxel is not a sensor.
+ *   applyScale = 0: no scaling at all. applyScale = 1, per voxel:
+ *     pAmp     = (float)((double)rms * ampScale), rms = the Pressure RMS map as bfd_get_map gives it; ampScale = Correction * sqrt(2) in float64
+ *     pComplex = re, im of bfd_get_sensor_dft, each times (float)correction in float32
+ *     pPeak    = the peak of bfd_get_sensor_dft times (float)correction in float32
+ *   (denormal operands and products are kept, as numpy on a CPU keeps them: these products are the one place where the library does not flush.)
+ * Each output may be NULL. pAmp needs the Pressure RMS map selected, pComplex / pPeak need sensorMode 1 with Pressure among the sensor maps
+ * (-2 otherwise). A sensor set that is a dense box (bfd_set_sensor_box, or a map recognised as one) is packed by index arithmetic; any other
+ * list by one zero fill and one lane per sensor; same values, no atomics, the same bytes in every run.
+ * -1, before the device is touched and in this order: sim or spec NULL; flipK or applyScale not 0 / 1; a scale that is not finite (with
+ * applyScale); lo or hi negative or an empty kept region; O not positive or beyond 2^31 - 1 voxels; at negative or the kept region not inside O.
+ * kernelMs (may be NULL): the kernels alone. */
+typedef struct bfd_pack_spec {
+    int32_t lo[3], hi[3];
+    int32_t zSource;
+    int32_t O[3], at[3];
+    int32_t flipK, applyScale;
+    double ampScale, correction;
+} bfd_pack_spec;
+int bfd_pack_results(bfd_sim *sim, const bfd_pack_spec *spec, float *pAmp, float *pComplex /*[..][2]*/, float *pPeak, float *kernelMs);
 /* one accumulated volume of this slab into a strided (N1,N2,nk) float32 view */
 int bfd_get_map(bfd_sim *sim, int32_t kind, int32_t map, float *out, int64_t s1, int64_t s2, int64_t s3);
 /* raw state array a (0..14: Vx Vy Vz Sxx Syy Szz Sxy Sxz Syz Rxx Ryy Rzz Rxy Rxz Ryz), for tests.
@@ -1031,6 +1076,47 @@ int bfd_thermal_get_plane(bfd_thermal handle, int which, int64_t j, void *out);
 
 /* Bytes the study has copied host -> device and device -> host since its creation, counted where each copy is issued */
 int bfd_thermal_traffic(bfd_thermal handle, int64_t *bytesUp, int64_t *bytesDown);
+
+/* Acoustic study (ABI 7, additive): the volumes of one Step-2 calculation held on one device from their upload to the results the caller asks for.
+ * Every stage is the launch sequence of the public entry it names, in device-pointer form, so its results equal that entry's element by element:
+ *   bfd_acoustic_set_volumes  labels (uint8 [M1][M2][M3], as stored), the ct index volume (ctBytes 2 or 4) and the air mask (uint8): one upload each
+ *   bfd_acoustic_survey       bfd_label_survey3d on the resident labels
+ *   bfd_acoustic_assemble     bfd_assemble_material_map3d from `lo` on, without output pointers: map, mapNoCT (with a ct) and airOut (with an air
+ *                             mask) stay resident, stats [8] comes back. waterOnly = 1: the map is zeros, formed on the device, and nothing else exists
+ *   bfd_acoustic_attach       bfd_set_material_map_device of the resident map on `sim`, then bfd_set_reflector_device where airOut exists
+ *   bfd_acoustic_pack         bfd_pack_results of `sim` (all three outputs) into resident volumes of slot 0 (tissue), 1 (water) or 2 (refocus), and
+ *                             the resident maps cropped, pasted and flipped the same way (not zeroed at the source plane), the air mask as uint8
+ *   bfd_acoustic_get          one packed volume of a slot, or (slot ignored) a whole assembled map, to the host
+ *   bfd_acoustic_traffic      bytes the study has copied host -> device and device -> host since its creation, counted where each copy is issued
+ * Contract (csrc/bfd_call.h): argument errors are -1 with a text, before a device is looked for, in the order of the entry each stage names (then
+ * what the stage adds: waterOnly, slot, which); -3: no device or a bad ordinal; -6: a stage was asked for before the stage it needs, which the text
+ * names (set_volumes before survey and assemble, assemble before attach, pack and the whole maps, a run before pack, pack before get), or a volume
+ * the study does not hold (no ct, no air mask, a water-only map); -10: a HIP error. Outputs are untouched on a refusal. The sim of attach and pack is
+ * a whole domain (k0 = 0) of the assembled map's shape on the study's device, else -1; the shape is compared with the assembled map, so this -1
+ * alone follows the -6 of a missing assembly (and precedes the -6 of a missing run). */
+typedef struct bfd_acoustic_s *bfd_acoustic;
+enum {
+    BFD_ACOUSTIC_P_AMP = 0,             /* float32 [O]: pAmp of bfd_pack_results */
+    BFD_ACOUSTIC_P_COMPLEX = 1,         /* float32 [O][2] */
+    BFD_ACOUSTIC_PEAK = 2,              /* float32 [O] */
+    BFD_ACOUSTIC_MATERIAL_MAP = 3,      /* uint32 [O]: the map the sim ran on */
+    BFD_ACOUSTIC_MATERIAL_MAP_NOCT = 4, /* uint32 [O]: the raw labels of the domain (with a ct) */
+    BFD_ACOUSTIC_AIR_MASK = 5,          /* uint8 [O] (with an air mask) */
+    BFD_ACOUSTIC_FULL_MAP = 6,          /* uint32 [N1][N2][N3]: map, mapNoCT, airOut as bfd_assemble_material_map3d writes them */
+    BFD_ACOUSTIC_FULL_MAP_NOCT = 7,
+    BFD_ACOUSTIC_FULL_AIR = 8
+};
+int bfd_acoustic_create(int device, int64_t M1, int64_t M2, int64_t M3, int ctBytes, int hasAir, bfd_acoustic *handle);
+void bfd_acoustic_destroy(bfd_acoustic handle);           /* NULL is accepted */
+int bfd_acoustic_set_volumes(bfd_acoustic handle, const uint8_t *labels, const void *ct, const uint8_t *air);
+int bfd_acoustic_survey(bfd_acoustic handle, const int64_t *lo, const int64_t *hi, int flipK, int64_t *hist, int64_t *bounds, int64_t *focal);
+int bfd_acoustic_assemble(bfd_acoustic handle, const int64_t *lo, const int64_t *size, const int64_t *padLo, const int64_t *padHi, int flipK,
+                          const uint32_t *lut, uint32_t ctOffset, int64_t zWater, int64_t nMaterials, const int64_t *focalIJ, int waterOnly,
+                          int64_t *stats);
+int bfd_acoustic_attach(bfd_acoustic handle, bfd_sim *sim);
+int bfd_acoustic_pack(bfd_acoustic handle, bfd_sim *sim, const bfd_pack_spec *spec, int slot);
+int bfd_acoustic_get(bfd_acoustic handle, int which, int slot, void *out);
+int bfd_acoustic_traffic(bfd_acoustic handle, int64_t *bytesUp, int64_t *bytesDown);
 
 #ifdef __cplusplus
 }
