@@ -288,15 +288,21 @@ def field_schedule(nStepsOnOffList, TotalDurationSteps):
     return np.ascontiguousarray(np.tile(cycle, reps)[:int(TotalDurationSteps)], np.int32)
 
 
-def bhte_pass_plan(sched, nFactorMonitoring=1, monitored_plane=True, steps_heating=4, steps_cooling=4):
-    """The passes bfd_bhte_run_* cuts a schedule into (the rule of bhte_run_core, restated for byte accounting): S = 4 steps per pass wherever the next S steps carry the same field; else two steps, else one. Returns [(first step, length, heating)]."""
+def bhte_pass_plan(sched, nFactorMonitoring=1, monitored_plane=True, steps_heating=4, steps_cooling=4, capture_steps=(), fuse=True):
+    """The passes bfd_bhte_run_* cuts a schedule into: bhte_plan_passes of csrc/bfd_bhte_plan_core.h restated for byte accounting (tests/test_bhte_plan_host.py holds
+    the two together, pass for pass). S steps per pass (4 by default) wherever the next S steps carry the same field and no capture boundary (capture_steps,
+    ascending) lies strictly inside; else two steps where none lies between them, else one; fuse=False: every step on its own. Every pass kind is taken to fit
+    the grid (fewer than 2^31 workgroups). Returns [(first step, length, heating)]."""
     sched = [int(v) for v in sched]
-    fm = max(int(nFactorMonitoring), 1)
-    out, s, n = [], 0, len(sched)
+    caps = [int(c) for c in capture_steps]
+    out, s, n, nxt = [], 0, len(sched), 0
     while s < n:
-        S = steps_heating if sched[s] >= 0 else steps_cooling
-        ok = S >= 3 and s + S <= n and all(sched[s + j] == sched[s] for j in range(1, S))
-        L = S if ok else (2 if s + 1 < n else 1)
+        while nxt < len(caps) and caps[nxt] == s:
+            nxt += 1
+        free = lambda L: nxt >= len(caps) or s + L <= caps[nxt]
+        S = 2 if not fuse else steps_heating if sched[s] >= 0 else steps_cooling
+        ok = 3 <= S <= 4 and s + S <= n and free(S) and all(sched[s + j] == sched[s] for j in range(1, S))
+        L = S if ok else (2 if fuse and s + 1 < n and free(2) else 1)
         out.append((s, L, sched[s] >= 0 or (L == 2 and sched[s + 1] >= 0)))
         s += L
     return out

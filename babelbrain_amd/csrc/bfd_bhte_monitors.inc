@@ -1,9 +1,9 @@
-// Monitor kernels of bfd_bhte.hip that are written ONCE over the material id type and compiled twice: bfd_bhte.hip includes this file inside its
+// Monitor kernels of bfd_bhte_kernels.hip that are written ONCE over the material id type and compiled twice: bfd_bhte_kernels.hip includes this file inside its
 // anonymous namespace with BHTE_ID = unsigned char and again with BHTE_ID = uint16_t, which gives two overloads of each kernel. The other kernels
-// of bfd_bhte.hip get their two overloads from a *_body template; these three do not, because inlined through a body their 8-bit machine code
+// of that file get their two overloads from a *_body template; these three do not, because inlined through a body their 8-bit machine code
 // came out in another instruction order than before (same instructions), and the 8-bit kernels are held to the code they had.
 #ifndef BHTE_ID
-#error "include from bfd_bhte.hip with BHTE_ID defined"
+#error "include from bfd_bhte_kernels.hip with BHTE_ID defined"
 #endif
 
 // Monitor points of the intermediate steps of an S-step pass: T(n + depth) at the listed voxels from T(n), depth 1 .. 3 -- the cube of side

@@ -5,7 +5,7 @@
                                                             remarks of one compiler together: without it parallel compilers tear each other's lines)
     scripts/isa_identity.py <parent tree>/babelbrain_amd/csrc <parent>.log <branch tree>/babelbrain_amd/csrc <branch>.log [new=old ...] [kernel:new=old ...]
 
-new=old (optional, e.g. bfd_outputs=bfd_api): kernels and resource records of object `new` of the second build are looked up under object `old`
+new=old (optional, e.g. bfd_outputs=bfd_api, bfd_bhte_kernels=bfd_bhte): kernels and resource records of object `new` of the second build are looked up under object `old`
 of the first (code that moved from one source file to another). An `old` that the Makefile no longer names (a source file that was split up) is read from the
 first build all the same.
 kernel:new=old (optional): in the kernel names of the second build the text `new` is replaced by `old` before the lookup (a kernel that lost a template
@@ -60,7 +60,8 @@ def kernels(obj, tmp):
 
 
 def owner(f):
-    """the source a remark belongs to: an include file of kernels counts for the source it is named after (bfd_bhte_monitors.inc -> bfd_bhte.hip)"""
+    """the source a remark belongs to: an include file of kernels counts for the source it is named after (bfd_bhte_monitors.inc -> bfd_bhte.hip; its kernels are
+    compiled into bfd_bhte_kernels.o, so compare that object with bfd_bhte_kernels=bfd_bhte, which puts both under one name)"""
     f = os.path.basename(f)
     if f.endswith('.inc'):
         f = max((s for s in SRC if f.startswith(s)), key=len) + '.hip'

@@ -1,7 +1,7 @@
 """The bio-heat solver's outputs against the numpy oracle, element by element: the step history of the oracle, the CEM43 dose in float64 from
 that history, and the bound a float32 dose of the device is held to, voxel by voxel.
 
-The device (bhte_dose_rate of csrc/bfd_bhte.hip) adds, after every step and in step order, fl(dtMin * v_exp_f32(-b (43 - T'))) to the float32
+The device (bhte_dose_rate of csrc/bfd_bhte_kernels.hip) adds, after every step and in step order, fl(dtMin * v_exp_f32(-b (43 - T'))) to the float32
 dose, dtMin = float32(dt/60), b = 1 where T' >= 43 and 2 otherwise. The temperature has the oracle's bits (the roundings of bhte_update are
 pinned), so the reference sums the same terms exactly:
 

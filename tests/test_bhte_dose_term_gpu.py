@@ -12,7 +12,7 @@ from tests import bhte_reference as BR
 pytestmark = pytest.mark.gpu
 
 N = (256, 256, 257)
-_ENV = ('BFD_BHTE_FUSE', 'BFD_BHTE_KERNEL', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN')
+_ENV = ('BFD_BHTE_FUSE', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN')
 
 
 @pytest.fixture(scope='module')
@@ -68,7 +68,7 @@ def test_one_term_at_every_temperature_and_the_fused_kernels_sum_it(dt, every_te
     want = ((r + r) + r) + r
     for name, nOn, env in (('four steps per pass, nothing heats', 0, {}), ('four steps per pass, a (zero) field heats', 4, {}),
                            ('three steps per pass and one', 0, dict(BFD_BHTE_STEPS='3')), ('three per pass, heating', 4, dict(BFD_BHTE_STEPS='3')),
-                           ('two steps per launch', 0, dict(BFD_BHTE_STEPS='2')), ('two per launch, round-3 kernel', 2, dict(BFD_BHTE_KERNEL='1'))):
+                           ('two steps per launch', 0, dict(BFD_BHTE_STEPS='2'))):
         D = run(4, nOn, **env)
         diff = D.view(np.uint32) != want.view(np.uint32)
         if diff.any():

@@ -152,7 +152,7 @@ def test_multiple_pressure_fields_schedule_and_oracle():
 
 def test_two_steps_per_launch_equal_one_step_per_launch(monkeypatch):
     """The default path takes two steps per launch (bhte_step2g: z-marching tiles of 64 x 24 cells with two rings, loads in
-    flight across the plane; BFD_BHTE_KERNEL=1: the round-3 kernel bhte_step2 on 64 x 26 tiles); the temperature, the dose and
+    flight across the plane); the temperature, the dose and
     every monitor must have the bits of the one-step kernel, on grids that do not fill the tiles, with odd step counts, with
     the field changing between the two fused steps, and with monitors on intermediate steps."""
     from babelbrain_amd import RayleighAndBHTE as R
@@ -165,17 +165,14 @@ def test_two_steps_per_launch_equal_one_step_per_launch(monkeypatch):
         mpm = np.zeros(N, np.uint32); mpm[1, 1, 1] = 1; mpm[N[0] // 2, N[1] // 2, N[2] // 2] = 2; mpm[N[0] - 1, N[1] - 2, 0] = 3
         T0 = (37.0 + 8.0 * rng.random(N)).astype(np.float32)                 # some cells above 43: both dose bases
         out = {}
-        for fuse, kernel in (('1', '0'), ('1', '1'), ('0', '0')):
+        for fuse in ('1', '0'):
             monkeypatch.setenv('BFD_BHTE_FUSE', fuse)
-            monkeypatch.setenv('BFD_BHTE_KERNEL', kernel)
             if zrun: monkeypatch.setenv('BFD_BHTE_ZRUN', zrun)
             else: monkeypatch.delenv('BFD_BHTE_ZRUN', raising=False)
-            out[fuse + kernel] = R.BHTEMultiplePressureFields(fields, mm, ml, 4e-4, nS, onoff, N[1] // 2, nFactorMonitoring=3, dt=0.02, initT0=T0, MonitoringPointsMap=mpm)
-        for k in ('10', '11'):
-            for a, b in zip(out[k], out['00']):
-                assert np.array_equal(a, b)
-        assert out['10'][0].max() > 44.0 and out['10'][1].max() > 0
-    monkeypatch.delenv('BFD_BHTE_KERNEL', raising=False)
+            out[fuse] = R.BHTEMultiplePressureFields(fields, mm, ml, 4e-4, nS, onoff, N[1] // 2, nFactorMonitoring=3, dt=0.02, initT0=T0, MonitoringPointsMap=mpm)
+        for a, b in zip(out['1'], out['0']):
+            assert np.array_equal(a, b)
+        assert out['1'][0].max() > 44.0 and out['1'][1].max() > 0
     # and the oracle, bit for bit on the temperature now that the roundings are pinned (the dose goes through exp2f against numpy's power)
     N = (70, 30, 35)
     mm = rng.integers(0, 5, N).astype(np.uint8)
@@ -199,7 +196,6 @@ def test_three_and_four_steps_per_pass_equal_one_step_per_launch(steps, monkeypa
     from babelbrain_amd import RayleighAndBHTE as R
     rng = np.random.default_rng(23)
     ml = _materials()
-    monkeypatch.delenv('BFD_BHTE_KERNEL', raising=False)
     cases = (((150, 61, 37), 40, [[9, 7], [5, 3]], None, 3, 30), ((64, 22, 16), 16, [[4, 4]], None, 1, 10), ((65, 23, 9), 13, [[7, 6]], '1', 4, 11),
              ((70, 41, 35), 27, [[12, 6], [3, 0]], '5', 10, -1), ((3, 3, 3), 9, [[4, 2]], None, 2, 1), ((131, 45, 20), 30, [[6, 4], [0, 5], [8, 2]], '32', 5, 22),
              ((129, 20, 50), 25, [[13, 12]], '64', 7, 0))
@@ -265,7 +261,7 @@ def test_monitors_against_the_oracle_at_every_sample_and_every_step(N, zrun, mon
         assert {L for _, L, _ in plan} == {1, 2, 4} and any(L == 4 and heat == (onoff[0][0] == 5) for _, L, heat in plan)
         h = None
         for env in ({}, dict(BFD_BHTE_FUSE='0')):
-            for k in ('BFD_BHTE_FUSE', 'BFD_BHTE_KERNEL', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN'):
+            for k in ('BFD_BHTE_FUSE', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN'):
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)

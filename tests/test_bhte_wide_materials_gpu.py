@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 N_SOFT, N_BONE = 6, 1024
 DX, DT = 4e-4, 0.02
-_ENV = ('BFD_BHTE_FUSE', 'BFD_BHTE_KERNEL', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN')
+_ENV = ('BFD_BHTE_FUSE', 'BFD_BHTE_STEPS', 'BFD_BHTE_ZRUN')
 
 
 def _ct_list(n_bone=N_BONE, init_varies=False):
@@ -81,8 +81,7 @@ def test_every_pass_length_has_the_bits_of_one_step_per_launch(case, monkeypatch
         return R.BHTEMultiplePressureFields(fields, mm, ml, DX, nS, onoff, sl, nFactorMonitoring=fm, dt=DT, initT0=T0, MonitoringPointsMap=mpm)
     one = run(BFD_BHTE_FUSE='0')
     assert one[0].max() > 44.0 and one[1].max() > 0 and one[4].shape == (len(np.unique(mpm)) - 1, nS)
-    variants = {'S=3': dict(BFD_BHTE_STEPS='3'), 'S=4': dict(BFD_BHTE_STEPS='4'), 'default': {}, 'two-step g': dict(BFD_BHTE_FUSE='1', BFD_BHTE_KERNEL='0', BFD_BHTE_STEPS='2'),
-                'two-step': dict(BFD_BHTE_FUSE='1', BFD_BHTE_KERNEL='1')}
+    variants = {'S=3': dict(BFD_BHTE_STEPS='3'), 'S=4': dict(BFD_BHTE_STEPS='4'), 'default': {}, 'two-step g': dict(BFD_BHTE_FUSE='1', BFD_BHTE_STEPS='2')}
     for name, env in variants.items():
         got = run(**env)
         for q, (a, b) in enumerate(zip(got, one)):
@@ -132,7 +131,7 @@ def test_relabelled_five_material_problem_has_the_bits_of_the_8_bit_run(monkeypa
     onoff = [[6, 4], [3, 2]]
     mpm = np.zeros(N, np.uint32); mpm[1, 1, 1] = 1; mpm[65, 22, 10] = 2; mpm[130, 43, 0] = 3; mpm[0, 44, 19] = 4
     T0 = (37.0 + 8.0 * rng.random(N)).astype(np.float32)
-    for env in ({}, dict(BFD_BHTE_STEPS='3'), dict(BFD_BHTE_STEPS='2'), dict(BFD_BHTE_KERNEL='1'), dict(BFD_BHTE_FUSE='0')):
+    for env in ({}, dict(BFD_BHTE_STEPS='3'), dict(BFD_BHTE_STEPS='2'), dict(BFD_BHTE_FUSE='0')):
         _clear(monkeypatch, **env)
         for init in (T0, None):                                           # None: from InitTemperature[material] (table_lookup)
             a = R.BHTEMultiplePressureFields(fields, mm5, ml5, DX, 31, onoff, 22, nFactorMonitoring=3, dt=DT, initT0=init, MonitoringPointsMap=mpm)
