@@ -145,125 +145,81 @@ class PropagationModel:
         if DT is None:
             DT = _engine.stable_dt(ml, Frequency, QfactorCorrection, SpatialStep, AlphaCFL, QCorrection)
         nt = n_steps(DurationSimulation, DT)
-        # device: explicit ordinal of the call, else the one this object was built with, else the first device whose
-        # name contains DefaultGPUDeviceName (the reference selects by name substring, BASE:2358, 918-925), else 0
+        if not ReturnSensorSeries and not ReturnSensorDFT:
+            raise ValueError('ReturnSensorSeries=False needs ReturnSensorDFT=True')
         devices = self._devices
         if DefaultGPUDeviceNumber is not None and not np.isscalar(DefaultGPUDeviceNumber):
             devices, DefaultGPUDeviceNumber = _device_list(DefaultGPUDeviceNumber), None
+        dims = (N1, N2, N3, ml.shape[0], SpatialStep, DT, Frequency, nt)
+        options = dict(NDelta=NDelta, reflectionLimit=ReflectionLimit, typeSource=TypeSource, sensorSub=SensorSubSampling,
+                       sensorStart=SensorStart, selRMSorPeak=SelRMSorPeak, selMapsRMS=SelMapsRMSPeakList,
+                       selMapsSensors=SelMapsSensorsList, qfactorCorrection=QfactorCorrection, kernelVariant=self._kernelVariant,
+                       sensorMode=1 if (ReturnSensorDFT and not ReturnSensorSeries) else 0)
+        # one engine, or a group: the same call on several devices, whole-domain arrays in, whole-domain results out (bfd_group_*)
+        solver = None
         if DefaultGPUDeviceNumber is None and self._device is None and devices is not None and len(devices) >= 1:
             devices = devices[:max(1, N3 // 4)]            # a slab owns at least the 2 + 2 planes its neighbours read
             if len(devices) > 1:
-                return self._run_group(devices, MaterialMap, ml, Frequency, SourceMap, PulseSource, SpatialStep, DT, nt, SensorMap,
-                                       Ox, Oy, Oz, NDelta, ReflectionLimit, QfactorCorrection, QCorrection, TypeSource, SelRMSorPeak,
-                                       SelMapsRMSPeakList, SelMapsSensorsList, SensorSubSampling, SensorStart, ReflectorMask, SILENT,
-                                       ReturnSensorDFT, ReturnSensorSeries)
+                solver = _engine.Group(devices, *dims, **options)
             DefaultGPUDeviceNumber = devices[0]
-        device = DefaultGPUDeviceNumber if DefaultGPUDeviceNumber is not None else self._device
-        if device is None:
-            device = 0
-            for d, name in _engine.list_devices() if DefaultGPUDeviceName else []:
-                if str(DefaultGPUDeviceName).lower() in name.lower():
-                    device = d
-                    break
-        eng = Engine(N1, N2, N3, ml.shape[0], SpatialStep, DT, Frequency, nt, NDelta=NDelta,
-                     reflectionLimit=ReflectionLimit, typeSource=TypeSource, sensorSub=SensorSubSampling,
-                     sensorStart=SensorStart, selRMSorPeak=SelRMSorPeak, selMapsRMS=SelMapsRMSPeakList,
-                     selMapsSensors=SelMapsSensorsList, qfactorCorrection=QfactorCorrection, device=device,
-                     kernelVariant=self._kernelVariant, sensorMode=1 if (ReturnSensorDFT and not ReturnSensorSeries) else 0)
-        if not ReturnSensorSeries and not ReturnSensorDFT:
-            eng.close()
-            raise ValueError('ReturnSensorSeries=False needs ReturnSensorDFT=True')
+        grouped = solver is not None
+        if not grouped:
+            # device: explicit ordinal of the call, else the one this object was built with, else the first device whose
+            # name contains DefaultGPUDeviceName (the reference selects by name substring, BASE:2358, 918-925), else 0
+            device = DefaultGPUDeviceNumber if DefaultGPUDeviceNumber is not None else self._device
+            if device is None:
+                device = 0
+                for d, name in _engine.list_devices() if DefaultGPUDeviceName else []:
+                    if str(DefaultGPUDeviceName).lower() in name.lower():
+                        device = d
+                        break
+            solver = Engine(*dims, device=device, **options)
         try:
-            eng.set_materials(ml, QCorrection)
-            eng.set_material_map(MaterialMap, 0, 0)
+            solver.set_materials(ml, QCorrection)
+            if grouped:
+                solver.set_material_map(MaterialMap)
+            else:
+                solver.set_material_map(MaterialMap, 0, 0)      # no ghost planes: the engine owns the whole domain
             if ReflectorMask is not None:
-                eng.set_reflector(ReflectorMask)
+                solver.set_reflector(ReflectorMask)
             lin, row, wx, wy, wz = compact_sources(np.asarray(SourceMap), Ox, Oy, Oz)
-            eng.set_sources(lin, row, wx, wy, wz, PulseSource)
-            eng.set_sensor_map(SensorMap)
-            eng.timing_begin(False)
-            eng.run(nt)
-            self.last_timing = eng.timing_end()
+            solver.set_sources(lin, row, wx, wy, wz, PulseSource)
+            solver.set_sensor_map(SensorMap)
+            solver.timing_begin()
+            solver.run(nt)
+            self.last_timing = solver.timing_end()
             self.last_timing['voxel_steps'] = float(N1) * N2 * N3 * nt
             Sensor = {'time': sensor_steps(nt, SensorSubSampling, SensorStart) * DT}
             if ReturnSensorSeries:
-                sens = eng.sensors()
-                for q, name in enumerate(eng.selS):
+                sens = solver.sensors()
+                for q, name in enumerate(solver.selS):
                     Sensor[name] = sens[q]
-            InputParam = {'IndexSensorMap': eng.sensor_index(), 'DT': DT, 'nt': nt,
-                          'device_bytes': eng.device_bytes, 'timing': self.last_timing, 'placement': eng.placement_note()}
+            InputParam = {'IndexSensorMap': solver.sensor_index(), 'DT': DT, 'nt': nt,
+                          'device_bytes': solver.device_bytes, 'timing': self.last_timing}
+            if grouped:
+                InputParam['devices'] = list(devices)
+                InputParam['slabs'] = [solver.slab(r)[:3] for r in range(solver.size)]
+                InputParam['placement'] = [solver.slab(r)[3].placement_note() for r in range(solver.size)]
+            else:
+                InputParam['placement'] = solver.placement_note()
             if ReturnSensorDFT:
                 # extension: what CalculatePhaseData extracts from the sensor block
                 # (BASE:2498-2520), computed on the device
-                F, pk = eng.sensor_dft(Frequency)
-                InputParam['SensorDFT'] = {name: F[q] for q, name in enumerate(eng.selS)}
-                InputParam['SensorPeak'] = {name: pk[q] for q, name in enumerate(eng.selS)}
-            LastMap = {name: eng.get_map(KIND_LAST, name) for name in eng.selR}
+                F, pk = solver.sensor_dft(Frequency)
+                InputParam['SensorDFT'] = {name: F[q] for q, name in enumerate(solver.selS)}
+                InputParam['SensorPeak'] = {name: pk[q] for q, name in enumerate(solver.selS)}
+            LastMap = {name: solver.get_map(KIND_LAST, name) for name in solver.selR}
             out = [Sensor, LastMap]
             if SelRMSorPeak & 1:
-                out.append({name: eng.get_map(KIND_RMS, name) for name in eng.selR})
+                out.append({name: solver.get_map(KIND_RMS, name) for name in solver.selR})
             if SelRMSorPeak & 2:
-                out.append({name: eng.get_map(KIND_PEAK, name) for name in eng.selR})
+                out.append({name: solver.get_map(KIND_PEAK, name) for name in solver.selR})
             out.append(InputParam)
         finally:
-            eng.close()
+            solver.close()
             if not self._keepPlacementCache:
                 _engine.placement_cache_release()
         if not SILENT and self.last_timing['total_ms'] > 0:
-            print('HIP FDTD: %d steps, %.1f Mvoxel-steps/s' % (
-                nt, self.last_timing['voxel_steps'] / self.last_timing['total_ms'] / 1e3))
-        return tuple(out)
-
-    # ------------------------------------------------------------------------------------------
-    def _run_group(self, devices, MaterialMap, ml, Frequency, SourceMap, PulseSource, SpatialStep, DT, nt, SensorMap, Ox, Oy, Oz,
-                   NDelta, ReflectionLimit, QfactorCorrection, QCorrection, TypeSource, SelRMSorPeak, SelMapsRMSPeakList,
-                   SelMapsSensorsList, SensorSubSampling, SensorStart, ReflectorMask, SILENT, ReturnSensorDFT, ReturnSensorSeries):
-        """The same call on several devices: whole-domain arrays in, whole-domain results out (bfd_group_*)."""
-        if not ReturnSensorSeries and not ReturnSensorDFT:
-            raise ValueError('ReturnSensorSeries=False needs ReturnSensorDFT=True')
-        N1, N2, N3 = MaterialMap.shape
-        grp = _engine.Group(devices, N1, N2, N3, ml.shape[0], SpatialStep, DT, Frequency, nt, NDelta=NDelta,
-                            reflectionLimit=ReflectionLimit, typeSource=TypeSource, sensorSub=SensorSubSampling,
-                            sensorStart=SensorStart, selRMSorPeak=SelRMSorPeak, selMapsRMS=SelMapsRMSPeakList,
-                            selMapsSensors=SelMapsSensorsList, qfactorCorrection=QfactorCorrection,
-                            kernelVariant=self._kernelVariant, sensorMode=1 if (ReturnSensorDFT and not ReturnSensorSeries) else 0)
-        try:
-            grp.set_materials(ml, QCorrection)
-            grp.set_material_map(MaterialMap)
-            if ReflectorMask is not None:
-                grp.set_reflector(ReflectorMask)
-            lin, row, wx, wy, wz = compact_sources(np.asarray(SourceMap), Ox, Oy, Oz)
-            grp.set_sources(lin, row, wx, wy, wz, PulseSource)
-            grp.set_sensor_map(SensorMap)
-            grp.timing_begin()
-            grp.run(nt)
-            self.last_timing = grp.timing_end()
-            self.last_timing['voxel_steps'] = float(N1) * N2 * N3 * nt
-            Sensor = {'time': sensor_steps(nt, SensorSubSampling, SensorStart) * DT}
-            if ReturnSensorSeries:
-                sens = grp.sensors()
-                for q, name in enumerate(grp.selS):
-                    Sensor[name] = sens[q]
-            InputParam = {'IndexSensorMap': grp.sensor_index(), 'DT': DT, 'nt': nt, 'device_bytes': grp.device_bytes,
-                          'timing': self.last_timing, 'devices': list(devices),
-                          'slabs': [grp.slab(r)[:3] for r in range(grp.size)],
-                          'placement': [grp.slab(r)[3].placement_note() for r in range(grp.size)]}
-            if ReturnSensorDFT:
-                F, pk = grp.sensor_dft(Frequency)
-                InputParam['SensorDFT'] = {name: F[q] for q, name in enumerate(grp.selS)}
-                InputParam['SensorPeak'] = {name: pk[q] for q, name in enumerate(grp.selS)}
-            LastMap = {name: grp.get_map(KIND_LAST, name) for name in grp.selR}
-            out = [Sensor, LastMap]
-            if SelRMSorPeak & 1:
-                out.append({name: grp.get_map(KIND_RMS, name) for name in grp.selR})
-            if SelRMSorPeak & 2:
-                out.append({name: grp.get_map(KIND_PEAK, name) for name in grp.selR})
-            out.append(InputParam)
-        finally:
-            grp.close()
-            if not self._keepPlacementCache:
-                _engine.placement_cache_release()
-        if not SILENT and self.last_timing['total_ms'] > 0:
-            print('HIP FDTD: %d steps on %d slabs, %.1f Mvoxel-steps/s' % (
-                nt, len(devices), self.last_timing['voxel_steps'] / self.last_timing['total_ms'] / 1e3))
+            print('HIP FDTD: %d steps%s, %.1f Mvoxel-steps/s' % (
+                nt, ' on %d slabs' % len(devices) if grouped else '', self.last_timing['voxel_steps'] / self.last_timing['total_ms'] / 1e3))
         return tuple(out)

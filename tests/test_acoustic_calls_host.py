@@ -28,7 +28,7 @@ def lib():
 def test_entries_are_exported_and_bound(lib):
     for entry in ENTRIES:
         assert entry in _engine.ABI_SYMBOLS and hasattr(lib, entry) and getattr(lib, entry).argtypes
-    assert lib.bfd_abi_version() == 7
+    assert lib.bfd_abi_version() == _engine.ABI_VERSION
     assert C.sizeof(_engine.PackSpec) == 4 * 15 + 4 + 16 and _engine.PackSpec.ampScale.offset == 64       # int32 x 15, padding, two doubles
 
 

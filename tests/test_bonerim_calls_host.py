@@ -19,7 +19,7 @@ def lib():
 
 
 def test_abi_symbol_and_version(lib):
-    assert lib.bfd_abi_version() == 7
+    assert lib.bfd_abi_version() == _engine.ABI_VERSION
     assert TC.ENTRY in _engine.ABI_SYMBOLS and hasattr(lib, TC.ENTRY)
 
 

@@ -18,7 +18,7 @@ def lib():
 
 
 def test_abi_symbols_and_version(lib):
-    assert lib.bfd_abi_version() == 7
+    assert lib.bfd_abi_version() == _engine.ABI_VERSION
     for entry in TC.ENTRIES:
         assert entry in _engine.ABI_SYMBOLS and hasattr(lib, entry), entry
 

@@ -295,7 +295,7 @@ def test_abi_symbols_and_version():
         import __graft_entry__
         __graft_entry__.build()
     lib = _engine.load_library()
-    assert lib.bfd_abi_version() == 7
+    assert lib.bfd_abi_version() == _engine.ABI_VERSION
     for entry in TC.ENTRIES:
         assert entry in _engine.ABI_SYMBOLS and hasattr(lib, entry), entry
 

@@ -152,4 +152,4 @@ def test_library_exports_separable_entry_points():
     lib = _engine.load_library()
     for name in ('bfd_set_sources_separable', 'bfd_group_set_sources_separable'):
         assert hasattr(lib, name) and name in _engine.ABI_SYMBOLS
-    assert lib.bfd_abi_version() == 7
+    assert lib.bfd_abi_version() == _engine.ABI_VERSION

@@ -317,7 +317,7 @@ def lib():
 @pytest.mark.parametrize('entry', TC.ENTRIES)
 def test_abi_refuses_before_a_device_in_the_header_s_order(lib, entry):
     """-1 with the text of the first fault the header lists, whether or not a device exists, with every output and kernelMs untouched."""
-    assert entry in _engine.ABI_SYMBOLS and hasattr(lib, entry) and lib.bfd_abi_version() == 7
+    assert entry in _engine.ABI_SYMBOLS and hasattr(lib, entry) and lib.bfd_abi_version() == _engine.ABI_VERSION
     words = {n: w for n, w, _ in TC.faults(entry)}
     for names, first in TC.ordered_plants(entry):
         c = TC.planted(entry, names)
